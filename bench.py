@@ -8,8 +8,18 @@ forward + DiceCE + backward + AdamW, bf16, per-GPU batch 2 (configs[1]; configs[
     python bench.py --workload swin_unetr        # configs[3]: Swin-UNETR-48 (reference encoder), same step
     python bench.py --workload sliding_window    # configs[4]: 512^3 sliding-window inference, roi 96^3, overlap 0.5
 
-Prints ONE JSON line on rank 0; `config.workload`, the FLOP / byte model, `roofline` (dominant kernel, measured with HIP
-events in this process) and `cpu_baseline` (the oracle on the host cores, bounded sample) all follow `--workload`.
+Prints ONE JSON line on rank 0; `config.workload` and the FLOP / byte model follow `--workload`.  A plain run sets up,
+warms up, times the steps and prints the line.  `--full` adds the legs measured beyond the headline: `roofline`
+(dominant kernel, measured with HIP events in this process), `cpu_baseline` (the oracle on the host cores, bounded
+sample), the 512^3 `sliding_window` half of the default line and, with N > 1, the timed all-reduce in
+`config.distributed`.
+
+    python bench.py --full                       # the line with every leg
+    python bench.py --steps 20 --warmup 5 --dump-outputs DIR
+
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32): for the training workloads
+`loss`, `logits` (the network output) and `params` (the flat parameter buffer after the optimiser step); for
+`sliding_window` the blended `logits`.  Arrays above DUMP_MAX_ELEMS keep a fixed, seeded sample of their elements.
 """
 from __future__ import annotations
 
@@ -19,6 +29,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -115,6 +126,25 @@ def synth_batch(batch, size, n_cls, device, seed):
         y[r < 0.9 * (n_cls - c) / (n_cls - 1)] = c
     y = y[None, None].repeat(batch, 1, 1, 1, 1)
     return x.to(device), y.to(device)
+
+
+DUMP_MAX_ELEMS = 6 << 20   # per array (24 MB of float32): at most two such arrays plus a scalar stay under 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each tensor of `arrays` (name -> tensor) as out_dir/<name>.npy in float32, flattened in logical (NCDHW)
+    order when it is sampled.  A tensor of more than DUMP_MAX_ELEMS elements keeps one element per stratum of
+    numel // DUMP_MAX_ELEMS consecutive ones, at an offset drawn from a fixed seed: the same positions on every run and
+    every build for the same shape."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            stride = t.numel() // DUMP_MAX_ELEMS
+            offs = np.random.default_rng(0).integers(0, stride, DUMP_MAX_ELEMS)
+            idx = torch.from_numpy(np.arange(DUMP_MAX_ELEMS, dtype=np.int64) * stride + offs).to(t.device)
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def cpu_baseline_train(workload, batch, size, n_cls, budget_s=40.0):
@@ -270,10 +300,10 @@ def roofline_from_timer(summ, ksumm, dtype, step_ms, instr_steps, top=5):
     return r
 
 
-def measure_sliding_window(args, dev, dtype, world, rank, steps, warmup, with_roofline=True):
+def measure_sliding_window(args, dev, dtype, world, rank, steps, warmup, with_roofline=True, dump_dir=None):
     """512^3 sliding-window inference (roi 96^3, overlap 0.5, gaussian; 1000 windows) with the UNet in eval mode: the second
     half of BASELINE.json's metric.  N > 1: window batches dealt round-robin to the ranks, one all-gather of logits per
-    step, every rank blends.  Returns the result dict on rank 0 (None elsewhere)."""
+    step, every rank blends.  Returns (result dict, window count) on rank 0 (None elsewhere)."""
     from medicalsemseg_amd import hip
     from medicalsemseg_amd.engine import utils as U
     from medicalsemseg_amd.models.unet import UNet
@@ -308,6 +338,8 @@ def measure_sliding_window(args, dev, dtype, world, rank, steps, warmup, with_ro
         dt = float(t.item())
     if rank != 0:
         return None
+    if dump_dir:
+        dump_outputs(dump_dir, {"logits": out})
     value = steps / dt
     w = WORK["sliding_window"]
     nsteps = -(-n_win // (args.sw_batch * world))
@@ -345,10 +377,11 @@ def measure_sliding_window(args, dev, dtype, world, rank, steps, warmup, with_ro
 
 
 def bench_sliding_window(args, dev, dtype, world, rank):
-    r = measure_sliding_window(args, dev, dtype, world, rank, args.steps, args.warmup)
+    r = measure_sliding_window(args, dev, dtype, world, rank, args.steps, args.warmup, with_roofline=args.full,
+                               dump_dir=args.dump_outputs)
     if rank == 0:
         res, n_win = r
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline_sw(args.size, args.classes, n_win)
         print(json.dumps(res), flush=True)
     if world > 1:
@@ -403,7 +436,7 @@ def main():
     ap.add_argument("--size", type=int, default=96)
     ap.add_argument("--classes", type=int, default=3)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true", help="do not replay the step from a captured hipGraph")
     ap.add_argument("--split-graph", action="store_true",
                     help="single GPU: use the multi-GPU replay structure (graph A | eager gap | graph B)")
@@ -412,11 +445,17 @@ def main():
                     help="unet = the headline (BASELINE configs[1]); swin_unetr = configs[3]; sliding_window = configs[4]; "
                          "segformer3d / swin_depth / swinception = the SURVEY 8(f) N3 / N4 model families")
     ap.add_argument("--no-sliding-window", action="store_true",
-                    help="default workload only: skip the 512^3 sliding-window leg (the second half of BASELINE.json's metric)")
-    ap.add_argument("--sw-steps", type=int, default=3, help="timed 512^3 volumes of the sliding-window leg of the default line")
-    ap.add_argument("--all-groups", action="store_true", help="list every timer group in roofline.groups, not the top five")
+                    help="--full, default workload only: skip the 512^3 sliding-window leg (the second half of BASELINE.json's "
+                         "metric)")
+    ap.add_argument("--sw-steps", type=int, default=3, help="timed 512^3 volumes of the sliding-window leg of the --full default line")
+    ap.add_argument("--all-groups", action="store_true", help="--full: list every timer group in roofline.groups, not the top five")
     ap.add_argument("--sw-size", type=int, default=512)
     ap.add_argument("--sw-batch", type=int, default=8)   # windows per forward
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: roofline (instrumented eager steps after the timed ones), "
+                         "the sliding-window leg of the default workload, the CPU baseline, the timed all-reduce (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 3 if args.workload == "sliding_window" else 20
@@ -498,7 +537,7 @@ def main():
         gsync.finish()
         opt.step()
         opt.zero_grad()
-        return loss
+        return loss, out
 
     def sync():
         if world > 1:
@@ -506,7 +545,7 @@ def main():
         torch.cuda.synchronize()
 
     for _ in range(max(args.warmup, 1)):
-        loss = step()
+        loss, out = step()
     sync()
     # Replay the step from captured hipGraphs; the work per replay is exactly the eager step's.  Single GPU: ONE graph
     # (forward + loss + backward + AdamW).  Multi-GPU (or --split-graph): graph A = forward + loss + backward head, the
@@ -521,7 +560,7 @@ def main():
         out = net((x, None, None))
         loss = crit(out, y)
         loss.backward()
-        return loss
+        return loss, out
 
     def part_b():
         opt.step()
@@ -549,10 +588,10 @@ def main():
             graph = torch.cuda.CUDAGraph()
             if not split:
                 with torch.cuda.graph(graph):
-                    static_loss = step()
+                    static_loss, static_out = step()
             else:
                 with torch.cuda.graph(graph):
-                    static_loss = part_a()
+                    static_loss, static_out = part_a()
                 if two_phase:
                     gsync.start()
                     graph_tail = torch.cuda.CUDAGraph()
@@ -574,18 +613,21 @@ def main():
     if graph is not None:
         for _ in range(args.steps):
             replay()
-        loss = static_loss
+        loss, out = static_loss, static_out
     else:
-        hip.TIMER.enabled = True
-        hip.ktimer_enable(True)
+        # --full: the eager steps themselves are the roofline's instrumented ones
+        hip.TIMER.enabled = args.full
+        hip.ktimer_enable(args.full)
         for _ in range(args.steps):
-            loss = step()
+            loss, out = step()
     sync()
     hip.ktimer_enable(False)
     dt = time.perf_counter() - t0
     hip.TIMER.enabled = False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(1), "logits": out, "params": opt.flat_param})
     instr_steps = args.steps
-    if graph is not None:
+    if args.full and graph is not None:
         instr_steps = min(args.steps, 5)
         # per-kernel HIP-event timing needs eager launches: instrument a few extra steps right after the timed region
         hip.TIMER.records.clear()
@@ -602,11 +644,11 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     loss_v = float(loss.detach())
-    facts = dist_facts(dev, world, rank, opt.flat_grad.numel() * 4)
-    # The other half of BASELINE.json's metric ("... & 512^3 sliding-window vols/sec"): part of the default line so that
-    # the driver's run times both halves.  All ranks take part (window batches are sharded over them).
+    facts = dist_facts(dev, world, rank, opt.flat_grad.numel() * 4) if args.full else {"world_size": world}
+    # The other half of BASELINE.json's metric ("... & 512^3 sliding-window vols/sec"): part of the default line under
+    # --full.  All ranks take part (window batches are sharded over them).
     sw_res = None
-    if args.workload == "unet" and not args.no_sliding_window:
+    if args.full and args.workload == "unet" and not args.no_sliding_window:
         sw_res = measure_sliding_window(args, dev, dtype, world, rank, args.sw_steps, 1, with_roofline=False)
 
     vols = args.batch * args.steps * world
@@ -629,8 +671,9 @@ def main():
     if rank == 0:
         scale = (args.size / 96.0) ** 3
         step_ms = dt * 1e3 / args.steps
-        res["roofline"] = roofline_from_timer(hip.TIMER.summary(), hip.ktimer_summary(), args.dtype, step_ms, instr_steps,
-                                              top=1000 if args.all_groups else 5)
+        if args.full:
+            res["roofline"] = roofline_from_timer(hip.TIMER.summary(), hip.ktimer_summary(), args.dtype, step_ms,
+                                                  instr_steps, top=1000 if args.all_groups else 5)
         if w["gflop_per_vol"] is not None:
             res["model_tflops"] = round(value / world * w["gflop_per_vol"] * scale / 1e3, 2)
             res["hbm_roofline_frac_algorithmic"] = round(value / world * w["gb_per_vol_bf16"] * scale *
@@ -641,7 +684,7 @@ def main():
                                      "warmup": r["warmup"], "ms_per_step": r["ms_per_step"], "scaling": r["scaling"],
                                      "model_tflops": r["model_tflops"], "launch": r["launch"],
                                      "hbm_roofline_frac_algorithmic": r["hbm_roofline_frac_algorithmic"], "config": r["config"]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline_train(args.workload, args.batch, args.size, args.classes)
             if "counted_gflop_per_vol" in res["cpu_baseline"]:
                 res["model_tflops"] = round(value * res["cpu_baseline"]["counted_gflop_per_vol"] / 1e3, 2)

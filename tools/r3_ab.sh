@@ -7,7 +7,7 @@ for round in 1 2; do
   for envs in "$@"; do
     i=$((i+1))
     [ "$envs" = "-" ] && envs=""
-    env $envs python bench.py --no-cpu-baseline --no-sliding-window --all-groups --steps 30 --warmup 5 > $out/v${i}_r$round.json 2> $out/v${i}_r$round.err || tail -3 $out/v${i}_r$round.err
+    env $envs python bench.py --full --no-cpu-baseline --no-sliding-window --all-groups --steps 30 --warmup 5 > $out/v${i}_r$round.json 2> $out/v${i}_r$round.err || tail -3 $out/v${i}_r$round.err
   done
 done
 python3 - "$out" "$@" <<'PY'

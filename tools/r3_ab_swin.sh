@@ -7,7 +7,7 @@ for round in 1 2; do
   for envs in "$@"; do
     i=$((i+1))
     [ "$envs" = "-" ] && envs=""
-    env $envs python bench.py --workload $wl --no-cpu-baseline --all-groups --steps 10 --warmup 3 > $out/v${i}_r$round.json 2> $out/v${i}_r$round.err || tail -3 $out/v${i}_r$round.err
+    env $envs python bench.py --full --workload $wl --no-cpu-baseline --all-groups --steps 10 --warmup 3 > $out/v${i}_r$round.json 2> $out/v${i}_r$round.err || tail -3 $out/v${i}_r$round.err
   done
 done
 python3 - "$out" "$@" <<'PY'
