@@ -430,6 +430,36 @@ int msseg_window_attention_bwd_ws(const void* qkv, const float* qkv_bias, const 
                                   const float* lse, const void* dout, void* dqkv, float* dtable, int B, int S, int H, int W,
                                   int C, int heads, int ws, int shift, int dtype, void* workspace, size_t workspace_bytes,
                                   msseg_stream_t stream);
+/* Forms with one bias table PER SAMPLE: sample b's windows read table + b * table_stride and the backward ACCUMULATES the
+ * table gradient of sample b into dtable + b * table_stride (caller zero-fills; table_stride >= (2*bias_ws-1)^3 * heads, or
+ * 0 = the calls above).  The workspace path then sums dS over the windows of one sample at a time, so its workspace grows
+ * with B: size it with msseg_window_attention_bwd3_workspace_bytes. */
+int msseg_window_attention_fwd3(const void* qkv, const float* qkv_bias, const float* table, void* out, float* lse, int B,
+                                int S, int H, int W, int C, int heads, int ws, int shift, int bias_ws, long long table_stride,
+                                int dtype, msseg_stream_t stream);
+int msseg_window_attention_bwd3(const void* qkv, const float* qkv_bias, const float* table, const void* out,
+                                const float* lse, const void* dout, void* dqkv, float* dtable, int B, int S, int H, int W,
+                                int C, int heads, int ws, int shift, int bias_ws, long long table_stride, int dtype,
+                                void* workspace, size_t workspace_bytes, msseg_stream_t stream);
+size_t msseg_window_attention_bwd3_workspace_bytes(int B, int S, int H, int W, int C, int heads, int ws, int shift,
+                                                   int bias_ws, long long table_stride, int dtype);
+/* Spacing-conditioned relative position bias (swin_nnformer.py:89-97, :157-166, `--rel_pos_bias_affine`): the per-sample
+ * tables T [B][M3][heads] fp32 = table [M3][heads] + lin_b[0] + sum_k lin_w[k] * aff[b][k] * emb [M3][heads][3], for the
+ * *3 calls above with table_stride = M3 * heads.  aff [B][3] fp32 holds one row per sample.  Every input is read on the
+ * device (no host synchronisation). */
+int msseg_rel_bias_affine_fold(const float* table, const float* emb, const float* lin_w, const float* lin_b,
+                               const float* aff, float* T, int B, int M3, int heads, msseg_stream_t stream);
+/* From the per-sample table gradient dT [B][M3][heads]: dtable [M3][heads], demb [M3][heads][3], dlin_w [3], dlin_b [1]
+ * (each nullable = not wanted).  Each is overwritten, or added to when its MSSEG_AFFINE_ACC_* bit is set in `flags`.
+ * Fixed-order sums, no atomics: bit-identical from run to run.  workspace: msseg_rel_bias_affine_grad_workspace_bytes. */
+size_t msseg_rel_bias_affine_grad_workspace_bytes(int M3, int heads);
+#define MSSEG_AFFINE_ACC_TABLE 1
+#define MSSEG_AFFINE_ACC_EMB 2
+#define MSSEG_AFFINE_ACC_LIN_W 4
+#define MSSEG_AFFINE_ACC_LIN_B 8
+int msseg_rel_bias_affine_grad(const float* dT, const float* emb, const float* lin_w, const float* aff, float* dtable,
+                               float* demb, float* dlin_w, float* dlin_b, int B, int M3, int heads, int flags,
+                               void* workspace, size_t workspace_bytes, msseg_stream_t stream);
 /* LayerNorm over the channel dim of rows x C (nn.LayerNorm, eps 1e-5); mean/rstd [rows] saved for backward. */
 int msseg_layernorm_fwd(const void* x, long long ldx, const float* gamma, const float* beta, void* y, long long ldy,
                         float* mean, float* rstd, long long rows, int C, float eps, int dtype, msseg_stream_t stream);

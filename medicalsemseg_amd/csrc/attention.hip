@@ -37,6 +37,7 @@ __global__ __launch_bounds__(256) void win_attn_fwd_kernel(const AttnParams p) {
         const int wx = w % p.nWw, wy = (w / p.nWw) % p.nWh, wz = w / (p.nWw * p.nWh);
         const T* qkv = (const T*)p.qkv + (long long)b * p.S * p.H * p.W * 3 * p.C;
         T* out = (T*)p.out + (long long)b * p.S * p.H * p.W * p.C;
+        const float* table = p.table + b * p.tab_stride;
         __syncthreads();
         for (int i = threadIdx.x; i < p.N; i += 256) {
             int rg, cd;
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(256) void win_attn_fwd_kernel(const AttnParams p) {
         }
         for (int h = blockIdx.y; h < p.heads; h += gridDim.y) {
             __syncthreads();
-            for (int i = threadIdx.x; i < p.M3; i += 256) tabS[i] = p.table[(long long)i * p.heads + h];
+            for (int i = threadIdx.x; i < p.M3; i += 256) tabS[i] = table[(long long)i * p.heads + h];
             for (int i = threadIdx.x; i < p.N * HD; i += 256) {
                 const int j = i / HD, e = i % HD;
                 const int t = tok[j];
@@ -135,6 +136,7 @@ __global__ __launch_bounds__(256) void win_attn_bwd_kernel(const AttnParams p) {
         const T* outp = (const T*)p.out + b * vol * p.C;
         const T* dout = (const T*)p.dout + b * vol * p.C;
         T* dqkv = (T*)p.dqkv + b * vol * 3 * p.C;
+        const float* table = p.table + b * p.tab_stride;
         __syncthreads();
         for (int i = threadIdx.x; i < p.N; i += 256) {
             int rg, cd;
@@ -145,7 +147,7 @@ __global__ __launch_bounds__(256) void win_attn_bwd_kernel(const AttnParams p) {
         for (int h = blockIdx.y; h < p.heads; h += gridDim.y) {
             __syncthreads();
             float* dtab = p.dtab_all_heads ? dtabS + h * p.M3 : dtabS;
-            for (int i = threadIdx.x; i < p.M3; i += 256) tabS[i] = p.table[(long long)i * p.heads + h];
+            for (int i = threadIdx.x; i < p.M3; i += 256) tabS[i] = table[(long long)i * p.heads + h];
             for (int i = threadIdx.x; i < p.N * HD; i += 256) {
                 const int j = i / HD, e = i % HD;
                 const int t = tok[j];
@@ -234,13 +236,13 @@ __global__ __launch_bounds__(256) void win_attn_bwd_kernel(const AttnParams p) {
                 __syncthreads();
                 for (int i = threadIdx.x; i < p.M3; i += 256) {
                     const float v = dtabS[i];
-                    if (v != 0.f) atomicAdd(&p.dtable[(long long)i * p.heads + h], v);
+                    if (v != 0.f) atomicAdd(&p.dtable[b * p.tab_stride + (long long)i * p.heads + h], v);
                     dtabS[i] = 0.f;
                 }
             }
         }
     }
-    if (p.dtable && p.dtab_all_heads) {
+    if (p.dtable && p.dtab_all_heads) {   // (never with per-sample tables: the host clears dtab_all_heads for them)
         __syncthreads();
         for (int i = threadIdx.x; i < p.heads * p.M3; i += 256) {
             const float v = dtabS[i];
@@ -546,10 +548,25 @@ int msseg_window_attention_fwd(const void* qkv, const float* qkv_bias, const flo
 int msseg_window_attention_fwd2(const void* qkv, const float* qkv_bias, const float* table, void* out, float* lse, int B,
                                 int S, int H, int W, int C, int heads, int ws, int shift, int bias_ws, int dtype,
                                 msseg_stream_t stream) {
+    return msseg_window_attention_fwd3(qkv, qkv_bias, table, out, lse, B, S, H, W, C, heads, ws, shift, bias_ws, 0, dtype,
+                                       stream);
+}
+
+static int check_tab_stride(const AttnParams& p, long long table_stride) {
+    if (table_stride != 0 && table_stride < (long long)p.M3 * p.heads)
+        MSSEG_FAIL(MSSEG_EINVAL, "window_attention: table stride %lld smaller than one table (%d x %d)", table_stride, p.M3,
+                   p.heads);
+    return MSSEG_OK;
+}
+
+int msseg_window_attention_fwd3(const void* qkv, const float* qkv_bias, const float* table, void* out, float* lse, int B,
+                                int S, int H, int W, int C, int heads, int ws, int shift, int bias_ws, long long table_stride,
+                                int dtype, msseg_stream_t stream) {
     if (!qkv || !table || !out || !lse) MSSEG_FAIL(MSSEG_EINVAL, "window_attention_fwd: null pointer");
     AttnParams p{};
     if (int rc = fill_attn(p, B, S, H, W, C, heads, ws, shift, bias_ws)) return rc;
-    p.qkv = qkv; p.qkv_bias = qkv_bias; p.table = table; p.out = out; p.lse = lse;
+    if (int rc = check_tab_stride(p, table_stride)) return rc;
+    p.qkv = qkv; p.qkv_bias = qkv_bias; p.table = table; p.out = out; p.lse = lse; p.tab_stride = table_stride;
     const size_t smem = (size_t)p.N * p.hd * 2 * 4 + (size_t)p.M3 * 4 + (size_t)p.N * 3 * 4;
     if (smem > 160 * 1024) MSSEG_FAIL(MSSEG_EINVAL, "window_attention_fwd: window too large for LDS");
     if (dtype == MSSEG_BF16 && (p.hd == 16 || p.hd == 32) && p.N <= 352 && p.M3 <= 4095 && (C % 8) == 0 &&
@@ -581,6 +598,15 @@ size_t msseg_window_attention_bwd_workspace_bytes(int B, int S, int H, int W, in
     return msseg_window_attention_bwd_mfma_ws_bytes(p);
 }
 
+size_t msseg_window_attention_bwd3_workspace_bytes(int B, int S, int H, int W, int C, int heads, int ws, int shift,
+                                                   int bias_ws, long long table_stride, int dtype) {
+    AttnParams p{};
+    if (fill_attn(p, B, S, H, W, C, heads, ws, shift, bias_ws) != MSSEG_OK) return 0;
+    p.tab_stride = table_stride;
+    if (!attn_bwd_on_mfma(p, C, dtype) || getenv("MSSEG_ATTN_BWD_NO_WS")) return 0;
+    return msseg_window_attention_bwd_mfma_ws_bytes(p);
+}
+
 int msseg_window_attention_bwd_ws(const void* qkv, const float* qkv_bias, const float* table, const void* out,
                                   const float* lse, const void* dout, void* dqkv, float* dtable, int B, int S, int H, int W,
                                   int C, int heads, int ws, int shift, int dtype, void* workspace, size_t workspace_bytes,
@@ -593,11 +619,20 @@ int msseg_window_attention_bwd2(const void* qkv, const float* qkv_bias, const fl
                                 const float* lse, const void* dout, void* dqkv, float* dtable, int B, int S, int H, int W,
                                 int C, int heads, int ws, int shift, int bias_ws, int dtype, void* workspace,
                                 size_t workspace_bytes, msseg_stream_t stream) {
+    return msseg_window_attention_bwd3(qkv, qkv_bias, table, out, lse, dout, dqkv, dtable, B, S, H, W, C, heads, ws, shift,
+                                       bias_ws, 0, dtype, workspace, workspace_bytes, stream);
+}
+
+int msseg_window_attention_bwd3(const void* qkv, const float* qkv_bias, const float* table, const void* out,
+                                const float* lse, const void* dout, void* dqkv, float* dtable, int B, int S, int H, int W,
+                                int C, int heads, int ws, int shift, int bias_ws, long long table_stride, int dtype,
+                                void* workspace, size_t workspace_bytes, msseg_stream_t stream) {
     if (!qkv || !table || !out || !lse || !dout || !dqkv) MSSEG_FAIL(MSSEG_EINVAL, "window_attention_bwd: null pointer");
     AttnParams p{};
     if (int rc = fill_attn(p, B, S, H, W, C, heads, ws, shift, bias_ws)) return rc;
+    if (int rc = check_tab_stride(p, table_stride)) return rc;
     p.qkv = qkv; p.qkv_bias = qkv_bias; p.table = table; p.out = (void*)out; p.lse = (float*)lse; p.dout = dout;
-    p.dqkv = dqkv; p.dtable = dtable;
+    p.dqkv = dqkv; p.dtable = dtable; p.tab_stride = table_stride;
     if (attn_bwd_on_mfma(p, C, dtype)) {
         // bf16: all five contractions of the backward on the matrix cores (attention_mfma.hip); with a workspace the
         // table gradient is a window sum + gather instead of LDS float atomics
@@ -610,7 +645,8 @@ int msseg_window_attention_bwd2(const void* qkv, const float* qkv_bias, const fl
         return msseg_window_attention_bwd_mfma(p, (hipStream_t)stream);
     }
     const size_t base = (size_t)p.N * p.hd * 4 * 4 + (size_t)p.N * 5 * 4 + (size_t)p.M3 * 4;
-    p.dtab_all_heads = (base + (size_t)heads * p.M3 * 4 <= 96 * 1024) ? 1 : 0;
+    // (per-sample tables: the LDS sums are flushed after every (window, head), into the table of that window's sample)
+    p.dtab_all_heads = (table_stride == 0 && base + (size_t)heads * p.M3 * 4 <= 96 * 1024) ? 1 : 0;
     const size_t smem = base + (size_t)(p.dtab_all_heads ? heads : 1) * p.M3 * 4;
     if (smem > 160 * 1024) MSSEG_FAIL(MSSEG_EINVAL, "window_attention_bwd: window too large for LDS (%zu bytes)", smem);
     if (dtype == MSSEG_F32) ATTN_LAUNCH(win_attn_bwd_kernel, float, smem);

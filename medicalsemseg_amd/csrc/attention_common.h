@@ -8,6 +8,8 @@ struct AttnParams {
     const void* qkv;      // [B, S, H, W, 3C]  channel = which*C + head*hd + e
     const float* qkv_bias;  // [3C] or null (value of padded tokens)
     const float* table;   // relative position bias table [(2ws-1)^3][heads]
+    long long tab_stride; // 0: one table for all samples; else table / dtable of sample b start at + b * tab_stride (the
+                          // per-sample tables of the spacing-conditioned bias, rel_bias_affine.hip)
     void* out;            // [B, S, H, W, C]
     float* lse;           // [B, nW, heads, N]   log-sum-exp per query (saved for backward)
     const void* dout;     // backward: [B,S,H,W,C]

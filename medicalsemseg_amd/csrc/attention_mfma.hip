@@ -42,6 +42,7 @@ __global__ __launch_bounds__(256) void win_attn_fwd_mfma_kernel(const AttnParams
         const int wx = w % p.nWw, wy = (w / p.nWw) % p.nWh, wz = w / (p.nWw * p.nWh);
         const bf16_t* qkv = (const bf16_t*)p.qkv + (long long)b * p.S * p.H * p.W * C3;
         bf16_t* out = (bf16_t*)p.out + (long long)b * p.S * p.H * p.W * p.C;
+        const float* table = p.table + b * p.tab_stride;
         __syncthreads();
         for (int i = tid; i < NP; i += 256) {
             if (i < p.N) {
@@ -55,7 +56,7 @@ __global__ __launch_bounds__(256) void win_attn_fwd_mfma_kernel(const AttnParams
         }
         for (int h = blockIdx.y; h < p.heads; h += gridDim.y) {   // heads split over grid.y when there are few windows
             __syncthreads();
-            for (int i = tid; i < p.M3; i += 256) tabS[i] = p.table[(long long)i * p.heads + h];
+            for (int i = tid; i < p.M3; i += 256) tabS[i] = table[(long long)i * p.heads + h];
             // stage Q, K (row-major) and V (transposed): one 16-byte chunk (8 channels) per thread-iteration
             constexpr int CPT = HD / 8;   // chunks per token per matrix
             for (int i = tid; i < NP * CPT * 3; i += 256) {
@@ -239,6 +240,7 @@ __global__ __launch_bounds__(256) void win_attn_bwd_mfma_kernel(const AttnParams
         const bf16_t* outp = (const bf16_t*)p.out + b * vol * p.C;
         const bf16_t* dout = (const bf16_t*)p.dout + b * vol * p.C;
         bf16_t* dqkv = (bf16_t*)p.dqkv + b * vol * C3;
+        const float* table = p.table + b * p.tab_stride;
         __syncthreads();
         for (int i = tid; i < NP; i += 256) {
             if (i < p.N) {
@@ -252,7 +254,7 @@ __global__ __launch_bounds__(256) void win_attn_bwd_mfma_kernel(const AttnParams
         }
         for (int h = blockIdx.y; h < p.heads; h += gridDim.y) {   // heads split over grid.y when there are few windows
             __syncthreads();
-            for (int i = tid; i < p.M3; i += 256) { tabS[i] = p.table[(long long)i * p.heads + h]; dtabS[i] = 0.f; }
+            for (int i = tid; i < p.M3; i += 256) { tabS[i] = table[(long long)i * p.heads + h]; dtabS[i] = 0.f; }
             bf16_t* dsw = DSWS ? (bf16_t*)p.ds_ws + ((long long)wb * p.heads + h) * (NKT * NKT * 1024) + lane * 16 : nullptr;
             constexpr int CPT = HD / 8;
             for (int i = tid; i < NP * CPT * 4; i += 256) {   // q, k, v, dO
@@ -439,7 +441,7 @@ __global__ __launch_bounds__(256) void win_attn_bwd_mfma_kernel(const AttnParams
                 __syncthreads();
                 for (int i = tid; i < p.M3; i += 256) {
                     const float v = dtabS[i];
-                    if (v != 0.f) atomicAdd(&p.dtable[(long long)i * p.heads + h], v);
+                    if (v != 0.f) atomicAdd(&p.dtable[b * p.tab_stride + (long long)i * p.heads + h], v);
                 }
             }
         }
@@ -448,13 +450,16 @@ __global__ __launch_bounds__(256) void win_attn_bwd_mfma_kernel(const AttnParams
 
 // ---- table gradient without atomics (DSWS) ----
 // step 1: sum the bf16 dS tiles over the windows of one group; element order is the MFMA fragment order the backward
-// kernel wrote, identical for every window, so this is a plain strided sum (16 B per thread and window)
+// kernel wrote, identical for every window, so this is a plain strided sum (16 B per thread and window).  The windows are
+// cut into segments of `wps` consecutive windows (one segment in all; one per sample with per-sample tables) and each
+// segment into `gps` groups of `chunk` windows, so that no group crosses a segment boundary.
 __global__ __launch_bounds__(256) void attn_ds_window_sum_kernel(const bf16_t* __restrict__ ws, float* __restrict__ psum,
-                                                                 int nwin, int heads, int E, int chunk) {
+                                                                 int wps, int gps, int heads, int E, int chunk) {
     const int e8 = blockIdx.x * 256 + threadIdx.x;
     const int h = blockIdx.y, g = blockIdx.z;
     if (e8 * 8 >= E) return;
-    const int w0 = g * chunk, w1 = min(nwin, w0 + chunk);
+    const int seg0 = (g / gps) * wps;
+    const int w0 = seg0 + (g % gps) * chunk, w1 = min(seg0 + wps, w0 + chunk);
     float acc[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] = 0.f;
@@ -482,12 +487,16 @@ __global__ __launch_bounds__(256) void attn_ds_window_sum_kernel(const bf16_t* _
     *(float4*)(dst + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
 }
 
-// step 2: one workgroup per (table entry, head).  The entry's relative offset (dz, dy, dx) fixes the key of every query:
-// thread i reads the summed dS of (query i, key i - offset) from each group and the block adds them up in a fixed order.
+// step 2: one workgroup per (table entry, head, segment).  The entry's relative offset (dz, dy, dx) fixes the key of every
+// query: thread i reads the summed dS of (query i, key i - offset) from each group of the segment and the block adds them
+// up in a fixed order; segment s adds into dtable + s * tab_stride.
 __global__ __launch_bounds__(256) void attn_dtable_gather_kernel(const float* __restrict__ psum, float* __restrict__ dtable,
-                                                                 int groups, int heads, int nkt, int wsz, int N) {
+                                                                 int groups, int heads, int nkt, int wsz, int N,
+                                                                 long long tab_stride) {
     __shared__ float red[256];
     const int ti = blockIdx.x, h = blockIdx.y, i = threadIdx.x;
+    psum += (long long)blockIdx.z * groups * heads * nkt * nkt * 1024;
+    dtable += blockIdx.z * tab_stride;
     const int m = 2 * wsz - 1;
     const int dz = ti / (m * m) - (wsz - 1), dy = (ti / m) % m - (wsz - 1), dx = ti % m - (wsz - 1);
     float v = 0.f;
@@ -530,13 +539,14 @@ template <int HD, int NKT> int launch_bwd(const AttnParams& p, hipStream_t strea
     MSSEG_CHECK_LAUNCH("window_attention_bwd_mfma");
     if (dsws) {
         const int E = NKT * NKT * 1024;
-        const int groups = p.ds_groups;
-        const int chunk = (p.nwin_total + groups - 1) / groups;
-        hipLaunchKernelGGL(attn_ds_window_sum_kernel, dim3((E / 8 + 255) / 256, p.heads, groups), dim3(256), 0, stream,
-                           (const bf16_t*)p.ds_ws, p.ds_psum, p.nwin_total, p.heads, E, chunk);
+        const int nseg = p.tab_stride ? p.B : 1;           // per-sample tables: no group crosses a sample
+        const int wps = p.nwin_total / nseg, gps = p.ds_groups / nseg;
+        const int chunk = (wps + gps - 1) / gps;
+        hipLaunchKernelGGL(attn_ds_window_sum_kernel, dim3((E / 8 + 255) / 256, p.heads, p.ds_groups), dim3(256), 0, stream,
+                           (const bf16_t*)p.ds_ws, p.ds_psum, wps, gps, p.heads, E, chunk);
         MSSEG_CHECK_LAUNCH("attn_ds_window_sum");
-        hipLaunchKernelGGL(attn_dtable_gather_kernel, dim3(p.M3, p.heads), dim3(256), 0, stream, (const float*)p.ds_psum,
-                           p.dtable, groups, p.heads, NKT, p.bws, p.N);
+        hipLaunchKernelGGL(attn_dtable_gather_kernel, dim3(p.M3, p.heads, nseg), dim3(256), 0, stream, (const float*)p.ds_psum,
+                           p.dtable, gps, p.heads, NKT, p.bws, p.N, p.tab_stride);
         MSSEG_CHECK_LAUNCH("attn_dtable_gather");
     }
     return MSSEG_OK;
@@ -584,7 +594,14 @@ static int bwd_nkt(const AttnParams& p) {   // the NKT instantiation launch_bwd_
     return nkt == 1 ? 1 : (nkt == 2 ? 2 : (nkt <= 4 ? 4 : (nkt <= 7 ? 7 : 11)));
 }
 
-static int ds_groups_for(const AttnParams& p) { return p.nwin_total < DS_GROUPS ? p.nwin_total : DS_GROUPS; }
+static int ds_groups_for(const AttnParams& p) {   // all segments' groups (attn_ds_window_sum_kernel)
+    // per-sample segments share the DS_GROUPS groups (at least one each): the gather then reads as many partial tiles per
+    // table entry as with one segment
+    const int nseg = p.tab_stride ? p.B : 1, wps = p.nwin_total / nseg;
+    int gps = DS_GROUPS / nseg;
+    if (gps < 1) gps = 1;
+    return nseg * (wps < gps ? wps : gps);
+}
 
 size_t msseg_window_attention_bwd_mfma_ws_bytes(const AttnParams& p) {
     const size_t E = (size_t)bwd_nkt(p) * bwd_nkt(p) * 1024;

@@ -64,6 +64,13 @@ SIGNATURES = {
     "msseg_window_attention_bwd2": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp,
                                      _sz, _vp], _i),
     "msseg_window_attention_bwd_workspace_bytes": ([_i, _i, _i, _i, _i, _i, _i, _i, _i], _sz),
+    "msseg_window_attention_fwd3": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _ll, _i, _vp], _i),
+    "msseg_window_attention_bwd3": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _ll, _i,
+                                     _vp, _sz, _vp], _i),
+    "msseg_window_attention_bwd3_workspace_bytes": ([_i, _i, _i, _i, _i, _i, _i, _i, _i, _ll, _i], _sz),
+    "msseg_rel_bias_affine_fold": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp], _i),
+    "msseg_rel_bias_affine_grad_workspace_bytes": ([_i, _i], _sz),
+    "msseg_rel_bias_affine_grad": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp], _i),
     "msseg_layernorm_fwd": ([_vp, _ll, _vp, _vp, _vp, _ll, _vp, _vp, _ll, _i, _f, _i, _vp], _i),
     "msseg_layernorm_bwd": ([_vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _ll, _i, _i, _vp], _i),
     "msseg_layernorm_bwd_add": ([_vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _ll, _ll, _i, _i, _vp], _i),
@@ -1357,6 +1364,72 @@ def window_attention_bwd(qkv, qkv_bias, table, out, lse, dout, dqkv, dtable, hea
                                           _p(dtable), B, S, H, W, C3 // 3, heads, ws, shift, bws, dt(qkv), _p(work), wsb,
                                           _stream()), "window_attention_bwd")
     return dqkv
+
+
+def window_attention_fwd_per_sample(qkv, qkv_bias, tables, out, heads, ws, shift):
+    """window_attention_fwd with one bias table per sample: tables [B, (2ws-1)^3, heads] fp32 contiguous"""
+    _need_gpu(qkv, tables, out)
+    assert qkv.is_contiguous() and out.is_contiguous() and tables.is_contiguous() and tables.dtype == torch.float32
+    B, S, H, W, C3 = qkv.shape
+    assert tables.shape == (B, (2 * ws - 1) ** 3, heads), tables.shape
+    nW = -(-S // ws) * -(-H // ws) * -(-W // ws)
+    lse = torch.empty(B * nW, heads, ws ** 3, dtype=torch.float32, device=qkv.device)
+    _ck(lib().msseg_window_attention_fwd3(_p(qkv), _p(qkv_bias), _p(tables), _p(out), _p(lse), B, S, H, W, C3 // 3, heads,
+                                          ws, shift, ws, tables[0].numel(), dt(qkv), _stream()), "window_attention_fwd3")
+    return lse
+
+
+def window_attention_bwd_per_sample(qkv, qkv_bias, tables, out, lse, dout, dqkv, dtables, heads, ws, shift):
+    """backward of window_attention_fwd_per_sample; dtables [B, (2ws-1)^3, heads] (nullable) is ACCUMULATED per sample"""
+    _need_gpu(qkv, tables, out, lse, dout, dqkv)
+    assert qkv.is_contiguous() and out.is_contiguous() and dout.is_contiguous() and dqkv.is_contiguous()
+    B, S, H, W, C3 = qkv.shape
+    stride = tables[0].numel()
+    wsb = 0
+    if dtables is not None:
+        assert dtables.is_contiguous() and dtables.shape == tables.shape
+        wsb = int(lib().msseg_window_attention_bwd3_workspace_bytes(B, S, H, W, C3 // 3, heads, ws, shift, ws, stride,
+                                                                     dt(qkv)))
+    work = torch.empty(wsb, dtype=torch.uint8, device=qkv.device) if wsb else None
+    _ck(lib().msseg_window_attention_bwd3(_p(qkv), _p(qkv_bias), _p(tables), _p(out), _p(lse), _p(dout), _p(dqkv),
+                                          _p(dtables), B, S, H, W, C3 // 3, heads, ws, shift, ws, stride, dt(qkv), _p(work),
+                                          wsb, _stream()), "window_attention_bwd3")
+    return dqkv
+
+
+AFFINE_ACC_TABLE, AFFINE_ACC_EMB, AFFINE_ACC_LIN_W, AFFINE_ACC_LIN_B = 1, 2, 4, 8
+
+
+def rel_bias_affine_fold(table, emb, lin_w, lin_b, aff, out):
+    """out [B, M3, heads] = table + lin_b + sum_k lin_w[k] * aff[b, k] * emb[..., k]  (all fp32, contiguous, on the GPU)"""
+    _need_gpu(table, emb, lin_w, lin_b, aff, out)
+    M3, heads = table.shape
+    B = aff.shape[0]
+    assert emb.shape == (M3, heads, 3) and lin_w.numel() == 3 and lin_b.numel() == 1 and aff.shape == (B, 3)
+    assert out.shape == (B, M3, heads)
+    for t in (table, emb, lin_w, lin_b, aff, out):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    _ck(lib().msseg_rel_bias_affine_fold(_p(table), _p(emb), _p(lin_w), _p(lin_b), _p(aff), _p(out), B, M3, heads,
+                                         _stream()), "rel_bias_affine_fold")
+    return out
+
+
+def rel_bias_affine_grad(dT, emb, lin_w, aff, dtable=None, demb=None, dlin_w=None, dlin_b=None, flags=0):
+    """parameter gradients from the per-sample table gradient dT [B, M3, heads]; each output (nullable) is overwritten, or
+    accumulated when its AFFINE_ACC_* bit is in `flags`"""
+    _need_gpu(dT, emb, lin_w, aff)
+    B, M3, heads = dT.shape
+    for t in (dT, emb, lin_w, aff, dtable, demb, dlin_w, dlin_b):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda)
+    assert emb.shape == (M3, heads, 3) and aff.shape == (B, 3)
+    assert dtable is None or dtable.numel() == M3 * heads
+    assert demb is None or demb.numel() == M3 * heads * 3
+    assert (dlin_w is None or dlin_w.numel() == 3) and (dlin_b is None or dlin_b.numel() == 1)
+    wsb = int(lib().msseg_rel_bias_affine_grad_workspace_bytes(M3, heads))
+    work = torch.empty(wsb, dtype=torch.uint8, device=dT.device)
+    _ck(lib().msseg_rel_bias_affine_grad(_p(dT), _p(emb), _p(lin_w), _p(aff), _p(dtable), _p(demb), _p(dlin_w),
+                                         _p(dlin_b), B, M3, heads, int(flags), _p(work), wsb, _stream()),
+        "rel_bias_affine_grad")
 
 
 def layernorm_fwd(x, gamma, beta, y, eps=1e-5, save=True):

@@ -4,7 +4,8 @@ for the models on the hot path.
 * ``cfg.model in {'UNet', 'UNetSmall'}`` -- MONAI BasicUNet topology (BASELINE.json configs 1-3; the reference has no
   UNet).
 * ``cfg.model == 'nnFormerUNETR'`` -- ``SwinTransformerNNFormer`` encoder + ``SwinUNETRCustom`` decoder, the branch
-  at ``model_builder.py:15-66``.
+  at ``model_builder.py:15-66``.  ``cfg.rel_pos_bias_affine`` (this branch and the two below) turns on the
+  spacing-conditioned relative position bias, fed by the ``affine_xyz`` of the engine's input tuple.
 * ``cfg.model == 'SwinDepth'`` -- the same wiring around the ``SwinDepth`` encoder (depthwise-conv + BatchNorm MLP), the
   branch at ``model_builder.py:120-171``.
 * ``cfg.model == 'SwInception'`` -- the same wiring around the ``SwInception`` encoder (Inception-head MLP: Conv3d +
@@ -46,7 +47,7 @@ def build_model(cfg):
         return UNet(cfg.in_chans, cfg.output_dim, UNET_FEATURES[name], compute_dtype=_dtype(cfg))
     if name in ("nnFormerUNETR", "SwinDepth", "SwInception"):
         from .swin_unetr import SwInception, SwinDepth, SwinTransformerNNFormer, SwinUNETRCustom
-        for flag in ("learned_cls_vectors", "rel_pos_bias_affine", "rel_crop_pos_emb", "abs_pos_emb", "global_token"):
+        for flag in ("learned_cls_vectors", "rel_crop_pos_emb", "abs_pos_emb", "global_token"):
             if getattr(cfg, flag, False):
                 raise NotImplementedError(f"--{flag} is outside the hot-path scope of this build (SURVEY.md section 2)")
         ws = cfg.window_size if isinstance(cfg.window_size, (tuple, list)) else (cfg.window_size,) * len(cfg.depths)
@@ -54,7 +55,8 @@ def build_model(cfg):
         encoder = enc_cls(pretrain_img_size=_t3(cfg.vol_size), patch_size=_t3(cfg.patch_size), in_chans=cfg.in_chans,
                           embed_dim=cfg.hidden_dim, depths=tuple(cfg.depths), num_heads=tuple(cfg.num_heads),
                           window_size=tuple(ws), qkv_bias=cfg.qkv_bias, mlp_ratio=getattr(cfg, "mlp_ratio", 4.0),
-                          compute_dtype=_dtype(cfg))
+                          compute_dtype=_dtype(cfg),
+                          rel_pos_bias_affine=bool(getattr(cfg, "rel_pos_bias_affine", False)))   # model_builder.py:15-171
         return SwinUNETRCustom(encoder, in_channels=cfg.in_chans, out_channels=cfg.output_dim,
                                img_size=_t3(cfg.vol_size), hidden_size=cfg.hidden_dim, patch_size=_t3(cfg.patch_size),
                                compute_dtype=_dtype(cfg))

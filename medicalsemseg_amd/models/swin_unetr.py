@@ -210,10 +210,16 @@ class _InceptionMlp(nn.Module):
 
 
 class _WindowAttention(nn.Module):
-    def __init__(self, dim, ws, heads, qkv_bias):
+    def __init__(self, dim, ws, heads, qkv_bias, rel_pos_bias_affine=False):
         super().__init__()
         self.ws, self.heads = ws, heads
+        self.rel_pos_bias_affine = bool(rel_pos_bias_affine)
         self.relative_position_bias_table = nn.Parameter(torch.zeros((2 * ws - 1) ** 3, heads))
+        if self.rel_pos_bias_affine:     # spacing-conditioned bias (swin_nnformer.py:89-97): names, order and init as there
+            self.rel_pos_bias_affine_emb = nn.Parameter(torch.zeros((2 * ws - 1) ** 3, heads, 3))
+            self.rel_pos_bias_affine_lin = nn.Linear(3, 1)
+            nn.init.trunc_normal_(self.rel_pos_bias_affine_emb, std=.02)
+            nn.init.trunc_normal_(self.rel_pos_bias_affine_lin.weight, std=.02)
         self.register_buffer("relative_position_index", _rel_index(ws))
         self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
         self.proj = nn.Linear(dim, dim)
@@ -221,14 +227,14 @@ class _WindowAttention(nn.Module):
 
 
 class _Block(nn.Module):
-    def __init__(self, dim, res, heads, ws, shift, mlp_ratio, qkv_bias, drop_path, mlp="plain"):
+    def __init__(self, dim, res, heads, ws, shift, mlp_ratio, qkv_bias, drop_path, mlp="plain", rel_pos_bias_affine=False):
         super().__init__()
         self.res = tuple(res)
         if min(self.res) <= ws:          # swin_nnformer.py:213-216
             shift, ws = 0, min(self.res)
         self.ws, self.shift, self.heads, self.drop_path = ws, shift, heads, float(drop_path)
         self.norm1 = nn.LayerNorm(dim)
-        self.attn = _WindowAttention(dim, ws, heads, qkv_bias)
+        self.attn = _WindowAttention(dim, ws, heads, qkv_bias, rel_pos_bias_affine)
         self.norm2 = nn.LayerNorm(dim)
         if mlp == "depth":
             self.mlp = _DepthMlp(dim, int(dim * mlp_ratio))
@@ -248,11 +254,17 @@ class _Block(nn.Module):
             mask = torch.empty(x.shape[0], device=x.device, dtype=torch.float32).bernoulli_(keep)
         return mask.to(device=x.device, dtype=torch.float32) / keep
 
-    def forward(self, x):
+    def forward(self, x, affine=None):
+        """affine: [B, 3] fp32 spacings on the device (ops.expand_affine) or None; used by rel_pos_bias_affine blocks only"""
         a = self.attn
         x, xn = ops.layer_norm_res(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)   # x: the residual, through the node
         qkv = ops.linear(xn, a.qkv.weight, a.qkv.bias)
-        y = ops.WindowAttnFn.apply(qkv, a.qkv.bias, a.relative_position_bias_table, self.heads, self.ws, self.shift)
+        if a.rel_pos_bias_affine and affine is not None:
+            y = ops.WindowAttnAffineFn.apply(qkv, a.qkv.bias, a.relative_position_bias_table, a.rel_pos_bias_affine_emb,
+                                             a.rel_pos_bias_affine_lin.weight, a.rel_pos_bias_affine_lin.bias, affine,
+                                             self.heads, self.ws, self.shift)
+        else:
+            y = ops.WindowAttnFn.apply(qkv, a.qkv.bias, a.relative_position_bias_table, self.heads, self.ws, self.shift)
         dp = self._dp_scale(x)
         if dp is None:     # no stochastic depth in this step: the residual adds ride on the Linear kernels' epilogues
             x = ops.linear_add(y, a.proj.weight, a.proj.bias, x)
@@ -279,15 +291,15 @@ class _PatchMerging(nn.Module):
 
 
 class _BasicLayer(nn.Module):
-    def __init__(self, dim, res, depth, heads, ws, mlp_ratio, qkv_bias, drop_path, mlp="plain"):
+    def __init__(self, dim, res, depth, heads, ws, mlp_ratio, qkv_bias, drop_path, mlp="plain", rel_pos_bias_affine=False):
         super().__init__()
         self.blocks = nn.ModuleList([_Block(dim, res, heads, ws, 0 if i % 2 == 0 else ws // 2, mlp_ratio, qkv_bias,
-                                            drop_path[i], mlp) for i in range(depth)])
+                                            drop_path[i], mlp, rel_pos_bias_affine) for i in range(depth)])
         self.downsample = _PatchMerging(dim)
 
-    def forward(self, x):
+    def forward(self, x, affine=None):
         for b in self.blocks:
-            x = b(x)
+            x = b(x, affine)
         return self.downsample(x)
 
 
@@ -311,25 +323,33 @@ class SwinTransformerNNFormer(nn.Module):
     def __init__(self, pretrain_img_size=(96, 96, 96), patch_size=(2, 2, 2), in_chans=1, embed_dim=48,
                  depths: Sequence[int] = (2, 2, 2, 2), num_heads: Sequence[int] = (3, 6, 12, 24),
                  window_size: Sequence[int] = (6, 6, 6, 3), mlp_ratio=4.0, qkv_bias=True, drop_path_rate=0.2,
-                 compute_dtype=torch.bfloat16, mlp="plain"):
+                 compute_dtype=torch.bfloat16, mlp="plain", rel_pos_bias_affine=False):
         super().__init__()
         self.num_layers, self.embed_dim, self.compute_dtype = len(depths), embed_dim, compute_dtype
+        self.rel_pos_bias_affine = bool(rel_pos_bias_affine)
         self.patch_embed = _PatchEmbed3D(patch_size, in_chans, embed_dim)
         dpr = [x.item() for x in torch.linspace(0, drop_path_rate, sum(depths))]
         self.layers = nn.ModuleList()
         for i in range(self.num_layers):
             res = tuple(pretrain_img_size[d] // patch_size[d] // 2 ** i for d in range(3))
             self.layers.append(_BasicLayer(embed_dim * 2 ** i, res, depths[i], num_heads[i], window_size[i], mlp_ratio,
-                                           qkv_bias, dpr[sum(depths[:i]):sum(depths[:i + 1])], mlp))
+                                           qkv_bias, dpr[sum(depths[:i]):sum(depths[:i + 1])], mlp, rel_pos_bias_affine))
         self.num_features = [embed_dim * 2 ** (i + 1) for i in range(self.num_layers)]
         for i in range(self.num_layers):
             self.add_module(f"norm{i}", nn.LayerNorm(self.num_features[i]))
 
     def forward(self, inp):
+        """inp: the volume, or the engine's (volume, rel_crop_loc, affine_xyz) tuple.  With rel_pos_bias_affine, an affine
+        [A, 3] (A dividing the batch) conditions every window attention on the spacing, as the reference's `aff`."""
         vol = inp[0] if isinstance(inp, (tuple, list)) else inp
+        aff = inp[2] if isinstance(inp, (tuple, list)) and len(inp) > 2 else None
         if not vol.is_cuda:
             raise RuntimeError("SwinTransformerNNFormer runs on the GPU only (no CPU fallback)")
         B, Cin, D, H, W = vol.shape
+        if self.rel_pos_bias_affine and aff is not None:
+            aff = ops.expand_affine(aff.to(vol.device), B)
+        else:
+            aff = None
         p = self.patch_embed.patch_size[0]
         if D % p or H % p or W % p:
             raise ValueError("volume must be a multiple of the patch size")
@@ -338,7 +358,7 @@ class SwinTransformerNNFormer(nn.Module):
         x = self.patch_embed(x_cl)
         feats = [x]
         for i, layer in enumerate(self.layers):
-            x = layer(x)
+            x = layer(x, aff)
             n = getattr(self, f"norm{i}")
             feats.append(ops.layer_norm(x, n.weight, n.bias, n.eps))   # norm of the DOWNSAMPLED tensor (:653-658)
         return feats, x_cl
@@ -346,7 +366,7 @@ class SwinTransformerNNFormer(nn.Module):
 
 class SwinDepth(SwinTransformerNNFormer):
     """/root/reference/models/backbones/swindepth.py:400-691 with its default-off extras off (learned class vectors,
-    affine / crop position terms, global token): the reference's Swin encoder whose MLP carries three depthwise
+    crop position term, global token; the spacing-conditioned bias is `rel_pos_bias_affine`): the reference's Swin encoder whose MLP carries three depthwise
     Conv3d + BatchNorm3d + GELU stages (`_DepthMlp`).  `sync_batchnorm(group)` = what run_training.py:83 does under DDP."""
 
     def __init__(self, *a, **k):
@@ -362,7 +382,7 @@ class SwinDepth(SwinTransformerNNFormer):
 
 class SwInception(SwinDepth):
     """/root/reference/models/backbones/swinception.py:609-791 with its default-off extras off (learned class vectors,
-    affine / crop position terms, global token): the reference's Swin encoder whose MLP is the Inception head
+    crop position term, global token; the spacing-conditioned bias is `rel_pos_bias_affine`): the reference's Swin encoder whose MLP is the Inception head
     (`_InceptionMlp`); everything else is SwinTransformerNNFormer.  `sync_batchnorm(group)` as for SwinDepth."""
 
     def __init__(self, *a, **k):

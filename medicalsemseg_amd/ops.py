@@ -391,6 +391,66 @@ class WindowAttnFn(torch.autograd.Function):
         return dqkv, None, (None if ctx.table.is_contiguous() else dtable), None, None, None, None
 
 
+def expand_affine(aff, B):
+    """[A, 3] spacings -> [B, 3] fp32 on the device, one row per sample: sample b takes row b // (B / A) (window b * nW + w
+    of the reference's window_affine takes row (b * nW + w) // (B * nW / A), the same row).  A = B in training, A = 1 in
+    sliding-window inference."""
+    aff = aff.reshape(-1, 3)
+    A = aff.shape[0]
+    if A < 1 or B % A:
+        raise ValueError(f"affine has {A} rows, which do not divide the batch of {B} samples")
+    aff = aff.to(dtype=torch.float32).contiguous()
+    return aff if A == B else aff.repeat_interleave(B // A, dim=0)
+
+
+class WindowAttnAffineFn(torch.autograd.Function):
+    """WindowAttnFn with the spacing-conditioned bias term (`rel_pos_bias_affine`, swin_nnformer.py:157-166): one bias
+    table per sample, T_b = table + lin.b + sum_k lin.w[k] * aff[b, k] * emb[..., k] (hip.rel_bias_affine_fold), and the
+    parameter gradients from the per-sample table gradient dT (hip.rel_bias_affine_grad, fixed-order sums).
+    aff [B, 3] fp32 on the device (expand_affine); it is data and gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, qkv, qkv_bias, table, emb, lin_w, lin_b, aff, heads, ws, shift):
+        qkv = _c(qkv)
+        B, S, H, W, C3 = qkv.shape
+        if tuple(aff.shape) != (B, 3) or aff.dtype != torch.float32 or not aff.is_contiguous():
+            raise ValueError(f"affine must be fp32 [{B}, 3] contiguous (ops.expand_affine), got {tuple(aff.shape)} {aff.dtype}")
+        prm = [t.detach().contiguous() for t in (table, emb, lin_w, lin_b)]
+        tabs = torch.empty((B,) + tuple(prm[0].shape), dtype=torch.float32, device=qkv.device)
+        hip.rel_bias_affine_fold(*prm, aff, tabs)
+        out = torch.empty(B, S, H, W, C3 // 3, dtype=qkv.dtype, device=qkv.device)
+        qb = qkv_bias.detach() if qkv_bias is not None else None
+        lse = hip.window_attention_fwd_per_sample(qkv, qb, tabs, out, heads, ws, shift)
+        ctx.save_for_backward(qkv, qb, tabs, out, lse, aff, prm[1], prm[2])
+        ctx.cfg = (heads, ws, shift)
+        ctx.params = (table, emb, lin_w, lin_b)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, qb, tabs, out, lse, aff, emb, lin_w = ctx.saved_tensors
+        heads, ws, shift = ctx.cfg
+        dqkv = torch.empty_like(qkv)
+        want = [ctx.needs_input_grad[i] for i in (2, 3, 4, 5)]
+        dT = torch.zeros_like(tabs) if any(want) else None
+        hip.window_attention_bwd_per_sample(qkv, qb, tabs, out, lse, _c(dout), dqkv, dT, heads, ws, shift)
+        bufs, ret = [None] * 4, [None] * 4
+        flags = 0
+        if dT is not None:
+            for k, (p, bit) in enumerate(zip(ctx.params, (hip.AFFINE_ACC_TABLE, hip.AFFINE_ACC_EMB, hip.AFFINE_ACC_LIN_W,
+                                                        hip.AFFINE_ACC_LIN_B))):
+                if not want[k]:
+                    continue
+                if p.is_contiguous():
+                    bufs[k], acc = _gbuf(p)          # each parameter keeps its own overwrite / accumulate decision
+                    flags |= bit if acc else 0
+                else:
+                    bufs[k] = ret[k] = torch.empty(p.shape, dtype=torch.float32, device=p.device)
+            hip.rel_bias_affine_grad(dT, emb, lin_w, aff, *bufs, flags=flags)
+        # gradient w.r.t. qkv_bias through PADDED tokens is dropped, as in WindowAttnFn
+        return (dqkv, None, *ret, None, None, None, None)
+
+
 class Conv3Fn(torch.autograd.Function):
     """Conv3d k3 p1, stride 1 or 2 (+bias) on [B,D,H,W,C]"""
 

@@ -47,7 +47,17 @@ class FlatAdamW(torch.optim.Optimizer):
         if len(wds) > 1:
             raise ValueError("FlatAdamW supports one non-zero weight_decay value")
         self._wd = wds.pop() if wds else 0.0
-        n = sum(p.numel() for p in ps)
+        # offsets of the parameters in the flat buffers: 1-D parameters (biases, norm scales) start on a 16-byte boundary,
+        # kernels read them with 16-byte vector loads.  A parameter of a size that is no multiple of 4 in front of them (the
+        # [1, 3] / [1] Linear of the spacing-conditioned bias) leaves zero padding slots; none of the other models has one
+        self._offs = []
+        off = 0
+        for p in ps:
+            if p.ndim <= 1:
+                off += (-off) % 4
+            self._offs.append(off)
+            off += p.numel()
+        n = off
         pad = (-n) % 4
         self.flat_param = torch.zeros(n + pad, dtype=torch.float32, device=dev)
         self.flat_grad = torch.zeros(n + pad, dtype=torch.float32, device=dev)
@@ -55,18 +65,16 @@ class FlatAdamW(torch.optim.Optimizer):
         self.exp_avg_sq = torch.zeros_like(self.flat_param)
         self.decay_mask = torch.zeros(n + pad, dtype=torch.uint8, device=dev)
         self._views = []
-        off = 0
         with torch.no_grad():
             for g in self.param_groups:
                 for p in g["params"]:
-                    k = p.numel()
+                    k, off = p.numel(), self._offs[len(self._views)]
                     self.flat_param[off:off + k].copy_(p.detach().reshape(-1))
                     p.data = self.flat_param[off:off + k].view(p.shape)
                     gv = self.flat_grad[off:off + k].view(p.shape)
                     self._views.append((p, gv))
                     if g["weight_decay"] != 0.0:
                         self.decay_mask[off:off + k] = 1
-                    off += k
         self._n = n
         self._step = 0
         # lazy zero_grad (layers._grad_buf): gradients live in flat_grad for good, zero_grad() only opens a new epoch
@@ -112,13 +120,12 @@ class FlatAdamW(torch.optim.Optimizer):
         n_k = sum(1 for p, _ in self._views if getattr(p, "_msseg_kgrad", False))
         if getattr(self, "_ar_key", None) != n_k:
             runs, off, start = [], 0, None
-            for p, _ in self._views:
-                k = p.numel()
+            for (p, _), o in zip(self._views, self._offs):
                 if not getattr(p, "_msseg_kgrad", False):
-                    start = off if start is None else start
+                    start = o if start is None else start
                 elif start is not None:
                     runs.append((start, off)); start = None
-                off += k
+                off = o + p.numel()
             if start is not None:
                 runs.append((start, off))
             self._ar_key, self._ar = n_k, runs
@@ -161,11 +168,10 @@ class FlatAdamW(torch.optim.Optimizer):
         """Smallest offset o such that flat_grad[o:] holds no gradient of `late_params` (the ones a split backward
         produces last): flat_grad[o:] can be all-reduced while those are still being computed."""
         late = {id(p) for p in late_params}
-        off, o = 0, 0
-        for p, _ in self._views:
-            off += p.numel()
+        o = 0
+        for (p, _), off in zip(self._views, self._offs):
             if id(p) in late:
-                o = off
+                o = off + p.numel()
         return o
 
     def state_dict(self):
@@ -181,9 +187,8 @@ class FlatAdamW(torch.optim.Optimizer):
             raise ValueError("optimizer state does not match the parameter groups of this model")
         ids = [i for g in groups for i in g["params"]]
         steps = set()
-        off = 0
         self.exp_avg.zero_(); self.exp_avg_sq.zero_()
-        for (p, _), i in zip(self._views, ids):
+        for (p, _), i, off in zip(self._views, ids, self._offs):
             k = p.numel()
             st = sd["state"].get(i)
             if st is not None:
@@ -192,7 +197,6 @@ class FlatAdamW(torch.optim.Optimizer):
                 self.exp_avg[off:off + k].copy_(st["exp_avg"].reshape(-1))
                 self.exp_avg_sq[off:off + k].copy_(st["exp_avg_sq"].reshape(-1))
                 steps.add(int(st["step"]))
-            off += k
         if len(steps) > 1:
             raise ValueError("parameters with different step counts cannot share the fused optimiser step")
         return steps.pop() if steps else 0, groups
