@@ -187,6 +187,18 @@ int msseg_deconv_k2s2_fwd(const void* x, long long ldx, const void* wp, const fl
 /* input gradient of the above: dy [N,2D,2H,2W,Cout] -> dx [N,D,H,W,Cin]. */
 int msseg_deconv_k2s2_bwd_data(const void* dy, long long lddy, const void* wp, void* dx, long long lddx,
                                int N, int D, int H, int W, int Cin, int Cout, int dtype, msseg_stream_t stream);
+/* ConvTranspose3d k=s=4 (the last UnetrUpBlock.transp_conv of Swin-UNETR with patch size 4; csrc/deconv_k4s4.hip):
+ * x [N,D,H,W,Cin] -> y [N,4D,4H,4W,Cout], y[n,4d+a,4h+b,4w+c,co] = bias[co] + sum_ci x[n,d,h,w,ci] * W[ci,co,a,b,c].
+ * wp: msseg_pack_weights image with T = 1 -- forward: M = abc * Cout + co (abc = (a*4 + b)*4 + c), K = ci; input gradient:
+ * M = ci, K = abc * Cout + co (hip.pack_deconv builds both).  ldx / ldy: voxel strides, so y may be the first Cout channels
+ * of a concat buffer.  bf16 with Cin = Cout in {32, 48, 64, 96} (forward: Cin <= 96 a multiple of 8, Cout a multiple of 32 or
+ * 48) and 16-byte aligned rows runs on MFMA kernels; fp32 and every other channel count on plain vector kernels.  All
+ * three are deterministic (fixed-order reductions, no atomics). */
+int msseg_deconv_k4s4_fwd(const void* x, long long ldx, const void* wp, const float* bias, void* y, long long ldy,
+                          int N, int D, int H, int W, int Cin, int Cout, int dtype, msseg_stream_t stream);
+/* input gradient of the above: dy [N,4D,4H,4W,Cout] -> dx [N,D,H,W,Cin]. */
+int msseg_deconv_k4s4_bwd_data(const void* dy, long long lddy, const void* wp, void* dx, long long lddx,
+                               int N, int D, int H, int W, int Cin, int Cout, int dtype, msseg_stream_t stream);
 /* The two flat input-gradient kernels with the InstanceNorm-backward sums of the RECEIVING layer fused into the epilogue
  * (arguments as msseg_conv3d_k3_dgrad_inbwd): the gradient that reaches the second conv+norm unit of a UNet level comes
  * from the 1x1x1 output conv (level 0) or from a transposed conv (other decoder levels / the bottleneck).
@@ -251,6 +263,12 @@ int msseg_conv3d_gather_wgrad(const void* x, long long ldx, const void* dy, long
                               int N, int ID, int IH, int IW, int Cin, int Cout, int k, int s, int p, int accumulate,
                               void* workspace, size_t workspace_bytes, int dtype, msseg_stream_t stream);
 int msseg_deconv_k2s2_wgrad(const void* x, long long ldx, const void* dy, long long lddy, float* dw,
+                            int N, int D, int H, int W, int Cin, int Cout, int accumulate,
+                            void* workspace, size_t workspace_bytes, int dtype, msseg_stream_t stream);
+/* dw [Cin][Cout][4][4][4] (+)= sum over coarse voxels of x[v][ci] * dy[child abc of v][co] (ConvTranspose3d k4 s4);
+ * workspace: at least Cin * 64 * Cout * 4 bytes (one partial image; more lets more workgroups share the voxels),
+ * msseg_wgrad_workspace_bytes(Cin, 1, 64 * Cout) is ample. */
+int msseg_deconv_k4s4_wgrad(const void* x, long long ldx, const void* dy, long long lddy, float* dw,
                             int N, int D, int H, int W, int Cin, int Cout, int accumulate,
                             void* workspace, size_t workspace_bytes, int dtype, msseg_stream_t stream);
 

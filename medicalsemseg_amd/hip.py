@@ -97,12 +97,15 @@ SIGNATURES = {
     "msseg_conv3d_gather_fwd": ([_vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "msseg_deconv_k2s2_fwd": ([_vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "msseg_deconv_k2s2_bwd_data": ([_vp, _ll, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "msseg_deconv_k4s4_fwd": ([_vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "msseg_deconv_k4s4_bwd_data": ([_vp, _ll, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "msseg_wgrad_workspace_bytes": ([_i, _i, _i], _sz),
     "msseg_conv3d_k3_wgrad_kernel": ([_i, _i, _i, _i, _i, _i, _i], _i),
     "msseg_conv3d_k3_wgrad": ([_vp, _ll, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp], _i),
     "msseg_conv3d_k1_wgrad": ([_vp, _ll, _vp, _ll, _vp, _ll, _i, _i, _i, _vp, _sz, _i, _vp], _i),
     "msseg_conv3d_gather_wgrad": ([_vp, _ll, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp], _i),
     "msseg_deconv_k2s2_wgrad": ([_vp, _ll, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp], _i),
+    "msseg_deconv_k4s4_wgrad": ([_vp, _ll, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp], _i),
     "msseg_channel_stats": ([_vp, _ll, _vp, _i, _ll, _i, _vp, _sz, _i, _vp], _i),
     "msseg_instnorm_act_fwd": ([_vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _i, _ll, _i, _f, _f, _i, _vp], _i),
     "msseg_instnorm_act_poolbwd_reduce": ([_vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _i,
@@ -362,11 +365,15 @@ def pack_conv_gather(w: torch.Tensor, dtype, out=None):
 
 
 def pack_deconv(w: torch.Tensor, dtype, bwd=False, out=None):
-    """w: ConvTranspose3d weight [Cin, Cout, 2,2,2].  fwd: M = abc*Cout+co, K = ci.  bwd-data: M = ci, K = abc*Cout+co."""
+    """w: ConvTranspose3d weight [Cin, Cout, k,k,k], k = 2 or 4 (kernel = stride).  fwd: M = abc*Cout+co, K = ci.
+    bwd-data: M = ci, K = abc*Cout+co.  abc = the child's index in the weight's own (a, b, c) order, k^3 children."""
     ci, co = w.shape[0], w.shape[1]
+    nc = w.shape[2] * w.shape[3] * w.shape[4]
+    if nc not in (8, 64) or not (w.shape[2] == w.shape[3] == w.shape[4]):
+        raise NotImplementedError(f"transposed conv with kernel {tuple(w.shape[2:])}: only k = s = 2 and k = s = 4 are implemented")
     if not bwd:
-        return pack_weights(w, dtype, 8 * co, co, 1, ci, ci, 1, 8, 0, 0, co * 8, False, out)
-    return pack_weights(w, dtype, ci, ci, 1, 8 * co, co, 0, co * 8, 0, 1, 8, False, out)
+        return pack_weights(w, dtype, nc * co, co, 1, ci, ci, 1, nc, 0, 0, co * nc, False, out)
+    return pack_weights(w, dtype, ci, ci, 1, nc * co, co, 0, co * nc, 0, 1, nc, False, out)
 
 
 # --------------------------------------------------------------------------------------------
@@ -770,6 +777,33 @@ def deconv_k2s2_bwd_data(dy, wp, dx, cin, cout):
     return dx
 
 
+def deconv_k4s4(x, wp, bias, y, cin, cout):
+    """ConvTranspose3d k = s = 4: x [N,D,H,W,cin] -> y [N,4D,4H,4W,cout] (y may be a channel slice of a wider buffer)"""
+    _need_gpu(x, wp, y)
+    N, D, H, W = x.shape[:4]
+    if tuple(y.shape) != (N, 4 * D, 4 * H, 4 * W, cout):
+        raise ValueError(f"deconv_k4s4: output shape {tuple(y.shape)} for input {tuple(x.shape)}, cout {cout}")
+    nv = N * D * H * W
+    esz = x.element_size()
+    TIMER.launch("deconv_k4s4_fwd", 2.0 * nv * 64 * cin * cout, nv * (cin + 64 * cout) * esz + 64 * cin * cout * esz,
+                 lambda: _ck(lib().msseg_deconv_k4s4_fwd(_p(x), ld(x), _p(wp), _p(bias), _p(y), ld(y), N, D, H, W, cin, cout,
+                                                         dt(x), _stream()), "deconv_k4s4_fwd"))
+    return y
+
+
+def deconv_k4s4_bwd_data(dy, wp, dx, cin, cout):
+    _need_gpu(dy, wp, dx)
+    N, D, H, W = dx.shape[:4]
+    if tuple(dy.shape) != (N, 4 * D, 4 * H, 4 * W, cout):
+        raise ValueError(f"deconv_k4s4_bwd_data: gradient shape {tuple(dy.shape)} for input {tuple(dx.shape)}, cout {cout}")
+    nv = N * D * H * W
+    esz = dy.element_size()
+    TIMER.launch("deconv_k4s4_bwd_data", 2.0 * nv * 64 * cin * cout, nv * (cin + 64 * cout) * esz + 64 * cin * cout * esz,
+                 lambda: _ck(lib().msseg_deconv_k4s4_bwd_data(_p(dy), ld(dy), _p(wp), _p(dx), ld(dx), N, D, H, W, cin, cout,
+                                                              dt(dy), _stream()), "deconv_k4s4_bwd_data"))
+    return dx
+
+
 # --------------------------------------------------------------------------------------------
 # weight gradients
 # --------------------------------------------------------------------------------------------
@@ -848,6 +882,20 @@ def deconv_k2s2_wgrad(x, dy, dw, cin, cout, accumulate=False):
     ws = _wg_ws(cin, 1, 8 * cout, x.device)
     _ck(lib().msseg_deconv_k2s2_wgrad(_p(x), ld(x), _p(dy), ld(dy), _p(dw), N, D, H, W, cin, cout, int(accumulate),
                                       _p(ws), ws.numel(), dt(x), _stream()), "deconv_k2s2_wgrad")
+
+
+def deconv_k4s4_wgrad(x, dy, dw, cin, cout, accumulate=False):
+    """dw [cin, cout, 4,4,4] (+)= weight gradient of ConvTranspose3d k = s = 4; x coarse, dy fine (4x each way)"""
+    _need_gpu(x, dy, dw)
+    N, D, H, W = x.shape[:4]
+    if tuple(dy.shape) != (N, 4 * D, 4 * H, 4 * W, cout) or dw.numel() != cin * cout * 64 or not dw.is_contiguous():
+        raise ValueError(f"deconv_k4s4_wgrad: shapes x {tuple(x.shape)}, dy {tuple(dy.shape)}, dw {tuple(dw.shape)}")
+    ws = _wg_ws(cin, 1, 64 * cout, x.device)
+    nv = N * D * H * W
+    TIMER.launch("deconv_k4s4_wgrad", 2.0 * nv * 64 * cin * cout, nv * (cin + 64 * cout) * x.element_size() + 64 * cin * cout * 4,
+                 lambda: _ck(lib().msseg_deconv_k4s4_wgrad(_p(x), ld(x), _p(dy), ld(dy), _p(dw), N, D, H, W, cin, cout,
+                                                           int(accumulate), _p(ws), ws.numel(), dt(x), _stream()),
+                             "deconv_k4s4_wgrad"))
 
 
 # --------------------------------------------------------------------------------------------

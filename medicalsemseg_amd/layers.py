@@ -545,24 +545,50 @@ class Conv1:
 
 
 class Deconv2:
-    """ConvTranspose3d k = s = 2 (+bias): [N,D,H,W,Cin] -> [N,2D,2H,2W,Cout]."""
+    """ConvTranspose3d k = s (+bias), k = 2 or 4 taken from the weight's shape: [N,D,H,W,Cin] -> [N,kD,kH,kW,Cout]."""
 
     def __init__(self, weight, bias):
         self.w, self.b = weight, bias
         self.cin, self.cout = weight.shape[0], weight.shape[1]
+        self.k = weight.shape[2]
+        if tuple(weight.shape[2:]) not in ((2, 2, 2), (4, 4, 4)):
+            raise NotImplementedError(f"transposed conv with kernel {tuple(weight.shape[2:])}: only k = s = 2 and k = s = 4 are implemented")
         self.cache = PackedCache()
 
     def fwd(self, x, out=None):
         dtype = x.dtype
         N, D, H, W, _ = x.shape
-        y = out if out is not None else torch.empty(N, 2 * D, 2 * H, 2 * W, self.cout, dtype=dtype, device=x.device)
+        k = self.k
+        y = out if out is not None else torch.empty(N, k * D, k * H, k * W, self.cout, dtype=dtype, device=x.device)
         wp = self.cache.get(self.w, dtype, "f", lambda: hip.pack_deconv(self.w.detach(), dtype))
-        hip.deconv_k2s2(x, wp, self.b, y, self.cin, self.cout)
+        if k == 4:
+            hip.deconv_k4s4(x, wp, self.b, y, self.cin, self.cout)
+        else:
+            hip.deconv_k2s2(x, wp, self.b, y, self.cin, self.cout)
         return y
+
+    def _bwd_k4(self, x, dy, need_dx, next_norm):
+        """k = s = 4: weight gradient on the side stream, bias gradient as a channel sum over dy, input gradient; the
+        receiving layer's InstanceNorm-backward sums are not fused here (red = None: the norm runs its own reduction)"""
+        dtype = x.dtype
+        if self.w.requires_grad:
+            g, acc = _grad_buf(self.w)
+            WGRAD_SIDE.run(lambda: hip.deconv_k4s4_wgrad(x, dy, g, self.cin, self.cout, acc), x, dy)
+        if self.b is not None and self.b.requires_grad:
+            g, acc = _grad_buf(self.b)
+            hip.channel_sum(dy, g, acc)
+        if not need_dx:
+            return None
+        wp = self.cache.get(self.w, dtype, "d", lambda: hip.pack_deconv(self.w.detach(), dtype, bwd=True))
+        dx = torch.empty_like(x, memory_format=torch.contiguous_format)
+        hip.deconv_k4s4_bwd_data(dy, wp, dx, self.cin, self.cout)
+        return (dx, None) if next_norm is not None else dx
 
     def bwd(self, x, dy, need_dx=True, next_norm=None):
         """next_norm = (InstNormAct, yraw, stats, act) of the layer whose activation `x` is: its InstanceNorm-backward sums
         are fused into the input-gradient kernel; returns (dx, red).  The bias gradient comes out of the same pass."""
+        if self.k == 4:
+            return self._bwd_k4(x, dy, need_dx, next_norm)
         dtype = x.dtype
         if self.w.requires_grad:
             g, acc = _grad_buf(self.w)
@@ -597,6 +623,9 @@ class Deconv2:
                 nn_ = (yraw, act, stats, nrm.slope, nrm.eps)
         red = hip.deconv_k2s2_bwd_fused(dy, wp, dx, self.cin, self.cout, nn_, db, dbacc, dg, dbt, nacc)
         return (dx, red) if next_norm is not None else dx
+
+
+Deconv4 = Deconv2   # the k = s = 4 layer is the same class: the factor comes from the weight
 
 
 class InstNormAct:
@@ -792,7 +821,8 @@ class UpBlock:
 
     def alloc_cat(self, x):
         N, D, H, W, _ = x.shape
-        return torch.empty(N, 2 * D, 2 * H, 2 * W, 2 * self.cout, dtype=x.dtype, device=x.device)
+        k = self.up.k                    # upsampling factor = the transposed conv's kernel = stride
+        return torch.empty(N, k * D, k * H, k * W, 2 * self.cout, dtype=x.dtype, device=x.device)
 
     def fwd(self, x, cat):
         """cat[..., cout:] must already hold the skip; returns (out, saved)."""

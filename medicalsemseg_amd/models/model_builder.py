@@ -6,6 +6,8 @@ for the models on the hot path.
 * ``cfg.model == 'nnFormerUNETR'`` -- ``SwinTransformerNNFormer`` encoder + ``SwinUNETRCustom`` decoder, the branch
   at ``model_builder.py:15-66``.  ``cfg.rel_pos_bias_affine`` (this branch and the two below) turns on the
   spacing-conditioned relative position bias, fed by the ``affine_xyz`` of the engine's input tuple.
+  ``cfg.patch_size`` 2 or 4 (this branch and the two below): 4 is the nnFormer setting, whose last up block is a k4 s4
+  transposed convolution; ``vol_size`` must be a multiple of ``patch_size * 2^len(depths)``.
 * ``cfg.model == 'SwinDepth'`` -- the same wiring around the ``SwinDepth`` encoder (depthwise-conv + BatchNorm MLP), the
   branch at ``model_builder.py:120-171``.
 * ``cfg.model == 'SwInception'`` -- the same wiring around the ``SwInception`` encoder (Inception-head MLP: Conv3d +

@@ -309,6 +309,12 @@ class _PatchEmbed3D(nn.Module):
         self.patch_size = tuple(patch_size)
         if len(set(self.patch_size)) != 1:
             raise NotImplementedError("anisotropic patch sizes are not implemented")
+        k = self.patch_size[0]
+        if in_chans * k ** 3 > 128 and in_chans % 8:
+            # the few-channel gather kernels hold Cin * k^3 <= 128 (include/msseg.h); channel counts that are a multiple of
+            # the 16-byte chunk go through the space-to-depth GEMM instead
+            raise NotImplementedError(f"patch embedding with in_chans {in_chans} at patch size {k}: the gather kernels take "
+                                      f"in_chans * patch^3 <= 128 (in_chans <= {128 // k ** 3}), the GEMM path a multiple of 8 channels")
         self.proj = nn.Conv3d(in_chans, embed_dim, kernel_size=self.patch_size, stride=self.patch_size)
         self.norm = nn.LayerNorm(embed_dim)
 
@@ -424,8 +430,8 @@ class _UnetrBasicBlock(nn.Module):
 class _UnetrUpBlock(nn.Module):
     def __init__(self, cin, cout, up_k):
         super().__init__()
-        if up_k != 2:
-            raise NotImplementedError("only 2x transposed-conv upsampling (patch_size 2) is implemented")
+        if up_k not in (2, 4):
+            raise NotImplementedError("only 2x and 4x transposed-conv upsampling (patch_size 2 or 4) are implemented")
         self.transp_conv = _ConvOnly(cin, cout, up_k, transposed=True)
         self.conv_block = _UnetResBlock(cout + cout, cout)
 
@@ -447,6 +453,18 @@ class SwinUNETRCustom(nn.Module):
         self.encoder, self.out_channels, self.compute_dtype = encoder, out_channels, compute_dtype
         hs = hidden_size
         ps = patch_size[0] if isinstance(patch_size, (tuple, list)) else patch_size
+        if isinstance(patch_size, (tuple, list)) and len(set(patch_size)) != 1:
+            raise NotImplementedError("anisotropic patch sizes are not implemented")
+        # the token grid is halved num_layers times and every decoder level doubles it again (the last one multiplies by the
+        # patch size): the shapes meet only if every halving is exact
+        step = ps * 2 ** encoder.num_layers
+        sizes = tuple(img_size) if isinstance(img_size, (tuple, list)) else (img_size,) * 3
+        if any(v % step for v in sizes):
+            raise ValueError(
+                f"vol_size {sizes} is not a multiple of patch_size * 2^num_layers = {ps} * 2^{encoder.num_layers} = {step}: "
+                f"the decoder's skip connections could not meet the upsampled feature maps (the reference builds such a "
+                f"model silently and fails in its first forward); use fewer stages (--depths) or another volume size"
+                + (" -- with patch size 4, 96^3 allows at most three stages" if ps == 4 else ""))
         self.unet_encoders = nn.ModuleList([_UnetrBasicBlock(in_channels, hs), _UnetrBasicBlock(hs, hs)])
         self.unet_decoders = nn.ModuleList([_UnetrUpBlock(hs, hs, ps)])
         for i in range(encoder.num_layers):
