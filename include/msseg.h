@@ -645,6 +645,46 @@ typedef struct msseg_aug_row { int32_t z0, y0, x0, flips, rotk, pad0; float shif
 int msseg_aug_crop_batch(const float* img, const uint8_t* lab, int C, int VD, int VH, int VW, const void* table,
                          int npatch, void* out_img, int out_dtype, float* out_lab, int R, msseg_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Dataset path (csrc/dataprep.hip): one-off preprocessing of a loaded volume on the device and the per-step patch gather
+ * over many cached volumes.  Volumes are NCDHW single samples of arbitrary D x H x W.  MONAI parity unpinned: the
+ * semantics are those of the numpy / scipy restatement in tests/dataprep_ref.py.
+ * intensity_prep: src fp32 (src_dtype 0) or int16 (1) [C][D][H][W] -> dst fp32.  mode 0: copy; 1: ScaleIntensityRange(a_min,
+ *            a_min + a_range, 0, 1, clip=True); 2: the same after cbrt (a_min / a_range are those of the cube roots of
+ *            the bounds, data/transforms.py:45-75); then (v - subtrahend) / divisor when `normalize`.  One fp32 rounding per
+ *            numpy operation.  box6 (device, 6 ints) = {min z, y, x, max z, y, x (inclusive)} over voxels where any channel
+ *            is > 0 after scaling and before normalisation (CropForegroundd(source_key="image")); {D, H, W, -1, -1, -1}
+ *            when there is none.
+ * resample_spacing: Spacingd.  Source coordinate = destination index * r (r = new / old spacing per axis, double).  Image
+ *            (fp32, is_label 0): trilinear, border clamped; label (uint8, is_label 1): nearest, floor(c + 0.5).
+ * crop_pad_copy: dst[c][pad_before + i] = src[c][box start + i] for i inside box6 = {z0, y0, x0, z1, y1, x1} (half-open,
+ *            HOST ints, as pad_before3), the pad value elsewhere; elem_bytes 4 (fp32) or 1 (uint8).
+ * slab_counts: counts[z] = {#(lab > 0), #(lab == 0 && img0 > threshold)} per z-slice, int32 [D][2] on the device.
+ * pick_voxels: rows[i] = msseg_pick_row; mode 1 / 0: the rank-th foreground / background voxel (flat order) of slice z of
+ *            volume vol; mode 2: rank IS the in-slice flat index.  out[i][8] = {centre z, y, x (MONAI correct_crop_centers
+ *            clamp for the cubic roi R), crop start z, y, x, z, in-slice flat index of the voxel (-1: rank beyond the count)}.
+ * aug_crop_multi: msseg_aug_crop_batch over many volumes: row i reads volume rows[i].vol at the crop start picks[i][3..5]
+ *            (clamped into the volume) with the row's flips / rotk / shift / scale; out_img [npatch][C][R][R][R] fp32 or bf16,
+ *            out_lab fp32 [npatch][1][R][R][R].  One launch per batch.  Precondition (the tables live on the device, so the
+ *            entry point cannot check it; DeviceDatasetLoader does on the host): every rows[i].vol is in [0, nvol), that
+ *            volume has C channels and is at least R long on every axis.  A row that breaks it reads nothing and yields
+ *            an all-zero patch; the call still returns MSSEG_OK.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct msseg_volume_desc { const float* img; const uint8_t* lab; int32_t C, D, H, W; } msseg_volume_desc;
+typedef struct msseg_pick_row { int32_t vol, mode, z, rank, flips, rotk; float shift, scale; } msseg_pick_row;
+int msseg_intensity_prep(const void* src, int src_dtype, int C, int D, int H, int W, int mode, float a_min, float a_range,
+                         int normalize, float subtrahend, float divisor, float* dst, int* box6, msseg_stream_t stream);
+int msseg_resample_spacing(const void* src, int is_label, int C, int SD, int SH, int SW, void* dst, int TD, int TH, int TW,
+                           double rz, double ry, double rx, msseg_stream_t stream);
+int msseg_crop_pad_copy(const void* src, int elem_bytes, int C, int SD, int SH, int SW, const int* box6, void* dst, int TD,
+                        int TH, int TW, const int* pad_before3, float pad_f32, int pad_u8, msseg_stream_t stream);
+int msseg_slab_counts(const float* img0, const uint8_t* lab, int D, int H, int W, float threshold, int* counts,
+                      msseg_stream_t stream);
+int msseg_pick_voxels(const void* volumes, int nvol, const void* rows, int nrows, int R, float threshold, int* out,
+                      msseg_stream_t stream);
+int msseg_aug_crop_multi(const void* volumes, int nvol, const void* rows, const int* picks, int npatch, int C, void* out_img,
+                         int out_dtype, float* out_lab, int R, msseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,3 +113,281 @@ class DevicePatchLoader:
                    "image_transforms": [{"class": ["RandCropByPosNegLabeld"] * self.batch,
                                          "orig_size": [torch.full((self.batch,), float(s)) for s in (D, H, W)],
                                          "extra_info": {"center": [cen[:, 0], cen[:, 1], cen[:, 2]]}}]}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Dataset path: many preprocessed volumes cached in HBM, batches drawn across them with one gather launch.
+# The transforms are the chain of the reference's data/dataset_builder.py:19-217 (training) and :220-306 (validation) up
+# to the random crop; MONAI is absent, so what is pinned is parity with the numpy / scipy restatement in
+# tests/dataprep_ref.py (MONAI parity unpinned).  Cache cost: 4 bytes per voxel and channel (fp32 image) + 1 (uint8 label)
+# + 8 bytes per z-slice of candidate counts; no per-voxel index lists.
+# ---------------------------------------------------------------------------------------------------------------------
+class PickRow(C.Structure):
+    """mirror of msseg_pick_row (include/msseg.h)"""
+    _fields_ = [("vol", C.c_int32), ("mode", C.c_int32), ("z", C.c_int32), ("rank", C.c_int32), ("flips", C.c_int32),
+                ("rotk", C.c_int32), ("shift", C.c_float), ("scale", C.c_float)]
+
+
+class VolumeDesc(C.Structure):
+    """mirror of msseg_volume_desc (include/msseg.h)"""
+    _fields_ = [("img", C.c_uint64), ("lab", C.c_uint64), ("C", C.c_int32), ("D", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
+
+
+PICK_BG, PICK_FG, PICK_VOXEL = 0, 1, 2
+
+
+def _upload(structs, dev):
+    arr = (type(structs[0]) * len(structs))(*structs)
+    # a blocking copy: the temporary host buffer is gone when this returns
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+
+
+def check_transform_flags(cfg):
+    """the transform flags this build does not implement raise with the flag's name"""
+    for flag in ("t_percentile_ct_intensity", "t_normalize_channel_wise", "t_crop_foreground_kdiv", "t_rand_crop_classes",
+                 "t_rand_crop_dilated_center", "t_convert_labels_to_brats"):
+        if getattr(cfg, flag, False) and not (flag == "t_normalize_channel_wise" and not cfg.t_normalize):
+            raise NotImplementedError(f"--{flag} is not implemented on the device data path")
+
+
+def normalised_zero(cfg):
+    """what a scaled intensity of 0 becomes under --t_normalize, in fp32 as the kernel computes it (0.0 without the flag):
+    the pad value of the cache and the image threshold of the background crop centres.  The reference thresholds the
+    un-normalised image at 0 (RandCropByPosNegLabeld(image_threshold=0) runs in front of NormalizeIntensityd); on the
+    normalised cache `v > 0` is `(v - mean) / std > (0 - mean) / std`."""
+    if not cfg.t_normalize:
+        return 0.0
+    return float((np.float32(0.0) - np.float32(cfg.t_norm_mean)) / np.float32(cfg.t_norm_std))
+
+
+def voxel_dims(cfg):
+    """--t_voxel_dims as three spacings: one value is used for every axis"""
+    v = cfg.t_voxel_dims
+    v = tuple(v) if isinstance(v, (tuple, list)) else (v,)
+    if len(v) == 1:
+        v = v * 3
+    if len(v) != 3 or any(not float(x) > 0 for x in v):
+        raise ValueError(f"--t_voxel_dims takes one or three positive spacings, got {cfg.t_voxel_dims!r}")
+    return tuple(float(x) for x in v)
+
+
+def preprocess_volume(image, label, affine, cfg, device, filename="volume"):
+    """One loaded case -> the cached record.  image: numpy [C, X, Y, Z] (int16 / float32 / other numeric), label numpy
+    [X, Y, Z] or None.  Chain: Orientationd(RAS) when in_chans == 1 -> Spacingd -> intensity scaling (+ NormalizeIntensityd)
+    with the foreground box -> CropForegroundd -> SpatialPadd(vol_size).  NormalizeIntensityd is applied here for training
+    as well: the reference applies it after the random shift / scale, this cache before them (the pad value is the
+    normalised zero, as a pad before the normalisation gives; the background crop centres must then be thresholded at
+    normalised_zero(cfg), not at 0)."""
+    from . import data_files as df
+    check_transform_flags(cfg)
+    roi = cfg.vol_size if isinstance(cfg.vol_size, int) else cfg.vol_size[0]
+    image = np.asarray(image)
+    if image.dtype != np.int16 and image.dtype != np.float32:
+        image = image.astype(np.float32)
+    img = torch.from_numpy(np.ascontiguousarray(image)).to(device)
+    lab = torch.from_numpy(np.ascontiguousarray(label).astype(np.uint8)).to(device) if label is not None else \
+        torch.zeros(image.shape[1:], dtype=torch.uint8, device=device)
+    original_affine = np.array(affine, dtype=np.float64)
+    aff = original_affine.copy()
+    if cfg.in_chans == 1:
+        perm, flips = df.ras_orientation(aff)
+        aff = df.reorient_affine(aff, tuple(img.shape[1:]), perm, flips)
+        img = img.permute(0, *(1 + p for p in perm))
+        lab = lab.permute(*perm)
+        fl = [a for a in range(3) if flips[a]]
+        if fl:
+            img, lab = img.flip([1 + a for a in fl]), lab.flip(fl)
+        img, lab = img.contiguous(), lab.contiguous()
+    if cfg.t_voxel_spacings:
+        new = voxel_dims(cfg)
+        old = df.spacing_of(aff)
+        ratio = [float(n) / float(o) for n, o in zip(new, old)]
+        out = [df.resample_shape(s, o, n) for s, o, n in zip(img.shape[1:], old, new)]
+        if img.dtype != torch.float32:
+            img, _ = hip.intensity_prep(img)                    # int16 -> fp32, values unchanged
+        img = hip.resample_spacing(img, out, ratio)
+        lab = hip.resample_spacing(lab[None], out, ratio)[0]
+        aff = df.rescale_affine(aff, ratio)
+    mode = hip.INTENSITY_CUBED if cfg.t_cubed_ct_intensity else hip.INTENSITY_RANGE if cfg.t_fixed_ct_intensity else hip.INTENSITY_NONE
+    norm = (cfg.t_norm_mean, cfg.t_norm_std) if cfg.t_normalize else None
+    img, box = hip.intensity_prep(img, mode, cfg.t_ct_min, cfg.t_ct_max, norm)
+    pad = normalised_zero(cfg)
+    D, H, W = img.shape[1:]
+    b6 = (0, 0, 0, D, H, W)
+    if cfg.t_crop_foreground_img:
+        b = box.cpu().tolist()
+        if b[3] >= 0:                                            # an empty foreground keeps the whole volume
+            b6 = (b[0], b[1], b[2], b[3] + 1, b[4] + 1, b[5] + 1)
+    min_size = (roi,) * 3 if cfg.t_spatial_pad else None
+    before = (0, 0, 0)
+    if b6 != (0, 0, 0, D, H, W) or (min_size and min(D, H, W) < roi):
+        img, before = hip.crop_pad_copy(img, b6, min_size, pad)
+        lab = hip.crop_pad_copy(lab[None], b6, min_size, 0)[0][0]
+        aff = df.shift_affine(aff, [b6[a] - before[a] for a in range(3)])
+    return {"img": img, "lab": lab.contiguous(), "affine": aff, "original_affine": original_affine, "filename": filename,
+            "box": b6, "pad_before": tuple(before)}
+
+
+def build_cache(files, cfg, device):
+    """read, preprocess and keep every case of `files` on the device -> (records, cached bytes)"""
+    from . import data_files as df
+    recs, nbytes = [], 0
+    for item in files:
+        image, label, aff = df.load_case(item)
+        if image.shape[0] != cfg.in_chans:
+            raise ValueError(f"{item['image']}: {image.shape[0]} channel(s), --in_chans is {cfg.in_chans}")
+        r = preprocess_volume(image, label, aff, cfg, device, filename=item["image"])
+        nbytes += r["img"].numel() * 4 + r["lab"].numel()
+        recs.append(r)
+    return recs, nbytes
+
+
+def _aff(recs, key):
+    return torch.stack([torch.from_numpy(np.asarray(r[key])).float() for r in recs])
+
+
+class DeviceDatasetLoader:
+    """len() batches of `batch` patches of roi^3 drawn across the cached `volumes` (records of preprocess_volume): a seeded
+    permutation of the volumes per epoch, `patches_per_image` consecutive patches from each, the per-patch draws of
+    draw_rows; msseg_pick_voxels resolves the crop centres from the per-slice candidate counts and msseg_aug_crop_multi
+    writes the batch in ONE launch.  crop = "fgbg" (RandCropByPosNegLabeld) or "spatial" (RandSpatialCropd)."""
+
+    def __init__(self, volumes, roi, batch, n_batches, patches_per_image=1, device=None, seed=13, crop="fgbg", pos=1.0,
+                 neg=1.0, flip_prob=0.0, rot_prob=0.0, shift_os=0.1, shift_prob=0.0, scale_f=0.1, scale_prob=0.0,
+                 image_threshold=0.0, out_dtype=torch.float32):
+        if not volumes:
+            raise ValueError("DeviceDatasetLoader needs at least one cached volume")
+        if crop not in ("fgbg", "spatial"):
+            raise NotImplementedError(f"crop mode {crop!r}: --t_rand_crop_fgbg and --t_rand_spatial_crop are implemented")
+        self.vols, self.roi, self.batch, self.n = list(volumes), int(roi), int(batch), int(n_batches)
+        self.ppi, self.dev, self.crop, self.thr, self.out_dtype = max(int(patches_per_image), 1), device, crop, float(image_threshold), out_dtype
+        self.cfg = dict(pos=pos, neg=neg, flip_prob=flip_prob, rot_prob=rot_prob, shift_os=shift_os, shift_prob=shift_prob,
+                        scale_f=scale_f, scale_prob=scale_prob)
+        self.rng = np.random.default_rng(seed)
+        self.C = int(self.vols[0]["img"].shape[0])
+        descs = []
+        for v in self.vols:
+            img, lab = v["img"], v["lab"]
+            if img.dtype != torch.float32 or lab.dtype != torch.uint8 or not img.is_cuda or not lab.is_cuda or \
+                    not img.is_contiguous() or not lab.is_contiguous() or img.dim() != 4 or tuple(img.shape[1:]) != tuple(lab.shape):
+                raise ValueError("cached volumes: contiguous fp32 [C, D, H, W] image and uint8 [D, H, W] label on the GPU")
+            if img.shape[0] != self.C or min(img.shape[1:]) < self.roi:
+                raise ValueError(f"{v['filename']}: volume {tuple(img.shape)} does not hold a {self.roi}^3 patch of {self.C} "
+                                 f"channel(s) (--t_spatial_pad pads small volumes)")
+            descs.append(VolumeDesc(img.data_ptr(), lab.data_ptr(), *img.shape))
+        self.desc = _upload(descs, device)
+        # candidate counts per z-slice, cumulative on the host: 8 bytes per slice instead of 8 bytes per voxel
+        self.cum = []
+        if crop == "fgbg":
+            counts = [hip.slab_counts(v["img"], v["lab"], self.thr) for v in self.vols]
+            for c in counts:
+                c = c.cpu().numpy().astype(np.int64)
+                self.cum.append((np.cumsum(c[:, 0]), np.cumsum(c[:, 1])))
+        self.order, self.taken = [], 0
+        self.launches = 0
+        self.last_rows = self.last_picks = None
+
+    def __len__(self):
+        return self.n
+
+    def _next_volume(self):
+        """volume of the next patch: a new seeded permutation whenever the last one is used up"""
+        if self.taken == 0:
+            if not self.order:
+                self.order = list(self.rng.permutation(len(self.vols)))
+            self.current = int(self.order.pop(0))
+        self.taken = (self.taken + 1) % self.ppi
+        return self.current
+
+    def _row(self, vi):
+        D, H, W = self.vols[vi]["lab"].shape
+        if self.crop == "spatial":
+            (_, _, flips, rotk, shift, scale), = draw_rows(self.rng, 1, 0, 1, self.cfg)
+            start = [int(self.rng.integers(0, n - self.roi + 1)) for n in (D, H, W)]
+            fl = int(flips[0]) | int(flips[1]) << 1 | int(flips[2]) << 2
+            return PickRow(vi, PICK_VOXEL, 0, 0, fl, rotk, shift, scale), start
+        cf, cb = self.cum[vi]
+        nf, nb = int(cf[-1]), int(cb[-1])
+        (use_fg, idx, flips, rotk, shift, scale), = draw_rows(self.rng, 1, nf, nb, self.cfg)
+        fl = int(flips[0]) | int(flips[1]) << 1 | int(flips[2]) << 2
+        if nf == 0 and nb == 0:                                  # no candidate at all: a uniform voxel of the volume
+            flat = int(self.rng.integers(0, D * H * W))
+            return PickRow(vi, PICK_VOXEL, flat // (H * W), flat % (H * W), fl, rotk, shift, scale), None
+        cum = cf if use_fg else cb
+        z = int(np.searchsorted(cum, idx, side="right"))
+        rank = idx - (int(cum[z - 1]) if z else 0)
+        return PickRow(vi, PICK_FG if use_fg else PICK_BG, z, rank, fl, rotk, shift, scale), None
+
+    def __iter__(self):
+        R = self.roi
+        for _ in range(self.n):
+            vis = [self._next_volume() for _ in range(self.batch)]
+            made = [self._row(vi) for vi in vis]
+            rows = [m[0] for m in made]
+            table = _upload(rows, self.dev)
+            if self.crop == "spatial":
+                host = torch.tensor([[s[0] + R // 2, s[1] + R // 2, s[2] + R // 2, s[0], s[1], s[2], 0, 0] for _, s in made],
+                                    dtype=torch.int32)
+                picks = host.to(self.dev, non_blocking=True)
+            else:
+                picks = torch.empty(self.batch, 8, dtype=torch.int32, device=self.dev)
+                hip.pick_voxels(self.desc, len(self.vols), table, self.batch, R, self.thr, picks)
+            img = torch.empty(self.batch, self.C, R, R, R, dtype=self.out_dtype, device=self.dev)
+            lab = torch.empty(self.batch, 1, R, R, R, dtype=torch.float32, device=self.dev)
+            hip.aug_crop_multi(self.desc, len(self.vols), table, picks, img, lab, R)
+            self.launches += 1
+            if self.crop != "spatial":
+                host = picks.cpu()                               # the one small device-to-host copy of the batch
+            self.last_rows, self.last_picks = rows, host
+            cen = host[:, :3].float()
+            recs = [self.vols[vi] for vi in vis]
+            sizes = [[float(r["lab"].shape[a]) for r in recs] for a in range(3)]
+            yield {"image": img, "label": lab,
+                   "image_meta_dict": {"original_affine": _aff(recs, "original_affine"), "affine": _aff(recs, "affine"),
+                                       "filename_or_obj": [r["filename"] for r in recs]},
+                   "label_meta_dict": {"affine": _aff(recs, "affine")},
+                   "image_transforms": [{"class": ["RandCropByPosNegLabeld" if self.crop == "fgbg" else "RandSpatialCropd"] * self.batch,
+                                         "orig_size": [torch.tensor(s) for s in sizes],
+                                         "extra_info": {"center": [cen[:, 0], cen[:, 1], cen[:, 2]]}}]}
+
+
+class DeviceVolumeLoader:
+    """validation: one cached, preprocessed whole volume per step (batch 1), in the engine's batch-dict layout"""
+
+    def __init__(self, volumes):
+        self.vols = list(volumes)
+
+    def __len__(self):
+        return len(self.vols)
+
+    def __iter__(self):
+        for r in self.vols:
+            yield {"image": r["img"][None], "label": r["lab"][None, None].float(),
+                   "image_meta_dict": {"original_affine": _aff([r], "original_affine"), "affine": _aff([r], "affine"),
+                                       "filename_or_obj": [r["filename"]]},
+                   "label_meta_dict": {"affine": _aff([r], "affine")},
+                   "image_transforms": []}
+
+
+def crop_mode(cfg):
+    """the crop flag of a command line -> DeviceDatasetLoader's crop mode"""
+    check_transform_flags(cfg)
+    if cfg.t_rand_crop_fgbg:
+        return "fgbg"
+    if cfg.t_rand_spatial_crop:
+        return "spatial"
+    raise SystemExit("training on files needs a crop flag: --t_rand_crop_fgbg, --t_rand_spatial_crop or "
+                     "--t_rand_crop_classes (the last one is not implemented on the device data path)")
+
+
+def dataset_file_lists(cfg, rank, world):
+    """-> (this rank's training files, this rank's validation files, all training files, all validation files):
+    the "validation" section when the data list has one, the cross-validation split otherwise; both partitioned over the
+    ranks as dataset_builder.py:455-463 does"""
+    from . import data_files as df
+    js = df.datalist_path(cfg.data_path, cfg.task, cfg.json_list)
+    if df.has_key(js, "validation"):
+        train, val = df.load_datalist(js, "training"), df.load_datalist(js, "validation")
+    else:
+        train, val = df.cv_split(df.load_datalist(js, "training"), cfg.seed, cfg.cv_max_folds, cfg.cv_fold)
+    return df.partition(train, world, rank), df.partition(val, world, rank), train, val

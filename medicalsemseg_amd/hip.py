@@ -136,6 +136,12 @@ SIGNATURES = {
     "msseg_resample_nearest_u8": ([_vp, _i, _i, _i, _vp, _i, _i, _i, _vp], _i),
     "msseg_majority_vote_u8": ([_vp, _i, _ll, _i, _vp, _vp], _i),
     "msseg_aug_crop_batch": ([_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp], _i),
+    "msseg_intensity_prep": ([_vp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _f, _f, _vp, _vp, _vp], _i),
+    "msseg_resample_spacing": ([_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp], _i),
+    "msseg_crop_pad_copy": ([_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _f, _i, _vp], _i),
+    "msseg_slab_counts": ([_vp, _vp, _i, _i, _i, _f, _vp, _vp], _i),
+    "msseg_pick_voxels": ([_vp, _i, _vp, _i, _i, _f, _vp, _vp], _i),
+    "msseg_aug_crop_multi": ([_vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp], _i),
     "msseg_sw_gather_batch": ([_vp, _ll, _vp, _ll, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp], _i),
     "msseg_sw_blend_batch": ([_vp, _ll, _i, _vp, _vp, _ll, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "msseg_deconv_k2s2_bwd_partials_ok": ([_i, _i, _i], _i),
@@ -1323,6 +1329,95 @@ def aug_crop_batch(img, lab, table, out_img, out_lab, roi):
     assert table.numel() >= npatch * 32
     _ck(lib().msseg_aug_crop_batch(_p(img), _p(lab), img.shape[0], img.shape[1], img.shape[2], img.shape[3], _p(table),
                                    npatch, _p(out_img), dt(out_img), _p(out_lab), roi, _stream()), "aug_crop_batch")
+    return out_img, out_lab
+
+
+# --------------------------------------------------------------------------------------------
+# Dataset path (csrc/dataprep.hip): one-off preprocessing of a volume and the multi-volume patch gather
+# --------------------------------------------------------------------------------------------
+INTENSITY_NONE, INTENSITY_RANGE, INTENSITY_CUBED = 0, 1, 2
+
+
+def intensity_prep(src, mode=INTENSITY_NONE, a_min=0.0, a_max=1.0, normalize=None):
+    """src fp32 / int16 [C, D, H, W] -> (fp32 [C, D, H, W], box int32 [6] on the device: min z, y, x, max z, y, x inclusive
+    of the voxels > 0 after scaling, {D, H, W, -1, -1, -1} when none).  normalize: None or (subtrahend, divisor).
+    INTENSITY_CUBED takes the cube roots of the bounds on the host (np.cbrt in double, as the reference's transform)."""
+    import numpy as np
+    _need_gpu(src)
+    assert src.dim() == 4 and src.is_contiguous() and src.dtype in (torch.float32, torch.int16)
+    if mode == INTENSITY_CUBED:
+        a_min, a_max = float(np.cbrt(float(a_min))), float(np.cbrt(float(a_max)))
+    dst = torch.empty(src.shape, dtype=torch.float32, device=src.device)
+    box = torch.empty(6, dtype=torch.int32, device=src.device)
+    sub, div = (float(normalize[0]), float(normalize[1])) if normalize is not None else (0.0, 1.0)
+    _ck(lib().msseg_intensity_prep(_p(src), 0 if src.dtype == torch.float32 else 1, *src.shape, int(mode), float(a_min),
+                                   float(a_max) - float(a_min), int(normalize is not None), sub, div, _p(dst), _p(box),
+                                   _stream()), "intensity_prep")
+    return dst, box
+
+
+def resample_spacing(src, out_size, ratio):
+    """Spacingd: src fp32 (trilinear, border clamp) or uint8 (nearest) [C, D, H, W] -> [C, *out_size]; ratio = new / old
+    spacing per axis (source coordinate = destination index * ratio)"""
+    _need_gpu(src)
+    assert src.dim() == 4 and src.is_contiguous() and src.dtype in (torch.float32, torch.uint8)
+    td, th, tw = (int(v) for v in out_size)
+    dst = torch.empty(src.shape[0], td, th, tw, dtype=src.dtype, device=src.device)
+    _ck(lib().msseg_resample_spacing(_p(src), int(src.dtype == torch.uint8), *src.shape, _p(dst), td, th, tw,
+                                     float(ratio[0]), float(ratio[1]), float(ratio[2]), _stream()), "resample_spacing")
+    return dst
+
+
+def crop_pad_copy(src, box, min_size=None, pad_value=0):
+    """src fp32 / uint8 [C, D, H, W]; box = (z0, y0, x0, z1, y1, x1) half-open -> the box, padded with pad_value up to
+    min_size per axis (MONAI SpatialPad split: (target - n) // 2 before, the rest after).  -> (tensor, pad_before)"""
+    _need_gpu(src)
+    assert src.dim() == 4 and src.is_contiguous() and src.dtype in (torch.float32, torch.uint8)
+    box = [int(v) for v in box]
+    n = [box[3 + a] - box[a] for a in range(3)]
+    tgt = [max(n[a], int(min_size[a])) if min_size is not None else n[a] for a in range(3)]
+    before = [(tgt[a] - n[a]) // 2 for a in range(3)]
+    dst = torch.empty(src.shape[0], *tgt, dtype=src.dtype, device=src.device)
+    _ck(lib().msseg_crop_pad_copy(_p(src), src.element_size(), *src.shape, (C.c_int * 6)(*box), _p(dst), *tgt,
+                                  (C.c_int * 3)(*before), float(pad_value), int(pad_value) if src.dtype == torch.uint8 else 0,
+                                  _stream()), "crop_pad_copy")
+    return dst, tuple(before)
+
+
+def slab_counts(img, lab, threshold=0.0):
+    """img fp32 [C, D, H, W] (channel 0 is read), lab uint8 [D, H, W] -> int32 [D, 2] on the device:
+    per z-slice #(lab > 0), #(lab == 0 and img[0] > threshold)"""
+    _need_gpu(img, lab)
+    assert img.dtype == torch.float32 and lab.dtype == torch.uint8 and img.is_contiguous() and lab.is_contiguous()
+    assert img.dim() == 4 and lab.dim() == 3 and img.shape[1:] == lab.shape
+    out = torch.empty(lab.shape[0], 2, dtype=torch.int32, device=lab.device)
+    _ck(lib().msseg_slab_counts(_p(img), _p(lab), *lab.shape, float(threshold), _p(out), _stream()), "slab_counts")
+    return out
+
+
+def pick_voxels(volumes, nvol, rows, nrows, roi, threshold, out):
+    """volumes: uint8 device tensor of nvol msseg_volume_desc; rows: uint8 device tensor of nrows msseg_pick_row;
+    out: int32 [nrows, 8] on the device"""
+    _need_gpu(volumes, rows, out)
+    assert volumes.numel() >= nvol * 32 and rows.numel() >= nrows * 32 and out.dtype == torch.int32
+    assert out.is_contiguous() and out.numel() >= nrows * 8
+    _ck(lib().msseg_pick_voxels(_p(volumes), nvol, _p(rows), nrows, int(roi), float(threshold), _p(out), _stream()),
+        "pick_voxels")
+    return out
+
+
+def aug_crop_multi(volumes, nvol, rows, picks, out_img, out_lab, roi):
+    """one gather launch for a batch over many cached volumes; out_img [n, C, R, R, R] fp32 / bf16, out_lab fp32 [n, 1, R, R, R].
+    The descriptor and row tables are device memory: the caller guarantees that every row names one of the nvol volumes,
+    that it has out_img's channel count and holds an roi^3 patch (DeviceDatasetLoader checks this at construction); a row
+    that does not comes back as an all-zero patch."""
+    _need_gpu(volumes, rows, picks, out_img, out_lab)
+    npatch = out_img.shape[0]
+    assert volumes.numel() >= nvol * 32 and rows.numel() >= npatch * 32 and picks.numel() >= npatch * 8
+    assert picks.dtype == torch.int32 and picks.is_contiguous() and out_img.is_contiguous() and out_lab.is_contiguous()
+    assert out_lab.dtype == torch.float32 and out_lab.numel() == npatch * roi ** 3 and tuple(out_img.shape[2:]) == (roi,) * 3
+    _ck(lib().msseg_aug_crop_multi(_p(volumes), nvol, _p(rows), _p(picks), npatch, out_img.shape[1], _p(out_img), dt(out_img),
+                                   _p(out_lab), int(roi), _stream()), "aug_crop_multi")
     return out_img, out_lab
 
 

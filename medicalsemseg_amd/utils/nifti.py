@@ -85,8 +85,28 @@ def save_nifti(path: str, array, affine) -> None:
         f.write(payload)
 
 
+def _quatern_to_mat(b, c, d, qfac, pixdim):
+    """NIfTI-1 nifti_quatern_to_mat44: rotation from (b, c, d), columns scaled by pixdim, third column by qfac"""
+    a = 1.0 - (b * b + c * c + d * d)
+    if a < 1e-7:
+        a = 1.0 / np.sqrt(b * b + c * c + d * d)
+        b, c, d, a = b * a, c * a, d * a, 0.0
+    else:
+        a = np.sqrt(a)
+    R = np.array([[a * a + b * b - c * c - d * d, 2 * b * c - 2 * a * d, 2 * b * d + 2 * a * c],
+                  [2 * b * c + 2 * a * d, a * a + c * c - b * b - d * d, 2 * c * d - 2 * a * b],
+                  [2 * b * d - 2 * a * c, 2 * c * d + 2 * a * b, a * a + d * d - c * c - b * b]])
+    vox = np.array([v if v > 0 else 1.0 for v in pixdim], dtype=np.float64)
+    if qfac < 0:
+        vox[2] = -vox[2]
+    return R * vox[None, :]
+
+
 def load_nifti(path: str):
-    """-> (array, affine from the sform rows); enough of a reader to round-trip what save_nifti writes"""
+    """-> (array, affine).  Reads little-endian single-file NIfTI-1: up to 7 dimensions (a 4-D file keeps its channels
+    last), ``scl_slope`` / ``scl_inter`` applied (-> float32) when the slope is finite and non-zero and the pair is not the
+    identity, affine from the sform rows when ``sform_code > 0``, else from the qform quaternion and ``pixdim`` when
+    ``qform_code > 0``, else ``diag(pixdim)``.  What save_nifti writes reads back unchanged."""
     opener = gzip.open if path.endswith(".gz") else open
     with opener(path, "rb") as f:
         raw = f.read()
@@ -94,10 +114,24 @@ def load_nifti(path: str):
         raise ValueError("not a little-endian single-file NIfTI-1")
     dim = struct.unpack("<8h", raw[40:56])
     code, bits = struct.unpack("<2h", raw[70:74])
+    pixdim = struct.unpack("<8f", raw[76:108])
     off = int(struct.unpack("<f", raw[108:112])[0])
+    slope, inter = struct.unpack("<2f", raw[112:120])
+    qform_code, sform_code = struct.unpack("<2h", raw[252:256])
     shape = dim[1:1 + dim[0]]
+    if code not in _CODES:
+        raise ValueError(f"unsupported NIfTI datatype code {code}")
     dt = _CODES[code].newbyteorder("<")
     data = np.frombuffer(raw, dtype=dt, count=int(np.prod(shape)), offset=off).reshape(shape, order="F")
+    if np.isfinite(slope) and slope != 0.0 and np.isfinite(inter) and not (slope == 1.0 and inter == 0.0):
+        data = data.astype(np.float32) * np.float32(slope) + np.float32(inter)
     aff = np.eye(4)
-    aff[:3] = np.array(struct.unpack("<12f", raw[280:328])).reshape(3, 4)
+    if sform_code > 0:
+        aff[:3] = np.array(struct.unpack("<12f", raw[280:328])).reshape(3, 4)
+    elif qform_code > 0:
+        b, c, d, qx, qy, qz = struct.unpack("<6f", raw[256:280])
+        aff[:3, :3] = _quatern_to_mat(b, c, d, pixdim[0], pixdim[1:4])
+        aff[:3, 3] = (qx, qy, qz)
+    else:
+        aff[:3, :3] = np.diag([v if v > 0 else 1.0 for v in pixdim[1:4]])
     return data, aff

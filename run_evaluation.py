@@ -3,7 +3,8 @@
 ``engine.test.eval_model`` over the validation volumes) on the MI355X hot path.  The reference hands the model to MONAI's
 ``SlidingWindowInferer`` (``run_evaluation.py:68-74``); here ``inferer=None`` selects the built-in sliding window with the
 same settings (roi ``cfg.vol_size``, ``cfg.batch_size_val`` windows per forward, overlap ``cfg.val_infer_overlap``,
-gaussian blending).  Data: ``--synthetic`` volumes (the MONAI / Decathlon pipeline is outside the hot-path scope).
+gaussian blending).  Data: the validation list of the Decathlon data list (device cache,
+``medicalsemseg_amd/data_device.py``), or ``--synthetic`` volumes.
 
     python run_evaluation.py --synthetic --model UNet --output_dim 3 --vol_size 96 --resume out/best_model.pth
 """
@@ -33,16 +34,25 @@ def main(cfg):
         raise SystemExit("run_evaluation.py needs an MI355X: medicalsemseg_amd has no CPU fallback")
     device = torch.device("cuda", 0 if os.environ.get("MSSEG_BENCH_ONE_DEVICE") else int(os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(device)
-    if not cfg.synthetic:
-        raise SystemExit("only --synthetic data is available in this build (SURVEY.md section 2)")
     torch.manual_seed(cfg.seed)
     model = build_model(cfg).to(device)
     cfg.eval = True
     misc.load_model(cfg, model)                       # weights only: load_state_dict(torch.load(cfg.resume)['model'])
     criterion = DiceCELoss(to_onehot_y=True, softmax=True, squared_pred=True, smooth_nr=cfg.smooth_nr, smooth_dr=cfg.smooth_dr)
-    vval = cfg.synthetic_val_size if isinstance(cfg.synthetic_val_size, int) else cfg.synthetic_val_size[0]
-    loader = SyntheticLoader(cfg.synthetic_steps, 1, vval, cfg.in_chans, cfg.output_dim, cfg.seed + 7 + misc.get_rank(),
-                             with_crop_info=False)
+    if cfg.synthetic:
+        vval = cfg.synthetic_val_size if isinstance(cfg.synthetic_val_size, int) else cfg.synthetic_val_size[0]
+        loader = SyntheticLoader(cfg.synthetic_steps, 1, vval, cfg.in_chans, cfg.output_dim, cfg.seed + 7 + misc.get_rank(),
+                                 with_crop_info=False)
+    else:
+        # the validation list of the data list (its "validation" section, or fold --cv_fold of the seeded split),
+        # partitioned over the ranks, preprocessed on the GPU and cached in HBM
+        from medicalsemseg_amd.data_device import DeviceVolumeLoader, build_cache, dataset_file_lists
+        _, part_val, _, val = dataset_file_lists(cfg, misc.get_rank(), misc.get_world_size())
+        recs, nbytes = build_cache(part_val, cfg, device)
+        sys.stdout.write("rank {}: validation partition {} of {} file(s), cached {} bytes in HBM\n".format(
+            misc.get_rank(), len(part_val), len(val), nbytes))
+        sys.stdout.flush()
+        loader = DeviceVolumeLoader(recs)
     stats = eval_model(None, model, loader, criterion, device, cfg)
     if misc.is_main_process():
         print(json.dumps(stats))

@@ -3,8 +3,9 @@
 init -> seeds -> data -> build_model -> AdamW(+timm-style weight-decay groups) -> cosine schedule with linear warm-up
 -> resume -> DiceCE -> epochs of train_one_epoch / run_validation with best-mDice and periodic checkpoints.
 
-Differences: runs on MI355X through ``medicalsemseg_amd`` (no CPU fallback); ``--synthetic`` replaces the MONAI
-data pipeline (out of the hot-path scope); logging is stdout + ``log.txt`` JSON lines (tensorboardX / Neptune are not
+Differences: runs on MI355X through ``medicalsemseg_amd`` (no CPU fallback); without ``--synthetic`` the Decathlon
+data list under ``--data_path/--task/--json_list`` is read, preprocessed on the GPU and cached in HBM
+(``medicalsemseg_amd/data_device.py``), ``--synthetic`` generates volumes instead; logging is stdout + ``log.txt`` JSON lines (tensorboardX / Neptune are not
 available here); bf16 compute instead of fp16 autocast, so the GradScaler is a disabled pass-through;
 gradients are exchanged with one flat RCCL all-reduce instead of DDP buckets.
 """
@@ -13,6 +14,7 @@ from __future__ import annotations
 import datetime
 import json
 import os
+import sys
 import time
 
 import numpy as np
@@ -29,22 +31,42 @@ from medicalsemseg_amd.utils import misc
 from medicalsemseg_amd.utils.arguments import get_args
 
 
-def main(cfg):
-    misc.init_distributed_mode(cfg)
-    if not torch.cuda.is_available():
-        raise SystemExit("run_training.py needs an MI355X: medicalsemseg_amd has no CPU fallback "
-                         "(the CPU oracle under oracle/ is test infrastructure)")
-    # MSSEG_BENCH_ONE_DEVICE: several gloo ranks on one GPU, to rehearse the data-parallel control flow on a 1-GPU box
-    device = torch.device("cuda", 0 if os.environ.get("MSSEG_BENCH_ONE_DEVICE") else int(os.environ.get("LOCAL_RANK", "0")))
-    torch.cuda.set_device(device)
-    seed = cfg.seed + misc.get_rank()
-    torch.manual_seed(seed)
-    np.random.seed(seed)
+def file_loaders(cfg, device, seed, vol):
+    """Decathlon data list -> this rank's training / validation volumes, preprocessed once and cached in HBM
+    (the reference's ``data/dataset_builder.py:431-491``; transforms :19-306 as device kernels, MONAI parity unpinned)"""
+    from medicalsemseg_amd.data_device import (DeviceDatasetLoader, DeviceVolumeLoader, build_cache, crop_mode,
+                                               dataset_file_lists, normalised_zero)
+    crop = crop_mode(cfg)
+    rank, world = misc.get_rank(), misc.get_world_size()
+    part_train, part_val, train, val = dataset_file_lists(cfg, rank, world)
+    if misc.is_main_process():
+        print("Number of files in training cv split: {}".format(len(train)))
+        print("Number of files in val cv split: {}".format(len(val)))
+    t0 = time.time()
+    rec_train, b_train = build_cache(part_train, cfg, device)
+    rec_val, b_val = build_cache(part_val, cfg, device)
+    torch.cuda.synchronize()
+    # every rank reports (print is rank-0-only under data parallelism)
+    sys.stdout.write("rank {}: training partition {} file(s) [{}], validation partition {} file(s), cached {} bytes in HBM, "
+                     "preprocessed in {:.2f} s\n".format(rank, len(part_train),
+                                                         ", ".join(os.path.basename(f["image"]) for f in part_train),
+                                                         len(part_val), b_train + b_val, time.time() - t0))
+    sys.stdout.flush()
+    n_batches = len(part_train) * cfg.t_n_patches_per_image // cfg.n_images_per_batch
+    if n_batches < 1:
+        raise SystemExit(f"{len(part_train)} file(s) x --t_n_patches_per_image {cfg.t_n_patches_per_image} do not fill one "
+                         f"batch of --n_images_per_batch {cfg.n_images_per_batch}")
+    loader_train = DeviceDatasetLoader(rec_train, vol, cfg.n_images_per_batch, n_batches, cfg.t_n_patches_per_image, device,
+                                       seed=seed, crop=crop, pos=cfg.t_rand_crop_pos_weight or 1.0,
+                                       neg=cfg.t_rand_crop_neg_weight or 1.0, flip_prob=cfg.t_flip_prob, rot_prob=cfg.t_rot_prob,
+                                       shift_os=cfg.t_intensity_shift_os, shift_prob=cfg.t_intensity_shift_prob,
+                                       scale_f=cfg.t_intensity_scale_factors, scale_prob=cfg.t_intensity_scale_prob,
+                                       # image_threshold=0 of the reference, on the scale of the cached volume
+                                       image_threshold=normalised_zero(cfg))
+    return loader_train, DeviceVolumeLoader(rec_val)
 
-    if not cfg.synthetic:
-        raise SystemExit("only --synthetic data is available in this build: the MONAI/Decathlon pipeline of the "
-                         "reference (data/*) is outside the hot-path scope (SURVEY.md section 2)")
-    vol = cfg.vol_size if isinstance(cfg.vol_size, int) else cfg.vol_size[0]
+
+def synthetic_loaders(cfg, device, seed, vol):
     vval = cfg.synthetic_val_size if isinstance(cfg.synthetic_val_size, int) else cfg.synthetic_val_size[0]
     if cfg.t_rand_crop_fgbg:
         # device-side data path (SURVEY.md 8(f) N1): one synthetic "CT" of 2x the patch size cached in HBM, patches cropped
@@ -63,6 +85,26 @@ def main(cfg):
     else:
         loader_train = SyntheticLoader(cfg.synthetic_steps, cfg.n_images_per_batch, vol, cfg.in_chans, cfg.output_dim, seed)
     loader_val = SyntheticLoader(1, 1, vval, cfg.in_chans, cfg.output_dim, seed + 7, with_crop_info=False)
+    return loader_train, loader_val
+
+
+def main(cfg):
+    misc.init_distributed_mode(cfg)
+    if not torch.cuda.is_available():
+        raise SystemExit("run_training.py needs an MI355X: medicalsemseg_amd has no CPU fallback "
+                         "(the CPU oracle under oracle/ is test infrastructure)")
+    # MSSEG_BENCH_ONE_DEVICE: several gloo ranks on one GPU, to rehearse the data-parallel control flow on a 1-GPU box
+    device = torch.device("cuda", 0 if os.environ.get("MSSEG_BENCH_ONE_DEVICE") else int(os.environ.get("LOCAL_RANK", "0")))
+    torch.cuda.set_device(device)
+    seed = cfg.seed + misc.get_rank()
+    torch.manual_seed(seed)
+    np.random.seed(seed)
+
+    vol = cfg.vol_size if isinstance(cfg.vol_size, int) else cfg.vol_size[0]
+    if not cfg.synthetic:
+        loader_train, loader_val = file_loaders(cfg, device, seed, vol)
+    else:
+        loader_train, loader_val = synthetic_loaders(cfg, device, seed, vol)
 
     model = build_model(cfg).to(device)
     if cfg.distributed:
