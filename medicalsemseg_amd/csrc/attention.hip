@@ -588,7 +588,7 @@ static bool attn_bwd_on_mfma(const AttnParams& p, int C, int dtype) {
         if (7 * np * p.hd * 2 + 2 * np * 4 + (size_t)2 * p.M3 * 4 + np * 8 + 16 > 160 * 1024) return false;
     }
     return dtype == MSSEG_BF16 && (p.hd == 16 || p.hd == 32) && p.N <= 352 && p.M3 <= 4095 && (C % 8) == 0 &&
-           !getenv("MSSEG_ATTN_NO_MFMA") && !getenv("MSSEG_ATTN_BWD_NO_MFMA");
+           !getenv("MSSEG_ATTN_NO_MFMA");
 }
 
 size_t msseg_window_attention_bwd_workspace_bytes(int B, int S, int H, int W, int C, int heads, int ws, int shift, int dtype) {

@@ -437,8 +437,6 @@ template <int STATS, int TIMING = 0> int launch(const K3ppParams& p, hipStream_t
 }  // namespace
 
 bool msseg_k3c48_shape_ok(int N, int D, int H, int W, int M) {
-    static const bool off = getenv("MSSEG_NO_K3C48") != nullptr || getenv("MSSEG_NO_K3PP") != nullptr;
-    if (off) return false;
     if (M % 16 || M < 16 || M > 256 || N < 1 || N > NMAX) return false;
     const long long tiles = (long long)N * ceil_div(D, TD) * ceil_div(H, TH) * ceil_div(W, TW);
     if (tiles > 0x7fffffffLL) return false;

@@ -422,8 +422,6 @@ template <int STATS, int TIMING> int launch(const K3ppParams& p, hipStream_t str
 }  // namespace
 
 bool msseg_k3pp_eligible(const K3ppParams& p) {
-    static const bool off = getenv("MSSEG_NO_K3PP") != nullptr;
-    if (off) return false;
     if (p.K != 32 || p.M % 32 || p.M > 256) return false;
     if ((p.ldx % 8) || (p.ldy % 4) || ((uintptr_t)p.x & 15) || ((uintptr_t)p.y & 7)) return false;
     if (p.bias && ((uintptr_t)p.bias & 15)) return false;

@@ -30,8 +30,6 @@
 // rows on an 8-wide halo cost a 2-way bank conflict on part of the voxel-operand reads).
 #include "common.h"
 
-#include <stdlib.h>
-
 namespace {
 
 constexpr int TS = 6;                       // tile edge (h, w)
@@ -175,7 +173,6 @@ struct K3sFinParams {
     const bf16_t* uy; long long lduy;            // receiving unit: raw conv output, forward statistics, affine
     const float* ustats; const float* ugamma; const float* ubeta;
     float* dgamma; float* dbeta; int acc;
-    int dbg;                                     // timing experiments only (MSSEG_K3S_DBG): 1 = no output stores, 2 = no partial loads
 };
 
 constexpr int FCH = 4;        // channels of a finish workgroup (one float4 per stage group and voxel)
@@ -224,7 +221,7 @@ MSSEG_DEVFN void sum_partials(const K3sFinParams& p, int cg, const long long (&r
             const float* src = p.part + ((long long)cg * p.NV + (ok[c + i] ? row[c + i] : 0)) * 4;
 #pragma unroll
             for (int k = 0; k < NKG; ++k)
-                t[i][k] = (k < p.nks && ok[c + i] && !(p.dbg & 2)) ? *(const f32x4_t*)(src + (long long)k * p.NV * p.M) : f32x4_t{0.f, 0.f, 0.f, 0.f};
+                t[i][k] = (k < p.nks && ok[c + i]) ? *(const f32x4_t*)(src + (long long)k * p.NV * p.M) : f32x4_t{0.f, 0.f, 0.f, 0.f};
         }
 #pragma unroll
         for (int i = 0; i < NIC; ++i) {
@@ -264,7 +261,7 @@ __global__ __launch_bounds__(BS) void k3s_fwd_finish_kernel(const K3sFinParams p
             bf16x4_t o;
 #pragma unroll
             for (int e = 0; e < FCH; ++e) o[e] = (bf16_t)(y[i][e] + bias[e]);
-            if (!(p.dbg & 1)) *(bf16x4_t*)(p.yraw + row[i] * p.ldy + c0) = o;
+            *(bf16x4_t*)(p.yraw + row[i] * p.ldy + c0) = o;
 #pragma unroll
             for (int e = 0; e < FCH; ++e) {
                 y[i][e] = (float)o[e];              // statistics of the STORED values, as every conv epilogue takes them
@@ -301,7 +298,7 @@ __global__ __launch_bounds__(BS) void k3s_fwd_finish_kernel(const K3sFinParams p
                 const float z = y[i][e] * sc[e] + sh[e] + (float)rv[e];      // as msseg_instnorm_act_fwd: one rounding at the end
                 o[e] = (bf16_t)(z > 0.f ? z : z * p.slope);
             }
-            if (!(p.dbg & 1)) *(bf16x4_t*)(p.act + row[i] * p.lda + c0) = o;
+            *(bf16x4_t*)(p.act + row[i] * p.lda + c0) = o;
             if (p.pooled) slab[tid + i * BS] = o;
         }
     }
@@ -544,8 +541,6 @@ int msseg_conv3d_k3_small_fwd_finish_res(const float* part, int nstages, const f
     p.gamma = gamma; p.beta = beta; p.eps = eps; p.slope = slope;
     p.yraw = (bf16_t*)yraw; p.ldy = ldy; p.act = (bf16_t*)act; p.lda = lda; p.pooled = (bf16_t*)pooled; p.ldp = ldp; p.stats = stats;
     p.res = (const bf16_t*)residual; p.ldr = ldr;
-    static const int dbg = getenv("MSSEG_K3S_DBG") ? atoi(getenv("MSSEG_K3S_DBG")) : 0;
-    p.dbg = dbg;
     const int lds = pooled ? S * 8 : 0;
     dim3 grid(Cout / FCH, N);
     K3S_LAUNCH(k3s_fwd_finish_kernel, grid, lds, (hipStream_t)stream, p, S, nstages);

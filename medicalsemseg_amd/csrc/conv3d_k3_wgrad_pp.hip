@@ -236,7 +236,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3wg_pp_kernel(const K3WgParams p
             compute();
             if constexpr (TIMING) tcyc[0] += __builtin_readcyclecounter() - t0;
         } else {
-            if (ph + 1 < n_my && !(TIMING && p.dbg_noload)) load_tile(tile_of(ph + 1));
+            if (ph + 1 < n_my) load_tile(tile_of(ph + 1));
             if constexpr (TIMING) tcyc[1] += __builtin_readcyclecounter() - t0;
         }
         if constexpr (TIMING) t0 = __builtin_readcyclecounter();
@@ -286,8 +286,6 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3wg_pp_kernel(const K3WgParams p
 }  // namespace
 
 bool msseg_k3wg_pp_eligible(const K3WgParams& p) {
-    static const bool off = getenv("MSSEG_NO_K3PP") != nullptr;
-    if (off) return false;
     if (p.M % 8 || p.K % 8) return false;   // 16-byte channel chunks; partial 32-blocks are zero-filled
     if ((p.ldp % 8) || (p.ldq % 8) || ((uintptr_t)p.pten & 15) || ((uintptr_t)p.qten & 15)) return false;
     const long long ldm = p.ldp > p.ldq ? p.ldp : p.ldq;
@@ -309,16 +307,13 @@ int msseg_k3wg_pp_grid(const K3WgParams& p) {
 
 int msseg_k3wg_pp_launch(const K3WgParams& p, int gx, hipStream_t stream) {
     static const bool timing = getenv("MSSEG_K3PP_TIMING") != nullptr;
-    static const bool noload = getenv("MSSEG_K3PP_NOLOAD") != nullptr;   // timing experiments only (wrong results)
-    K3WgParams pl = p;
-    pl.dbg_noload = noload ? 1 : 0;
     const int lds = 2 * GRP_BYTES;
     static msseg_lds_attr_once attr[2];
     if (!attr[0].ensure((const void*)k3wg_pp_kernel<0>, lds) || !attr[1].ensure((const void*)k3wg_pp_kernel<1>, lds))
         MSSEG_FAIL(MSSEG_ELAUNCH, "conv3d_k3_wgrad_pp: cannot set dynamic LDS size %d", lds);
     const int pairs = ceil_div(p.M, 32) * ceil_div(p.K, 32);
-    if (timing) hipLaunchKernelGGL(k3wg_pp_kernel<1>, dim3(gx, pairs, 1), dim3(NTHREADS), lds, stream, pl);
-    else MSSEG_KTIMED("k3wg_pp_kernel", stream, hipLaunchKernelGGL(k3wg_pp_kernel<0>, dim3(gx, pairs, 1), dim3(NTHREADS), lds, stream, pl));
+    if (timing) hipLaunchKernelGGL(k3wg_pp_kernel<1>, dim3(gx, pairs, 1), dim3(NTHREADS), lds, stream, p);
+    else MSSEG_KTIMED("k3wg_pp_kernel", stream, hipLaunchKernelGGL(k3wg_pp_kernel<0>, dim3(gx, pairs, 1), dim3(NTHREADS), lds, stream, p));
     MSSEG_CHECK_LAUNCH("conv3d_k3_wgrad_pp");
     return MSSEG_OK;
 }

@@ -266,8 +266,7 @@ int grid_x(long long groups) {
 // ---- host interface (igemm_fwd.hip dispatches here when eligible) ----------------------------------------
 bool msseg_deconv2_fast_eligible(int dtype, int Cin, int Cout, const void* coarse, long long ldc, const void* fine,
                                  long long ldf, const float* bias) {
-    static const bool off = getenv("MSSEG_NO_DECONV_FAST") != nullptr;
-    if (off || dtype != MSSEG_BF16) return false;
+    if (dtype != MSSEG_BF16) return false;
     if (!((Cin == 32 || Cin == 64) && Cout == 32)) return false;   // weight fragments must fit the register file
     if ((ldc % 8) || (ldf % 8) || ((uintptr_t)coarse & 15) || ((uintptr_t)fine & 15)) return false;
     if (bias && ((uintptr_t)bias & 15)) return false;

@@ -18,8 +18,6 @@
 // Bound: HBM on the 96^3 / 48^3 outputs (8x the input voxels written / read once), launch latency below.
 #include "k3pp.h"
 
-#include <stdlib.h>
-
 namespace {
 
 constexpr int DG_THREADS = 256;
@@ -216,8 +214,7 @@ bool bwd_cfg(int Cin, int Cout, BwdCfg* c) {
 }
 
 bool common_ok(int dtype, const void* coarse, long long ldc, const void* fine, long long ldf, int Cin, int Cout) {
-    static const bool off = getenv("MSSEG_NO_DECONV_GEN") != nullptr;   // A/B switch
-    if (off || dtype != MSSEG_BF16) return false;
+    if (dtype != MSSEG_BF16) return false;
     if ((ldc % 8) || (ldf % 8) || ((uintptr_t)coarse & 15) || ((uintptr_t)fine & 15) || ldc < Cin || ldf < Cout) return false;
     return true;
 }
@@ -262,8 +259,7 @@ bool msseg_deconv2g_bwd_eligible(int dtype, int Cin, int Cout, const void* coars
                                  long long ldf) {
     BwdCfg c;
     if (coarse == nullptr) {   // partial-sum form: no coarse tensor
-        static const bool off = getenv("MSSEG_NO_DECONV_GEN") != nullptr;
-        if (off || dtype != MSSEG_BF16 || (ldf % 8) || ((uintptr_t)fine & 15) || ldf < Cout) return false;
+        if (dtype != MSSEG_BF16 || (ldf % 8) || ((uintptr_t)fine & 15) || ldf < Cout) return false;
     } else if (!common_ok(dtype, coarse, ldc, fine, ldf, Cin, Cout) || (ldc % 4)) {
         return false;
     }
@@ -308,8 +304,7 @@ extern "C" {
 /* 1 when msseg_deconv_k2s2_bwd_partials takes the shape (bf16, channel counts with an instantiation) */
 int msseg_deconv_k2s2_bwd_partials_ok(int Cin, int Cout, int dtype) {
     BwdCfg c;
-    static const bool off = getenv("MSSEG_NO_DECONV_GEN") != nullptr;
-    return (!off && dtype == MSSEG_BF16 && bwd_cfg(Cin, Cout, &c) && Cin % 32 == 0) ? 1 : 0;
+    return (dtype == MSSEG_BF16 && bwd_cfg(Cin, Cout, &c) && Cin % 32 == 0) ? 1 : 0;
 }
 
 /* input gradient of ConvTranspose3d k2 s2 as ONE fp32 stage group in the layout of msseg_conv3d_k3_small_partials

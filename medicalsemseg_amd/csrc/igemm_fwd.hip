@@ -19,8 +19,6 @@
 #include "common.h"
 #include "k3pp.h"
 
-#include <stdlib.h>
-
 #include <type_traits>
 
 namespace {
@@ -59,7 +57,7 @@ struct IgemmParams {
     float* nb_dgamma; float* nb_dbeta; int nb_acc;
 };
 
-template <typename T, int NTAPS, int SRC, int EPI, int TD, int TH, int TW, int WAVES, int NT, int STRIDE = 1, int NSL = 1>
+template <typename T, int NTAPS, int SRC, int EPI, int TD, int TH, int TW, int WAVES, int NT, int STRIDE = 1>
 struct IgemmCfg {
     static constexpr int EPC = DT<T>::EPC;
     static constexpr int CB = 4 * EPC;
@@ -74,11 +72,7 @@ struct IgemmCfg {
     static constexpr int COUTB = NT * 16;
     static constexpr int PLANE = ((HV * 16 + 255) / 256) * 256;
     static constexpr int A_BYTES = ((4 * PLANE + 64 + 255) / 256) * 256;
-    // NSL > 1: the weight image is staged in NSL tap slices (one kd plane each) instead of all 27 taps, which
-    // brings the workgroup under 80 KB of LDS so that two workgroups share a CU and fill each other's bubbles
-    static constexpr int BT = NTAPS / NSL;
-    static constexpr int B_BYTES = BT * 4 * COUTB * 16;
-    static_assert(NTAPS % NSL == 0, "tap slices must divide the taps");
+    static constexpr int B_BYTES = NTAPS * 4 * COUTB * 16;
     static constexpr int STAT_FLOATS = MSSEG_STATS_NMAX * COUTB * 2;
     static constexpr int STAT_BYTES = (EPI == EPI_STORE) ? (STAT_FLOATS + WAVES * COUTB * 2) * 4 + 256 : 0;
     static constexpr int LDS_BYTES = A_BYTES + B_BYTES + STAT_BYTES;
@@ -87,18 +81,12 @@ struct IgemmCfg {
 
 MSSEG_DEVFN int aoff(int q, int plane) { return q * plane + (q >> 1) * 32; }
 
-// DIAG (timing-only ablations, wrong results): 1 = no MFMA, 2 = no LDS fragment reads, 3 = no epilogue stores,
-// 4 = no global prefetch loads
-// DIAG == 5: per-phase cycle counters of workgroup 0 / wave 0 (s_memtime), read back by msseg_debug_phase_cycles()
-__device__ unsigned long long g_phase_cycles[16];
-
-template <typename T, int NTAPS, int SRC, int EPI, int TD, int TH, int TW, int WAVES, int NT, int STRIDE = 1, int NSL = 1, int DIAG = 0>
-__global__ __launch_bounds__(WAVES * 64, (NSL > 1 ? 2 : 1)) void igemm_fwd_kernel(const IgemmParams p) {
-    using C = IgemmCfg<T, NTAPS, SRC, EPI, TD, TH, TW, WAVES, NT, STRIDE, NSL>;
-    constexpr int BT = C::BT;
+template <typename T, int NTAPS, int SRC, int EPI, int TD, int TH, int TW, int WAVES, int NT, int STRIDE = 1>
+__global__ __launch_bounds__(WAVES * 64, 1) void igemm_fwd_kernel(const IgemmParams p) {
+    using C = IgemmCfg<T, NTAPS, SRC, EPI, TD, TH, TW, WAVES, NT, STRIDE>;
     constexpr int EPC = C::EPC, CB = C::CB, PAD = C::PAD, PH = C::PH, PW = C::PW, HV = C::HV, MT = C::MT;
     constexpr int NTHREADS = C::NTHREADS, COUTB = C::COUTB, PLANE = C::PLANE;
-    constexpr bool HREUSE = NTAPS == 27 && STRIDE == 1 && NSL == 1 && TW == 16 && TH % MT == 0 && DIAG != 1 && DIAG != 2;
+    constexpr bool HREUSE = NTAPS == 27 && STRIDE == 1 && TW == 16 && TH % MT == 0;
     extern __shared__ __attribute__((aligned(256))) unsigned char smem[];
     unsigned char* ldsA = smem;
     unsigned char* ldsB = smem + C::A_BYTES;
@@ -258,7 +246,7 @@ __global__ __launch_bounds__(WAVES * 64, (NSL > 1 ? 2 : 1)) void igemm_fwd_kerne
     bool f_interior = false, f_cok = false;
     int f_dB = 0, f_hB = 0, f_wB = 0, f_kb = 0;
     TileCo f_tc{0, 0, 0, 0};
-    auto fetch_setup = [&](const TileCo& tc, int kb, int ks) {
+    auto fetch_setup = [&](const TileCo& tc, int kb) {
         f_tc = tc;
         f_kb = kb;
         if constexpr (SRC == SRC_DIRECT) {
@@ -269,10 +257,9 @@ __global__ __launch_bounds__(WAVES * 64, (NSL > 1 ? 2 : 1)) void igemm_fwd_kerne
             const int nchunk = (p.K - kb * CB + EPC - 1) / EPC;   // valid 16-byte chunks of this channel block
             f_cok = (tid & 3) < nchunk;
         }
-        f_bsrc = (const u32x4_t*)((const unsigned char*)p.wp + (((long long)coutblk * p.NKB + kb) * NSL + ks) * C::B_BYTES);
+        f_bsrc = (const u32x4_t*)((const unsigned char*)p.wp + ((long long)coutblk * p.NKB + kb) * C::B_BYTES);
     };
     auto fetch_a = [&](int it) {
-        if constexpr (DIAG == 4) { pa[it] = u32x4_t{1u, 2u, 3u, 4u}; return; }
         const int i = tid + it * NTHREADS;
         if constexpr (SRC == SRC_DIRECT) {
             if (p.rel32_ok) {
@@ -296,28 +283,21 @@ __global__ __launch_bounds__(WAVES * 64, (NSL > 1 ? 2 : 1)) void igemm_fwd_kerne
         pa[it] = (i < HV * 4) ? load_a_chunk(f_tc, f_kb, i) : u32x4_t{0u, 0u, 0u, 0u};
     };
     auto fetch_b = [&](int it) {
-        if constexpr (DIAG == 4) { pb[it] = u32x4_t{1u, 2u, 3u, 4u}; return; }
         const int i = tid + it * NTHREADS;
         pb[it] = (i < C::B_BYTES / 16) ? f_bsrc[i] : u32x4_t{0u, 0u, 0u, 0u};
     };
-    auto fetch = [&](const TileCo& tc, int kb, int ks, bool with_a, bool with_b) {   // whole stage at once (prologue)
-        fetch_setup(tc, kb, ks);
-        if (with_a) {
+    auto fetch = [&](const TileCo& tc, int kb) {   // whole stage at once (prologue)
+        fetch_setup(tc, kb);
 #pragma unroll
-            for (int it = 0; it < NIT_A; ++it) fetch_a(it);
-        }
-        if (with_b) {
+        for (int it = 0; it < NIT_A; ++it) fetch_a(it);
 #pragma unroll
-            for (int it = 0; it < NIT_B; ++it) fetch_b(it);
-        }
+        for (int it = 0; it < NIT_B; ++it) fetch_b(it);
     };
-    auto commit = [&](bool with_a, bool with_b) {
-        if (with_a) {
+    auto commit = [&](bool with_b) {
 #pragma unroll
-            for (int it = 0; it < NIT_A; ++it) {
-                const int i = tid + it * NTHREADS;
-                if (i < HV * 4) *(u32x4_t*)(ldsA + aoff(i & 3, PLANE) + (i >> 2) * 16) = pa[it];
-            }
+        for (int it = 0; it < NIT_A; ++it) {
+            const int i = tid + it * NTHREADS;
+            if (i < HV * 4) *(u32x4_t*)(ldsA + aoff(i & 3, PLANE) + (i >> 2) * 16) = pa[it];
         }
         if (with_b) {
 #pragma unroll
@@ -369,61 +349,38 @@ __global__ __launch_bounds__(WAVES * 64, (NSL > 1 ? 2 : 1)) void igemm_fwd_kerne
 #pragma unroll
             for (int j = 0; j < NT; ++j) store_one(m, j);
     };
-    unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0;
-    auto mark = [&](int k) {
-        if constexpr (DIAG == 5) {
-            const unsigned long long now = __builtin_readcyclecounter();
-            ph[k] += now - tprev;
-            tprev = now;
-        }
-    };
-    if constexpr (DIAG == 5) tprev = __builtin_readcyclecounter();
-    int tile = blockIdx.x, kb = 0, ks = 0;
+    int tile = blockIdx.x, kb = 0;
     TileCo tc = decode(tile < p.ntiles ? tile : 0);
-    bool a_pending = true, b_pending = true;
-    if (tile < p.ntiles) fetch(tc, 0, 0, true, true);
+    bool b_pending = true;   // the weight image stays resident across tiles when the layer has a single channel block
+    if (tile < p.ntiles) fetch(tc, 0);
     while (tile < p.ntiles) {
         __syncthreads();  // everyone finished reading the previous stage's LDS image
-        mark(0);
-        if constexpr (DIAG == 5) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); mark(1); }
-        commit(a_pending, b_pending);
-        if constexpr (DIAG == 5) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); mark(2); }
+        commit(b_pending);
         __syncthreads();
-        mark(3);
-        // next stage: (tile, kb, ks) advance ks fastest
-        int ntile = tile, nkb = kb, nks = ks + 1;
-        if (nks == NSL) {
-            nks = 0;
-            nkb = kb + 1;
-            if (nkb == p.NKB) { nkb = 0; ntile = tile + gridDim.x; }
-        }
+        // next stage: (tile, kb) advance kb fastest
+        int ntile = tile, nkb = kb + 1;
+        if (nkb == p.NKB) { nkb = 0; ntile = tile + gridDim.x; }
         const TileCo ntc = decode(ntile < p.ntiles ? ntile : 0);
-        a_pending = nks == 0;
-        b_pending = NSL > 1 || p.NKB > 1;
+        b_pending = p.NKB > 1;
         // Side work of this stage, issued from slots spread over the MFMA loop so that it overlaps the matrix pipe
         // instead of serialising all waves in front of it: the previous tile's output stores (held in pend[][]),
         // then the next stage's halo and weight loads.
         const bool st_now = pend_valid, ld_now = ntile < p.ntiles;
         pend_valid = false;
-        fetch_setup(ntc, nkb, nks);
+        fetch_setup(ntc, nkb);
         constexpr int NI_ST = MT * NT, NI = NI_ST + NIT_A + NIT_B;
         auto side_item = [&](int i) {
             if (i < NI_ST) {
                 if (st_now) store_one(i / NT, i % NT);
             } else if (i < NI_ST + NIT_A) {
-                if (ld_now && a_pending) fetch_a(i - NI_ST);
+                if (ld_now) fetch_a(i - NI_ST);
             } else {
                 if (ld_now && b_pending) fetch_b(i - NI_ST - NIT_A);
             }
         };
-        if constexpr (NSL > 1) {
-#pragma unroll
-            for (int i = 0; i < NI; ++i) side_item(i);
-        }
-        mark(4);
 
         const int n = tc.n, d0 = tc.d0, h0 = tc.h0, w0 = tc.w0;
-        if (kb == 0 && ks == 0) {
+        if (kb == 0) {
             if constexpr (EPI == EPI_STORE) {
                 if (do_stats && n != cur_n) {
                     if (cur_n >= 0) flush_stats(cur_n);
@@ -440,23 +397,14 @@ __global__ __launch_bounds__(WAVES * 64, (NSL > 1 ? 2 : 1)) void igemm_fwd_kerne
         // MFMAs of tap t, so the matrix pipe runs under one full LDS latency instead of waiting for it per pair.
         {
             u32x4_t af[2][MT], bf[2][NT];
-            const int ksoff = (NSL > 1) ? ks * (PH * PW * 16) : 0;   // slice ks = kd plane ks of the halo
             auto load_frags = [&](int t, int buf) {
-                const int tap = (NSL > 1) ? t : t;   // local tap within the slice; (kh, kw) from t when sliced by kd
-                const int kd = (NSL > 1) ? 0 : tap / 9, kh = (tap / 3) % 3, kw = tap % 3;
+                const int kd = t / 9, kh = (t / 3) % 3, kw = t % 3;
                 const int toff = (NTAPS == 27) ? ((kd * PH + kh) * PW + kw) * 16 : 0;
-                if constexpr (DIAG == 2) {
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) bf[buf][j] = u32x4_t{(unsigned)(t + j), 1u, 2u, 3u};
-#pragma unroll
-                    for (int m = 0; m < MT; ++m) af[buf][m] = u32x4_t{(unsigned)(t + m), 5u, 6u, 7u};
-                    return;
-                }
 #pragma unroll
                 for (int j = 0; j < NT; ++j)
                     bf[buf][j] = *(const u32x4_t*)(ldsB + bbase + t * (4 * COUTB * 16) + j * 256);
 #pragma unroll
-                for (int m = 0; m < MT; ++m) af[buf][m] = *(const u32x4_t*)(ldsA + abase[m] + ksoff + toff);
+                for (int m = 0; m < MT; ++m) af[buf][m] = *(const u32x4_t*)(ldsA + abase[m] + toff);
             };
             if constexpr (HREUSE) {
                 // Row-reuse order (k3, 16-wide tiles whose MT voxel rows per wave are consecutive in h): for a fixed
@@ -505,38 +453,21 @@ __global__ __launch_bounds__(WAVES * 64, (NSL > 1 ? 2 : 1)) void igemm_fwd_kerne
                         }
                     }
                 }
-            } else if constexpr (NSL == 1) {
+            } else {
                 load_frags(0, 0);
 #pragma unroll
-                for (int t = 0; t < BT; ++t) {
+                for (int t = 0; t < NTAPS; ++t) {
                     const int cur = t & 1;
-                    if (t + 1 < BT) load_frags(t + 1, cur ^ 1);
+                    if (t + 1 < NTAPS) load_frags(t + 1, cur ^ 1);
 #pragma unroll
                     for (int i = 0; i < NI; ++i)
-                        if (i * BT / NI == t) side_item(i);
+                        if (i * NTAPS / NI == t) side_item(i);
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int m = 0; m < MT; ++m)
 #pragma unroll
-                        for (int j = 0; j < NT; ++j) {
-                            if constexpr (DIAG == 1) {
-                                asm volatile("" ::"v"(bf[cur][j]), "v"(af[cur][m]));   // keep the reads alive, no MFMA
-                            } else {
-                                mma_chunk<T>(acc[m][j], bf[cur][j], af[cur][m]);
-                            }
-                        }
+                        for (int j = 0; j < NT; ++j) mma_chunk<T>(acc[m][j], bf[cur][j], af[cur][m]);
                     __builtin_amdgcn_sched_barrier(0);
-                }
-            } else {
-                // two workgroups share the CU in this variant: the other workgroup's waves cover LDS latency, so the
-                // fragments are single-buffered to stay within 256 VGPRs (2 waves per SIMD)
-#pragma unroll
-                for (int t = 0; t < BT; ++t) {
-                    load_frags(t, 0);
-#pragma unroll
-                    for (int m = 0; m < MT; ++m)
-#pragma unroll
-                        for (int j = 0; j < NT; ++j) mma_chunk<T>(acc[m][j], bf[0][j], af[0][m]);
                 }
             }
         }
@@ -545,8 +476,7 @@ __global__ __launch_bounds__(WAVES * 64, (NSL > 1 ? 2 : 1)) void igemm_fwd_kerne
         for (int m = 0; m < MT; ++m)
 #pragma unroll
             for (int j = 0; j < NT; ++j) pend[m][j] = PendT{};
-        mark(5);
-        if (kb == p.NKB - 1 && ks == NSL - 1) {
+        if (kb == p.NKB - 1) {
             // ---------------- epilogue ----------------
     #pragma unroll
             for (int m = 0; m < MT; ++m) {
@@ -581,10 +511,6 @@ __global__ __launch_bounds__(WAVES * 64, (NSL > 1 ? 2 : 1)) void igemm_fwd_kerne
                         const int fd = 2 * dd + (abc >> 2), fh = 2 * dh + ((abc >> 1) & 1), fw = 2 * dw + (abc & 1);
                         const long long fv = (((long long)dn * (2 * p.OD) + fd) * (2 * p.OH) + fh) * (2 * p.OW) + fw;
                         dst = yg + fv * p.ldy + cbase;
-                    }
-                    if constexpr (DIAG == 3) {
-                        asm volatile("" ::"v"(o));
-                        continue;
                     }
                     if (p.vec_store && co + 4 <= p.M) {
                         if (p.bias) {
@@ -637,17 +563,10 @@ __global__ __launch_bounds__(WAVES * 64, (NSL > 1 ? 2 : 1)) void igemm_fwd_kerne
                 }
             }
         }
-        if (kb == p.NKB - 1 && ks == NSL - 1 && p.vec_store) { ptc = tc; pend_valid = true; }
-        mark(6);
-        tile = ntile; kb = nkb; ks = nks; tc = ntc;
+        if (kb == p.NKB - 1 && p.vec_store) { ptc = tc; pend_valid = true; }
+        tile = ntile; kb = nkb; tc = ntc;
     }
     store_pending();
-    if constexpr (DIAG == 5) {
-        if (blockIdx.x == 0 && tid == 0) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) g_phase_cycles[k] = ph[k];
-        }
-    }
     if constexpr (EPI == EPI_STORE) {
         if (do_stats) {
             if (cur_n >= 0) flush_stats(cur_n);
@@ -703,9 +622,9 @@ __global__ __launch_bounds__(256) void k3_stats_finalize_kernel(const K3FinParam
     }
 }
 
-template <typename T, int NTAPS, int SRC, int EPI, int TD, int TH, int TW, int WAVES, int NT, int STRIDE = 1, int NSL = 1, int DIAG = 0>
+template <typename T, int NTAPS, int SRC, int EPI, int TD, int TH, int TW, int WAVES, int NT, int STRIDE = 1>
 int launch_cfg(IgemmParams& p, hipStream_t stream) {
-    using C = IgemmCfg<T, NTAPS, SRC, EPI, TD, TH, TW, WAVES, NT, STRIDE, NSL>;
+    using C = IgemmCfg<T, NTAPS, SRC, EPI, TD, TH, TW, WAVES, NT, STRIDE>;
     p.tiles_d = ceil_div(p.D, TD);
     p.tiles_h = ceil_div(p.H, TH);
     p.tiles_w = ceil_div(p.W, TW);
@@ -718,7 +637,7 @@ int launch_cfg(IgemmParams& p, hipStream_t stream) {
         const long long xh = STRIDE == 1 ? p.H : p.IH, xw = STRIDE == 1 ? p.W : p.IW;
         p.rel32_ok = ((long long)(C::PD + 1) * xh * xw * p.ldx < 0x7fffffffLL) ? 1 : 0;
     }
-    auto kern = igemm_fwd_kernel<T, NTAPS, SRC, EPI, TD, TH, TW, WAVES, NT, STRIDE, NSL, DIAG>;
+    auto kern = igemm_fwd_kernel<T, NTAPS, SRC, EPI, TD, TH, TW, WAVES, NT, STRIDE>;
     static msseg_lds_attr_once attr;
     if (!attr.ensure((const void*)kern, C::LDS_BYTES)) MSSEG_FAIL(MSSEG_ELAUNCH, "igemm: cannot set dynamic LDS size %d", C::LDS_BYTES);
     const int ncb = ceil_div(p.M, C::COUTB);
@@ -742,13 +661,13 @@ int launch_cfg(IgemmParams& p, hipStream_t stream) {
     return MSSEG_OK;
 }
 
-template <typename T, int NTAPS, int SRC, int EPI, int TD, int TH, int TW, int WAVES, int STRIDE = 1, int NSL = 1>
+template <typename T, int NTAPS, int SRC, int EPI, int TD, int TH, int TW, int WAVES, int STRIDE = 1>
 int launch_nt(IgemmParams& p, hipStream_t stream) {
     const int cb = p.cout_block ? p.cout_block : msseg_cout_block(p.M);
     switch (cb) {
-        case 16: return launch_cfg<T, NTAPS, SRC, EPI, TD, TH, TW, WAVES, 1, STRIDE, NSL>(p, stream);
-        case 32: return launch_cfg<T, NTAPS, SRC, EPI, TD, TH, TW, WAVES, 2, STRIDE, NSL>(p, stream);
-        case 48: return launch_cfg<T, NTAPS, SRC, EPI, TD, TH, TW, WAVES, 3, STRIDE, NSL>(p, stream);
+        case 16: return launch_cfg<T, NTAPS, SRC, EPI, TD, TH, TW, WAVES, 1, STRIDE>(p, stream);
+        case 32: return launch_cfg<T, NTAPS, SRC, EPI, TD, TH, TW, WAVES, 2, STRIDE>(p, stream);
+        case 48: return launch_cfg<T, NTAPS, SRC, EPI, TD, TH, TW, WAVES, 3, STRIDE>(p, stream);
     }
     MSSEG_FAIL(MSSEG_EINVAL, "igemm: bad cout block %d", cb);
 }
@@ -759,14 +678,6 @@ int launch_nt(IgemmParams& p, hipStream_t stream) {
 static void k3_plan(int N, int D, int H, int W, int M, int* cfg, int* cb) {
     const int mn = D < H ? (D < W ? D : W) : (H < W ? H : W);
     const int std_cb = msseg_cout_block(M);
-    {   // tuning override for grids below 32 voxels per axis: MSSEG_K3_FORCE="<cfg 1|2>,<cout block 16|32>"
-        static const char* force = getenv("MSSEG_K3_FORCE");
-        if (force && mn < 32 && std_cb == 32) {
-            *cfg = force[0] - '0';
-            *cb = atoi(force + 2);
-            return;
-        }
-    }
     const long long want = (long long)msseg_num_cus() * 3 / 4;
     auto wgs = [&](int td, int th, int tw, int c) {
         return (long long)N * ceil_div(D, td) * ceil_div(H, th) * ceil_div(W, tw) * ceil_div(M, c);
@@ -787,26 +698,8 @@ template <typename T> int launch_k3(IgemmParams& p, hipStream_t stream) {
     int cfg, cb;
     k3_plan(p.N, p.D, p.H, p.W, p.M, &cfg, &cb);
     p.cout_block = cb;
-    if (cfg == 0) {
-        // A/B switch.  Measured on MI355X (round 1): the tap-sliced 2-WG/CU variant is SLOWER (32->32 @96^3: 144 us
-        // vs 110 us) -- weight-slice refetch + 3x barriers cost more than the second workgroup hides.
-        static const bool old_big = getenv("MSSEG_K3_SLICED") == nullptr;
-        if constexpr (sizeof(T) == 2) {
-            static const char* diag = getenv("MSSEG_DIAG");   // timing-only ablations of the dominant kernel
-            if (diag && cb == 32) {
-                p.cout_block = 32;
-                switch (diag[0]) {
-                    case '1': return launch_cfg<T, 27, SRC_DIRECT, EPI_STORE, 4, 8, 16, 8, 2, 1, 1, 1>(p, stream);
-                    case '2': return launch_cfg<T, 27, SRC_DIRECT, EPI_STORE, 4, 8, 16, 8, 2, 1, 1, 2>(p, stream);
-                    case '3': return launch_cfg<T, 27, SRC_DIRECT, EPI_STORE, 4, 8, 16, 8, 2, 1, 1, 3>(p, stream);
-                    case '4': return launch_cfg<T, 27, SRC_DIRECT, EPI_STORE, 4, 8, 16, 8, 2, 1, 1, 4>(p, stream);
-                    case '5': return launch_cfg<T, 27, SRC_DIRECT, EPI_STORE, 4, 8, 16, 8, 2, 1, 1, 5>(p, stream);
-                }
-            }
-        }
-        if (old_big || cb == 48) return launch_nt<T, 27, SRC_DIRECT, EPI_STORE, 4, 8, 16, 8>(p, stream);  // 48-wide: sliced variant spills
-        return launch_nt<T, 27, SRC_DIRECT, EPI_STORE, 2, 8, 16, 4, 1, 3>(p, stream);
-    }
+    // a tap-sliced variant of the big tile with two workgroups per CU measured 144 vs 110 us (32->32 at 96^3) and was removed
+    if (cfg == 0) return launch_nt<T, 27, SRC_DIRECT, EPI_STORE, 4, 8, 16, 8>(p, stream);
     if (cfg == 1) return launch_nt<T, 27, SRC_DIRECT, EPI_STORE, 4, 4, 8, 4>(p, stream);
     return launch_nt<T, 27, SRC_DIRECT, EPI_STORE, 2, 4, 8, 4>(p, stream);
 }
@@ -830,11 +723,6 @@ int msseg_k3_stats_finalize(const K3FinParams& f, int ncb, hipStream_t stream) {
     hipLaunchKernelGGL(k3_stats_finalize_kernel, dim3(ncb, f.nb_stats ? 1 : f.N), dim3(256), 0, stream, f);
     MSSEG_CHECK_LAUNCH("k3_stats_finalize");
     return MSSEG_OK;
-}
-
-// tools-only (not part of include/msseg.h): cycle counters written by the MSSEG_DIAG=5 build of the big-tile kernel
-extern "C" int msseg_debug_phase_cycles(unsigned long long* out8) {
-    return hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_phase_cycles), 8 * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
 }
 
 extern "C" {

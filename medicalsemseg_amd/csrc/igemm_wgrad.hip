@@ -12,8 +12,6 @@
 #include "common.h"
 #include "k3pp.h"
 
-#include <stdlib.h>
-
 namespace {
 
 enum { Q_DIRECT = 0, Q_GATHER = 1, Q_DECONV = 2 };
@@ -477,8 +475,7 @@ int launch_reduce(const ReduceParams& rp, hipStream_t stream) {
     // conv layout: dw[m][k][tap], taps contiguous, no two-level channel index
     const bool conv_layout = rp.s_t == 1 && rp.s_k0 == rp.T && rp.K0 == rp.K && rp.M0 == rp.M && rp.T > 1 && rp.T <= 32 &&
                              rp.s_m0 == (long long)rp.K * rp.T && (rp.cbw == 32 || rp.cbw == 16);
-    static const bool no_rows = getenv("MSSEG_NO_REDUCE_ROWS") != nullptr;   // A/B switch
-    if (rp.nslots <= 32 && conv_layout && !no_rows && ceil_div(rp.K, 32) <= 65535) {
+    if (rp.nslots <= 32 && conv_layout && ceil_div(rp.K, 32) <= 65535) {
         hipLaunchKernelGGL(wgrad_reduce_rows_kernel, dim3(rp.M, ceil_div(rp.K, 32)), dim3(256), 0, stream, rp);
     } else if (rp.nslots <= 32) {
         int rb = (int)((total + 255) / 256);
@@ -513,14 +510,13 @@ int launch_wg(WgradParams& p, ReduceParams& rp, void* workspace, size_t ws_bytes
     const size_t slab_bytes = (size_t)C::SLAB_FLOATS * 4;
     long long gx = msseg_num_cus() * ((C::LDS_BYTES > 80 * 1024) ? 1 : 2);
     // flat (1-tap) problems: a tile is 8 MFMAs per wave behind a load -> LDS -> barrier round trip and a slab is 4 KB, so
-    // resident workgroups are what hides the latency: as many as the 48 KB of LDS per workgroup allow (MSSEG_WG_FLAT_PER_CU)
-    static const int flat_per_cu = getenv("MSSEG_WG_FLAT_PER_CU") ? atoi(getenv("MSSEG_WG_FLAT_PER_CU")) : 3;
+    // resident workgroups are what hides the latency: as many as the 48 KB of LDS per workgroup allow
+    constexpr int flat_per_cu = 3;
     if (NTAPS == 1 && C::LDS_BYTES * flat_per_cu <= 160 * 1024) gx = (long long)msseg_num_cus() * flat_per_cu;
     // Small grids (the 24^3 ... 6^3 levels): every workgroup writes a 110 KB slab whatever it computed, so a full chip
     // of workgroups moves 56 MB of slabs (written, then read by the reduction) for a few GFLOP.  Half a workgroup per CU
     // measured fastest there (sweep 64 ... 512 in profiles/README.md): 30-34 -> 21-25 us per layer.
-    static const int wgs_env = getenv("MSSEG_WG_TOTAL") ? atoi(getenv("MSSEG_WG_TOTAL")) : 0;   // A/B: total workgroups
-    if (NTAPS == 27 && (long long)p.ntiles * pairs <= 4LL * msseg_num_cus()) gx = wgs_env > 0 ? wgs_env : msseg_num_cus() / 2;
+    if (NTAPS == 27 && (long long)p.ntiles * pairs <= 4LL * msseg_num_cus()) gx = msseg_num_cus() / 2;
     if (pairs > 1) gx = (gx + pairs - 1) / pairs;
     if (gx > p.ntiles) gx = p.ntiles;
     const long long fit = (long long)(ws_bytes / (slab_bytes * pairs * wave_slots));
@@ -547,7 +543,7 @@ template <typename T> int launch_wg_k3(WgradParams& p, ReduceParams& rp, void* w
         pp.pten = p.pten; pp.ldp = p.ldp; pp.qten = p.qten; pp.ldq = p.ldq;
         pp.N = p.N; pp.D = p.D; pp.H = p.H; pp.W = p.W; pp.M = p.M; pp.K = p.K; pp.kblks = ceil_div(p.K, 32);
         // grids below 8 voxels per axis fill a quarter of the ping-pong kernel's 4x4x16 tiles: generic kernel (2x4x8 tiles)
-        static const int pp_min_dim = getenv("MSSEG_K3WG_MINDIM") ? atoi(getenv("MSSEG_K3WG_MINDIM")) : 8;   // A/B
+        constexpr int pp_min_dim = 8;
         const int mnd = p.D < p.H ? (p.D < p.W ? p.D : p.W) : (p.H < p.W ? p.H : p.W);
         if (mnd >= pp_min_dim && msseg_k3wg_pp_eligible(pp)) {
             const int pairs = ceil_div(p.M, 32) * ceil_div(p.K, 32);
@@ -565,11 +561,7 @@ template <typename T> int launch_wg_k3(WgradParams& p, ReduceParams& rp, void* w
         }
     }
     const int mn = p.D < p.H ? (p.D < p.W ? p.D : p.W) : (p.H < p.W ? p.H : p.W);
-    if (mn >= 32) {
-        static const bool two_wg = getenv("MSSEG_WGRAD_2WG") != nullptr;   // A/B switch
-        if (two_wg) return launch_wg<T, 27, Q_DIRECT, 2, 8, 16>(p, rp, ws, wsb, st);
-        return launch_wg<T, 27, Q_DIRECT, 4, 8, 16>(p, rp, ws, wsb, st);
-    }
+    if (mn >= 32) return launch_wg<T, 27, Q_DIRECT, 4, 8, 16>(p, rp, ws, wsb, st);
     if (mn >= 12) return launch_wg<T, 27, Q_DIRECT, 4, 4, 8>(p, rp, ws, wsb, st);
     return launch_wg<T, 27, Q_DIRECT, 2, 4, 8>(p, rp, ws, wsb, st);
 }

@@ -51,7 +51,6 @@ struct K3WgParams {
     const void* qten; long long ldq;   // x  (channels K)
     float* slabs;                      // [pair = mblk * kblks + kblk][workgroup][27][32][32] fp32 partial sums
     int N, D, H, W, M, K, kblks;
-    int dbg_noload;                    // timing experiments only
 };
 bool msseg_k3wg_pp_eligible(const K3WgParams& p);
 int msseg_k3wg_pp_grid(const K3WgParams& p);      // workgroups per block pair (= slabs per pair)

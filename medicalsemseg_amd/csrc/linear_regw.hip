@@ -24,8 +24,6 @@
 // with the arithmetic of gelu_kernel (attention.hip) on the bf16-rounded operands, i.e. bit-identical to the unfused chain.
 #include "k3pp.h"
 
-#include <stdlib.h>
-
 namespace {
 
 constexpr int LR_THREADS = 256;
@@ -255,8 +253,7 @@ static bool lr_ks_ok(int ks) { return ks == 2 || ks == 3 || ks == 5 || ks == 6 |
 
 bool msseg_linear_regw_eligible(int dtype, long long NV, int Cin, int Cout, const void* x, long long ldx, const void* y,
                                 long long ldy, const float* bias) {
-    static const bool off = getenv("MSSEG_NO_LINEAR_REGW") != nullptr;   // A/B switch
-    if (off || dtype != MSSEG_BF16 || NV < 1 || Cout % 16 || Cin % 8) return false;
+    if (dtype != MSSEG_BF16 || NV < 1 || Cout % 16 || Cin % 8) return false;
     const int ks = (Cin + 31) / 32;
     if ((!lr_ks_ok(ks) || pick_nh(ks, Cout) == 0) && !ksplit_ok(Cin, Cout, NV)) return false;
     if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || (ldx % 8) || (ldy % 8) || ldx < Cin || ldy < Cout) return false;
@@ -313,8 +310,7 @@ template <int EPI> static int launch_gelu(const LinParams& p, int ks, int nh, in
 extern "C" {
 
 int msseg_linear_gelu_ok(long long NV, int Cin, int Cout, int dtype) {
-    static const bool off = getenv("MSSEG_NO_LINEAR_GELU") != nullptr || getenv("MSSEG_NO_LINEAR_REGW") != nullptr;   // A/B switch
-    if (off || dtype != MSSEG_BF16 || NV < 1 || Cout % 16 || Cin % 8) return 0;
+    if (dtype != MSSEG_BF16 || NV < 1 || Cout % 16 || Cin % 8) return 0;
     return lr_gelu_shape(Cin, Cout, nullptr, nullptr) ? 1 : 0;
 }
 
@@ -343,8 +339,7 @@ int msseg_linear_gelu_fwd(const void* x, long long ldx, const void* wp, const fl
  * output and res, as the unfused chain forms it).  msseg_linear_add_ok() == 1 for the widths of the register-resident-weight
  * kernel (Cin <= 768 at the Swin widths); callers keep Linear + add otherwise. */
 int msseg_linear_add_ok(long long NV, int Cin, int Cout, int dtype) {
-    static const bool off = getenv("MSSEG_NO_LINEAR_ADD") != nullptr || getenv("MSSEG_NO_LINEAR_REGW") != nullptr;   // A/B switch
-    if (off || dtype != MSSEG_BF16 || NV < 1 || Cout % 16 || Cin % 8) return 0;
+    if (dtype != MSSEG_BF16 || NV < 1 || Cout % 16 || Cin % 8) return 0;
     const int ks = (Cin + 31) / 32;
     return (lr_ks_ok(ks) && pick_nh(ks, Cout) != 0) ? 1 : 0;
 }

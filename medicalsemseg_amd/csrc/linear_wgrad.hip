@@ -19,8 +19,6 @@
 // memory holds token rows), NTP + NTQ fragments for NTP x NTQ (+ NTP) MFMAs.
 #include "common.h"
 
-#include <stdlib.h>
-
 namespace {
 
 constexpr int TT = 128;            // tokens per chunk
@@ -287,9 +285,8 @@ template <int NTP, int NTQ, bool DCV = false> int launch_lwg(const LwgParams& p,
 // (32 x 32) block pair of the [Cin][8 * Cout] matrix its own workgroup column, each walking all voxels (34 us per BasicUNet
 // layer, 64 us per Swin-UNETR layer); here a workgroup reads whole rows -- the coarse row and the 8 child rows it gathers.
 bool msseg_lwg_deconv_ok(int dtype, long long NV, int Cin, int Cout, const void* x, long long ldx, const void* dy, long long lddy) {
-    static const bool off = getenv("MSSEG_NO_LINEAR_WGRAD") != nullptr || getenv("MSSEG_NO_DECONV_LWG") != nullptr;   // A/B switch
     Shape s;
-    if (off || dtype != MSSEG_BF16 || NV < 100000 || NV > 0x7fffffffLL / 8 || Cout % 8) return false;
+    if (dtype != MSSEG_BF16 || NV < 100000 || NV > 0x7fffffffLL / 8 || Cout % 8) return false;
     if ((((uintptr_t)x | (uintptr_t)dy) & 15) || (ldx % 8) || (lddy % 8) || ldx < Cin || lddy < Cout) return false;
     return pick_shape_dcv(8 * Cout, Cin, &s);
 }
@@ -332,9 +329,8 @@ int msseg_lwg_deconv_wgrad(const void* x, long long ldx, const void* dy, long lo
 extern "C" {
 
 int msseg_linear_wgrad_ok(long long NV, int Cin, int Cout, int dtype) {
-    static const bool off = getenv("MSSEG_NO_LINEAR_WGRAD") != nullptr;   // A/B switch
     Shape s;
-    if (off || dtype != MSSEG_BF16 || NV < 1 || NV > 0x7fffffffLL || Cin > 4096 || Cout > 4096) return 0;
+    if (dtype != MSSEG_BF16 || NV < 1 || NV > 0x7fffffffLL || Cin > 4096 || Cout > 4096) return 0;
     // a few hundred tokens against a large weight (last Swin stage): the partial blocks dominate, the generic kernel + channel
     // sum measured 3 us faster per layer (tools/bench_linear.py: 432 tokens, 384 -> 1152 / 1536, 1536 -> 384)
     if (NV < 1024 && (long long)Cin * Cout > 200000) return 0;

@@ -382,8 +382,7 @@ __global__ __launch_bounds__(W_THREADS) void stem_wgrad_kernel(const StemWgParam
 }  // namespace
 
 bool msseg_stem_eligible(int dtype, int Cin, int Cout, int k, int s, int pd, long long ldx, long long ldy, const void* y) {
-    static const bool off = getenv("MSSEG_NO_STEM") != nullptr;
-    return !off && dtype == MSSEG_BF16 && Cin == 1 && ((k == 3 && pd == 1) || (k == 1 && pd == 0)) && s == 1 &&
+    return dtype == MSSEG_BF16 && Cin == 1 && ((k == 3 && pd == 1) || (k == 1 && pd == 0)) && s == 1 &&
            (Cout % 32 == 0 || Cout % 48 == 0) && Cout <= 256 &&
            ldx >= 1 && (ldy % 4) == 0 && (((uintptr_t)y) & 7) == 0;
 }

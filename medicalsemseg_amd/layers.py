@@ -124,83 +124,6 @@ class PackedCache:
         return rec["value"]
 
 
-class _WgradSide:
-    """Weight-gradient kernels on a second HIP stream.
-
-    In the backward pass only the input-gradient chain is serial; every weight gradient depends on tensors that exist
-    when its layer is reached and is needed only by the optimizer.  The whole-network backward functions open a
-    section (`begin`), the layers then issue their wgrad kernels through `run` on the side stream (after the main
-    stream's work so far), and `join` makes the main stream wait for them.  The full-chip wgrad kernels of the
-    high-resolution levels then overlap the many small kernels of the deep levels instead of queueing behind them.
-    The side stream owns the wgrad workspace (all wgrad launches are serial on it); tensors handed to it are kept
-    alive until the join."""
-
-    INLINE, SIDE, DEFER = 0, 1, 2
-
-    def __init__(self):
-        self.streams = {}
-        self.active = None
-        self.mode = self.INLINE
-        self.keep = []
-        self.deferred = []
-
-    def begin(self, device):
-        # Measured on MI355X (round 1, UNet 96^3 B=2): 5.38 ms/step with the side stream vs 5.22 ms without -- the
-        # persistent wgrad workgroups take a CU's whole register file, so nothing co-resides and the small kernels only
-        # queue behind them.  Kept as an opt-in experiment.
-        if not torch.cuda.is_available() or not os.environ.get("MSSEG_WGRAD_STREAM"):
-            return
-        st = self.streams.get(device)
-        if st is None:
-            st = self.streams[device] = torch.cuda.Stream(device=device)
-        self.active = st
-        self.mode = self.INLINE
-
-    def set_mode(self, mode):
-        """INLINE: on the calling stream (full-chip layers with nothing small to overlap); SIDE: on the side stream
-        right away (small layers); DEFER: collected and issued to the side stream by flush() -- full-chip wgrads that
-        should run under the small kernels of the deep levels rather than against the next full-chip dgrad."""
-        if self.active is not None:
-            if mode == self.INLINE and self.mode != self.INLINE:
-                # back on the calling stream: its weight-gradient launches share the slab workspace with the side
-                # stream's, so everything issued there must have finished first
-                self.flush()
-                torch.cuda.current_stream().wait_stream(self.active)
-            self.mode = mode
-
-    def _issue(self, fn):
-        st = self.active
-        st.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(st):
-            fn()
-
-    def run(self, fn, *tensors):
-        if self.active is None or self.mode == self.INLINE:
-            return fn()
-        self.keep.extend(tensors)
-        if self.mode == self.DEFER:
-            self.deferred.append(fn)
-        else:
-            self._issue(fn)
-
-    def flush(self):
-        if self.active is not None:
-            for fn in self.deferred:
-                self._issue(fn)
-        self.deferred = []
-
-    def join(self):
-        self.flush()
-        st, self.active = self.active, None
-        self.mode = self.INLINE
-        if st is not None:
-            torch.cuda.current_stream().wait_stream(st)
-        self.keep.clear()
-
-
-WGRAD_SIDE = _WgradSide()
-
-
 # set by a network's inference-only forward (nothing kept for a backward: models/unet.py _forward_cl(keep=False)) around its
 # layer calls: enables forms that only pay when no backward follows (Conv3.halves_ok: K-split of the 24^3-level convs)
 INFERENCE_FORWARD = False
@@ -247,7 +170,8 @@ def _norm_grad_bufs(nrm):
     """(dgamma, dbeta, accumulate) buffers of an InstNormAct for the fused InstanceNorm-backward epilogues"""
     if nrm.gamma is not None and nrm.gamma.requires_grad:
         dg, acc = _grad_buf(nrm.gamma)
-        db, _ = _grad_buf(nrm.beta)
+        db, acc2 = _grad_buf(nrm.beta)
+        assert acc == acc2
         return dg, db, acc
     return None, None, False
 
@@ -273,8 +197,7 @@ class Conv3:
         stats = None
         if self._gather(dtype):
             wp = self.cache.get(self.w, dtype, "g", lambda: hip.pack_conv_gather(self.w.detach(), dtype))
-            if (self.cin == 1 and dtype == torch.bfloat16 and (self.cout % 32 == 0 or self.cout % 48 == 0) and self.cout <= 256
-                    and not os.environ.get("MSSEG_NO_STEM")):
+            if self.cin == 1 and dtype == torch.bfloat16 and (self.cout % 32 == 0 or self.cout % 48 == 0) and self.cout <= 256:
                 # the one-channel stem: dedicated kernel with the statistics fused
                 if want_stats and x.shape[0] <= 8:
                     stats = torch.empty(x.shape[0], self.cout, 2, dtype=torch.float32, device=x.device)
@@ -370,9 +293,9 @@ class Conv3:
         if self.w.requires_grad:
             g, acc = _grad_buf(self.w)
             if self._gather(dtype):
-                WGRAD_SIDE.run(lambda: hip.conv3d_gather_wgrad(x, dy, g, self.cin, self.cout, 3, 1, 1, acc), x, dy)
+                hip.conv3d_gather_wgrad(x, dy, g, self.cin, self.cout, 3, 1, 1, acc)
             else:
-                WGRAD_SIDE.run(lambda: hip.conv3d_k3_wgrad(x, dy, g, self.cin, self.cout, acc), x, dy)
+                hip.conv3d_k3_wgrad(x, dy, g, self.cin, self.cout, acc)
         if self.b is not None and self.b.requires_grad:
             g, acc = _grad_buf(self.b)
             if bias_grad_is_zero:
@@ -414,11 +337,7 @@ class Conv3:
         if next_norm is not None:
             nrm, yraw, stats, act = next_norm
             if dy.shape[0] <= 8 and self.cin % 4 == 0:
-                dg = db = None
-                acc = False
-                if nrm.gamma is not None and nrm.gamma.requires_grad:
-                    dg, acc = _grad_buf(nrm.gamma)
-                    db, _ = _grad_buf(nrm.beta)
+                dg, db, acc = _norm_grad_bufs(nrm)
                 red = hip.conv3d_k3_dgrad_inbwd(dy, wp, dx, self.cout, self.cin, yraw, act, stats, nrm.slope, nrm.eps,
                                                 dg, db, acc)
                 return dx, red
@@ -445,14 +364,13 @@ class Conv1:
         if self._gather(dtype):
             wp = self.cache.get(self.w, dtype, "g", lambda: hip.pack_conv_gather(self.w.detach(), dtype))
             if (want_stats and self.cin == 1 and dtype == torch.bfloat16 and x.dim() == 5 and x.shape[0] <= 8 and hip.ld(y) == self.cout
-                    and (self.cout % 32 == 0 or self.cout % 48 == 0) and self.cout <= 256 and not os.environ.get("MSSEG_NO_STEM")):
+                    and (self.cout % 32 == 0 or self.cout % 48 == 0) and self.cout <= 256):
                 # the shortcut conv on the one-channel input: stem kernel (centre tap) with the statistics fused
                 stats = torch.empty(x.shape[0], self.cout, 2, dtype=torch.float32, device=x.device)
                 hip.conv3d_stem(x, wp, self.b, y, self.cout, stats, k=1)
                 return y, stats
             hip.conv3d_gather(x, wp, self.b, y, self.cin, self.cout, 1, 1, 0)
-        elif (self.cout <= 4 and self.cin <= 64 and x.shape[-1] == self.cin and self.w.is_contiguous()
-              and not os.environ.get("MSSEG_NO_HEAD_KERNEL")):
+        elif self.cout <= 4 and self.cin <= 64 and x.shape[-1] == self.cin and self.w.is_contiguous():
             # segmentation head (2-4 classes): streaming kernel on the fp32 weight as it is
             hip.conv3d_k1_head(x, self.w.detach(), self.b, y, self.cin, self.cout)
         else:
@@ -469,8 +387,7 @@ class Conv1:
         activation (backward): the unit's activation tensor is then never written or read"""
         epc = 16 // yraw.element_size()
         return (self.cout <= 4 and self.cin <= 64 and self.cin % epc == 0 and yraw.shape[-1] == self.cin
-                and hip.ld(yraw) % epc == 0 and yraw.data_ptr() % 16 == 0 and self.w.is_contiguous()
-                and not os.environ.get("MSSEG_NO_HEAD_KERNEL") and not os.environ.get("MSSEG_NO_HEAD_FUSE"))
+                and hip.ld(yraw) % epc == 0 and yraw.data_ptr() % 16 == 0 and self.w.is_contiguous())
 
     def fwd_norm(self, yraw, stats, nrm, out):
         return hip.conv3d_k1_head_norm(yraw, stats, nrm.gamma, nrm.beta, nrm.slope, nrm.eps, self.w.detach(), self.b, out,
@@ -502,15 +419,14 @@ class Conv1:
         if self.w.requires_grad:
             g, acc = _grad_buf(self.w)
             if self._gather(dtype):
-                WGRAD_SIDE.run(lambda: hip.conv3d_gather_wgrad(x, dy[..., :self.cout], g, self.cin, self.cout, 1, 1, 0, acc), x, dy)
+                hip.conv3d_gather_wgrad(x, dy[..., :self.cout], g, self.cin, self.cout, 1, 1, 0, acc)
             elif hip.linear_wgrad_ok(x, self.cin, self.cout):
                 # weight and bias gradient from one pass over the voxels (csrc/linear_wgrad.hip)
                 gb, bacc = _grad_buf(self.b) if (self.b is not None and self.b.requires_grad) else (None, False)
-                WGRAD_SIDE.run(lambda: hip.linear_wgrad(x, dy[..., :self.cout], g.view(self.cout, self.cin), gb, self.cin,
-                                                        self.cout, acc, bacc), x, dy)
+                hip.linear_wgrad(x, dy[..., :self.cout], g.view(self.cout, self.cin), gb, self.cin, self.cout, acc, bacc)
                 fused_bias = True
             else:
-                WGRAD_SIDE.run(lambda: hip.conv3d_k1_wgrad(x, dy[..., :self.cout], g, self.cin, self.cout, acc), x, dy)
+                hip.conv3d_k1_wgrad(x, dy[..., :self.cout], g, self.cin, self.cout, acc)
         if self.b is not None and self.b.requires_grad and not fused_bias:
             g, acc = _grad_buf(self.b)
             hip.channel_sum(dy[..., :self.cout], g, acc)
@@ -523,7 +439,7 @@ class Conv1:
         dyk = dy if dy_channels is None else dy[..., :kpad]
         epc = 16 // dy.element_size()
         if (next_norm is not None and self.cout <= 4 and kpad >= 4 and self.cin <= 64 and self.cin % epc == 0 and hip.ld(dyk) % epc == 0
-                and dyk.data_ptr() % 16 == 0 and self.w.is_contiguous() and not os.environ.get("MSSEG_NO_HEAD_KERNEL")):
+                and dyk.data_ptr() % 16 == 0 and self.w.is_contiguous()):
             # segmentation head: streaming kernel on the fp32 weight, with the receiving layer's backward sums
             nrm, yraw, stats, act = next_norm
             dg, db, acc = _norm_grad_bufs(nrm)
@@ -568,12 +484,12 @@ class Deconv2:
         return y
 
     def _bwd_k4(self, x, dy, need_dx, next_norm):
-        """k = s = 4: weight gradient on the side stream, bias gradient as a channel sum over dy, input gradient; the
+        """k = s = 4: weight gradient, bias gradient as a channel sum over dy, input gradient; the
         receiving layer's InstanceNorm-backward sums are not fused here (red = None: the norm runs its own reduction)"""
         dtype = x.dtype
         if self.w.requires_grad:
             g, acc = _grad_buf(self.w)
-            WGRAD_SIDE.run(lambda: hip.deconv_k4s4_wgrad(x, dy, g, self.cin, self.cout, acc), x, dy)
+            hip.deconv_k4s4_wgrad(x, dy, g, self.cin, self.cout, acc)
         if self.b is not None and self.b.requires_grad:
             g, acc = _grad_buf(self.b)
             hip.channel_sum(dy, g, acc)
@@ -592,7 +508,7 @@ class Deconv2:
         dtype = x.dtype
         if self.w.requires_grad:
             g, acc = _grad_buf(self.w)
-            WGRAD_SIDE.run(lambda: hip.deconv_k2s2_wgrad(x, dy, g, self.cin, self.cout, acc), x, dy)
+            hip.deconv_k2s2_wgrad(x, dy, g, self.cin, self.cout, acc)
         want_db = self.b is not None and self.b.requires_grad
         if not need_dx:
             if want_db:
@@ -641,7 +557,7 @@ class InstNormAct:
             stats = hip.channel_stats(y_raw)
         a = out if out is not None else torch.empty_like(y_raw, memory_format=torch.contiguous_format)
         if pooled is not None:
-            if residual is None and hip.instnorm_pool_ok(y_raw, a, pooled) and not os.environ.get("MSSEG_NO_NORM_POOL"):
+            if residual is None and hip.instnorm_pool_ok(y_raw, a, pooled):
                 hip.instnorm_act_pool_fwd(y_raw, stats, self.gamma, self.beta, a, pooled, self.slope, self.eps)
                 return a, stats
             hip.instnorm_act_fwd(y_raw, stats, self.gamma, self.beta, a, self.slope, self.eps, residual)
@@ -654,8 +570,7 @@ class InstNormAct:
         """Encoder level: the gradient of this layer's output is skip_grad + maxpool-backward(pooled_grad).  One kernel
         forms it (dense) together with this layer's backward sums; returns (da, red) for `bwd(..., red=red)`, or None when
         the shape is not eligible (the caller then runs maxpool2_bwd and the plain backward)."""
-        if (os.environ.get("MSSEG_NO_NORM_POOL") or os.environ.get("MSSEG_NO_POOL_BWD_FUSE")
-                or not hip.instnorm_pool_ok(y_raw, skip_grad, pooled_grad)):
+        if not hip.instnorm_pool_ok(y_raw, skip_grad, pooled_grad):
             return None
         da = torch.empty(y_raw.shape, dtype=y_raw.dtype, device=y_raw.device)
         dg, db, acc = _norm_grad_bufs(self)
@@ -696,8 +611,7 @@ class ConvNormAct:
     def fwd(self, x, out=None, pooled=None):
         cv, nm = self.conv, self.norm
         if (INFERENCE_FORWARD and pooled is None and cv.cin == 1 and x.dtype == torch.bfloat16 and x.shape[0] <= 8
-                and (cv.cout % 32 == 0 or cv.cout % 48 == 0) and cv.cout <= 256 and not os.environ.get("MSSEG_NO_STEM")
-                and not os.environ.get("MSSEG_NO_STEM_TWICE")):
+                and (cv.cout % 32 == 0 or cv.cout % 48 == 0) and cv.cout <= 256 and not os.environ.get("MSSEG_NO_STEM_TWICE")):
             # inference, the one-channel stem unit: a statistics-only launch, then the conv again with InstanceNorm + LeakyReLU
             # in its epilogue -- the raw output is never written and the normalisation pass over it (read + write of the
             # largest tensor of the network) disappears; the conv itself reads one channel and is bound by its output write

@@ -13,8 +13,6 @@ gradient is accumulated into the skip gradient, and parameter gradients land dir
 """
 from __future__ import annotations
 
-import os
-
 from typing import Sequence
 
 import torch
@@ -269,22 +267,14 @@ class _UNetFn(torch.autograd.Function):
         if dl is None:
             dl = torch.zeros(N, D, H, W, LOGIT_LD, dtype=T, device=dev)
             hip.to_channels_last(dlogits.contiguous(), dl[..., :C])
-        layers.WGRAD_SIDE.begin(dev)
-        try:
-            return _UNetFn._backward_body(ctx, net, saved, dl, f, n_in)
-        finally:
-            layers.WGRAD_SIDE.join()
+        return _UNetFn._backward_body(ctx, net, saved, dl, f, n_in)
 
     @staticmethod
     def _backward_body(ctx, net, saved, dl, f, n_in):
-        side = layers.WGRAD_SIDE
-        side.set_mode(side.DEFER if os.environ.get("MSSEG_WGRAD_STREAM") == "defer" else side.INLINE)
         # Every gradient that reaches the second conv+norm unit of a level comes from a flat input-gradient kernel (the
         # 1x1x1 output conv, a transposed conv): those kernels also produce the unit's InstanceNorm-backward sums
         # (`red_c1`), which saves its separate reduction pass over three full tensors.
         def unit_norm(cna, sv):
-            if os.environ.get("MSSEG_NO_FLAT_INBWD"):    # A/B switch: separate reduction pass
-                return None
             return (cna.norm, sv[1], sv[2], sv[3])      # (InstNormAct, yraw, stats, act) of a ConvNormAct's saved tuple
 
         def pair(r):                                     # (dx, red) with or without the fused sums
@@ -300,9 +290,6 @@ class _UNetFn(torch.autograd.Function):
         for j in range(3, -1, -1):  # decoder levels 0..3 in reverse order of execution
             up, c0, c1 = net._dec[j]
             lvl = 3 - j
-            if lvl == 2:   # the deep levels begin: their small kernels run under the deferred full-chip wgrads
-                side.flush()
-                side.set_mode(side.SIDE)
             up_in, s0, s1 = saved["dec"][j]
             g, red = c1.bwd(s1, g, True, red=red_c1, next_saved=s0, next_cna=c0)
             dcat = c0.bwd(s0, g, True, red=red)
@@ -320,22 +307,13 @@ class _UNetFn(torch.autograd.Function):
 
     @staticmethod
     def _run_tail(net, saved, g, skip_grads):
-        side = layers.WGRAD_SIDE
-        side.begin(g.device)
-        try:
-            side.set_mode(side.SIDE)
-            _UNetFn._encoder_bwd(net, saved, g, None, skip_grads, (3, 2, 1, 0))
-        finally:
-            side.join()
+        _UNetFn._encoder_bwd(net, saved, g, None, skip_grads, (3, 2, 1, 0))
 
     @staticmethod
     def _encoder_bwd(net, saved, g, red_c1, skip_grads, levels):
-        side = layers.WGRAD_SIDE
         for lvl in levels:
             c0, c1 = net._enc[lvl]
             s0, s1 = saved["enc"][lvl]
-            if lvl == 1:
-                side.set_mode(side.INLINE)
             red_in = red_c1 if lvl == 4 else None
             if lvl < 4:
                 # gradient of the skip (written by the decoder) + max-pool path from the level below: formed by the kernel

@@ -1445,10 +1445,8 @@ def test_resblock_small_grid_forward_backward(monkeypatch, cin, cout, sp, N):
             if w is not None:
                 w.grad = None
         blk = layers.ResBlock(w1, w2, w3)
-        layers.WGRAD_SIDE.begin(xg.device)
         o, saved = blk.fwd(xg)
         dx = blk.bwd(saved, dog, True)
-        layers.WGRAD_SIDE.join()
         res[mode] = (o.float().clone(), dx.float().clone(), w1.grad.clone(), w2.grad.clone())
     monkeypatch.delenv("MSSEG_NO_K3_SMALL", raising=False)
     # torch reference
@@ -1503,12 +1501,10 @@ def test_resblock_large_grid_shortcut_gradient_accumulated(monkeypatch, cin, cou
             if w is not None:
                 w.grad = None
         blk = layers.ResBlock(w1, w2, w3)
-        layers.WGRAD_SIDE.begin(xg.device)
         o, saved = blk.fwd(xg)
         if mode == "accum":
             assert blk.c1.dgrad_accumulate_ok(saved[1])
         dx = blk.bwd(saved, dog, True)
-        layers.WGRAD_SIDE.join()
         res[mode] = (dx.float().clone(), w1.grad.clone())
     monkeypatch.delenv("MSSEG_NO_DGRAD_ACCUM", raising=False)
     assert torch.equal(res["accum"][1], res["add"][1])

@@ -1,7 +1,7 @@
 """Per-shape timing of the 48-input-channel ping-pong kernel (csrc/conv3d_k3_c48.hip) on the Swin-UNETR decoder shapes:
 forward with statistics, plain input gradient, input gradient with the fused InstanceNorm-backward sums, the accumulate
 launch; each entry is a hipGraph of REP launches (the statistics-finalize launch of the fused modes included).
-usage: python tools/bench_c48.py [batch]        (MSSEG_NO_K3C48=1: the generic kernel on the same shapes)"""
+usage: python tools/bench_c48.py [batch]"""
 import os
 import sys
 

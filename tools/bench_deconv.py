@@ -3,7 +3,7 @@ gradient, weight gradient; us per call (hipGraph of REP calls) and the HBM-bound
 Then the k = s = 4 shapes of the patch-4 Swin-UNETR (batch 2: coarse 24^3 48->48 and 32->32; coarse 32^3 48->48 for 128^3
 volumes) with the same columns, next to torch.nn.functional.conv_transpose3d (bf16, channels_last_3d: forward, and the
 input + weight gradient of one autograd backward) on the same device.
-usage: [MSSEG_NO_DECONV_GEN=1] [MSSEG_NO_DECONV_LWG=1] python tools/bench_deconv.py"""
+usage: python tools/bench_deconv.py"""
 import os
 import sys
 

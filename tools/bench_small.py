@@ -13,7 +13,7 @@ B = int(sys.argv[1]) if len(sys.argv) > 1 else 2
 REP = 10
 dev = torch.device("cuda:0")
 dt = torch.bfloat16
-LAYERS = [(12, 128, 128)] if os.environ.get("MSSEG_K3S_DBG") else [(12, 64, 128), (12, 128, 128), (12, 256, 128), (6, 128, 256), (6, 256, 256), (24, 32, 64), (24, 64, 64), (24, 128, 64)]
+LAYERS = [(12, 64, 128), (12, 128, 128), (12, 256, 128), (6, 128, 256), (6, 256, 256), (24, 32, 64), (24, 64, 64), (24, 128, 64)]
 
 
 def timed(fn):
