@@ -536,16 +536,20 @@ int launch_wg(WgradParams& p, ReduceParams& rp, void* workspace, size_t ws_bytes
     return launch_reduce(rp, stream);
 }
 
+// grids below 8 voxels per axis fill a quarter of the ping-pong kernel's 4x4x16 tiles: generic kernel (2x4x8 tiles)
+bool k3wg_pp_grid_ok(int D, int H, int W) {
+    constexpr int pp_min_dim = 8;
+    const int mnd = D < H ? (D < W ? D : W) : (H < W ? H : W);
+    return mnd >= pp_min_dim;
+}
+
 template <typename T> int launch_wg_k3(WgradParams& p, ReduceParams& rp, void* ws, size_t wsb, hipStream_t st) {
     if constexpr (sizeof(T) == 2) {
         // large grids with 32-multiple channel counts: the ping-pong kernel (conv3d_k3_wgrad_pp.hip)
         K3WgParams pp{};
         pp.pten = p.pten; pp.ldp = p.ldp; pp.qten = p.qten; pp.ldq = p.ldq;
         pp.N = p.N; pp.D = p.D; pp.H = p.H; pp.W = p.W; pp.M = p.M; pp.K = p.K; pp.kblks = ceil_div(p.K, 32);
-        // grids below 8 voxels per axis fill a quarter of the ping-pong kernel's 4x4x16 tiles: generic kernel (2x4x8 tiles)
-        constexpr int pp_min_dim = 8;
-        const int mnd = p.D < p.H ? (p.D < p.W ? p.D : p.W) : (p.H < p.W ? p.H : p.W);
-        if (mnd >= pp_min_dim && msseg_k3wg_pp_eligible(pp)) {
+        if (k3wg_pp_grid_ok(p.D, p.H, p.W) && msseg_k3wg_pp_eligible(pp)) {
             const int pairs = ceil_div(p.M, 32) * ceil_div(p.K, 32);
             int gx = msseg_k3wg_pp_grid(pp);
             const long long fit = (long long)(wsb / ((size_t)27 * 32 * 32 * 4 * pairs));
@@ -599,7 +603,7 @@ int msseg_conv3d_k3_wgrad_kernel(int N, int D, int H, int W, int Cin, int Cout, 
     K3WgParams pp{};
     pp.pten = (const void*)256; pp.ldp = Cout; pp.qten = (const void*)256; pp.ldq = Cin;
     pp.N = N; pp.D = D; pp.H = H; pp.W = W; pp.M = Cout; pp.K = Cin; pp.kblks = ceil_div(Cin, 32);
-    return msseg_k3wg_pp_eligible(pp) ? 3 : 0;
+    return (k3wg_pp_grid_ok(D, H, W) && msseg_k3wg_pp_eligible(pp)) ? 3 : 0;   // the rule of launch_wg_k3
 }
 
 int msseg_conv3d_k3_wgrad(const void* x, long long ldx, const void* dy, long long lddy, float* dw, int N, int D, int H,
