@@ -321,6 +321,46 @@ int msseg_dwconv3d_k3_wgrad(const void* x, long long ldx, const void* dy, long l
                             size_t scratch_bytes, int dtype, msseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Depthwise Conv3d with an odd kernel K in {3, 5, 7, 9, 11}, stride 1, padding K / 2, groups = channels, no bias: the focal
+ * convolutions of FocalNet (models/backbones/focalnet_3d.py:73-81).  x, y channels-last [N, D, H, W, C] with voxel strides
+ * ldx / ldy (a channel slice of a wider buffer is fine), C % 8 == 0 for both dtypes, any D, H, W >= 1.  w_taps = the weight
+ * [C, 1, K, K, K] transposed to tap-major [K^3][C] in the tensors' dtype; flip = 1 mirrors the taps (the input gradient).
+ * fp32 accumulation.  Any other K or C returns MSSEG_EINVAL.
+ * wgrad: dw (torch layout [C, 1, K, K, K], fp32) written or accumulated; partial rows in `workspace`
+ * (msseg_dwconv3d_wgrad_workspace_bytes; a smaller one, down to one row of K^3 * C floats, is used as far as it goes) are
+ * added in row order by a second kernel -- deterministic, no atomics.
+ * ------------------------------------------------------------------------------------------- */
+int msseg_dwconv3d_fwd(const void* x, long long ldx, const void* w_taps, void* y, long long ldy, int N, int D, int H, int W,
+                       int C, int K, int flip, int dtype, msseg_stream_t stream);
+size_t msseg_dwconv3d_wgrad_workspace_bytes(int N, int D, int H, int W, int C, int K, int dtype);
+int msseg_dwconv3d_wgrad(const void* x, long long ldx, const void* dy, long long lddy, float* dw, int accumulate, int N, int D,
+                         int H, int W, int C, int K, void* workspace, size_t workspace_bytes, int dtype, msseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Focal modulation (models/backbones/focalnet_3d.py:83-106) on channels-last token volumes of N samples x S voxels x C
+ * channels (C a multiple of the 16-byte chunk).  q and the gates are channel ranges of a wider Linear output (voxel strides
+ * ldq / ldg; `gates` points at gate 0 of voxel 0); the other activations are dense.
+ * spatial_sum: out0[n][c] = scale * sum_v x[n][v][c] * (g ? g[n][v * ldg] : 1); mode 0 also writes out1 = GELU(out0) (if not
+ *   null), mode 1 multiplies by gelu'(m_in[n][c]).  Fixed-order sums through `scratch` (msseg_reduce_scratch_bytes()).
+ * aggregate_fwd: out = c1 * g0 + c2 * g1 + gm[n][c] * g2.
+ * aggregate_bwd: dc1 = da * g0, dc2 = da * g1 + dmv[n][c], dgates[v][0..2] = sum_c da * (c1, c2, gm) and zeros in
+ *   dgates[v][3 .. gate_width - 1].
+ * mul_fwd: y = q * h.  mul_bwd: dq = dy * h (voxel stride lddq), dh = dy * q.
+ * ------------------------------------------------------------------------------------------- */
+int msseg_focal_spatial_sum(const void* x, long long ldx, const void* g, long long ldg, const float* m_in, float* out0, float* out1,
+                            float scale, int mode, int N, long long S, int C, void* scratch, size_t scratch_bytes, int dtype,
+                            msseg_stream_t stream);
+int msseg_focal_aggregate_fwd(const void* c1, const void* c2, const void* gates, long long ldg, const float* gm, void* out, int N,
+                              long long S, int C, int dtype, msseg_stream_t stream);
+int msseg_focal_aggregate_bwd(const void* da, const void* c1, const void* c2, const void* gates, long long ldg, const float* gm,
+                              const float* dmv, void* dc1, void* dc2, void* dgates, long long lddg, int gate_width, int N,
+                              long long S, int C, int dtype, msseg_stream_t stream);
+int msseg_focal_mul_fwd(const void* q, long long ldq, const void* h, void* y, long long rows, int C, int dtype,
+                        msseg_stream_t stream);
+int msseg_focal_mul_bwd(const void* dy, const void* q, long long ldq, const void* h, void* dq, long long lddq, void* dh,
+                        long long rows, int C, int dtype, msseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * SegFormer3D pieces (models/backbones/segformer_backbone.py:51-117, models/segmentors/segformer_head_official.py:65-90).
  * interp_trilinear: F.interpolate(mode='trilinear', align_corners=False) between channels-last volumes
  *   x [N, ID, IH, IW, C] and y [N, OD, OH, OW, C] (C % (16 / sizeof(elem)) == 0); bwd = its adjoint in gather form

@@ -38,6 +38,14 @@ SIGNATURES = {
     "msseg_conv3d_k3_fwd_accumulate": ([_vp, _ll, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _i, _vp], _i),
     "msseg_dwconv3d_k3_fwd": ([_vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "msseg_dwconv3d_k3_wgrad": ([_vp, _ll, _vp, _ll, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp], _i),
+    "msseg_dwconv3d_fwd": ([_vp, _ll, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "msseg_dwconv3d_wgrad_workspace_bytes": ([_i, _i, _i, _i, _i, _i, _i], _sz),
+    "msseg_dwconv3d_wgrad": ([_vp, _ll, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp], _i),
+    "msseg_focal_spatial_sum": ([_vp, _ll, _vp, _ll, _vp, _vp, _vp, _f, _i, _i, _ll, _i, _vp, _sz, _i, _vp], _i),
+    "msseg_focal_aggregate_fwd": ([_vp, _vp, _vp, _ll, _vp, _vp, _i, _ll, _i, _i, _vp], _i),
+    "msseg_focal_aggregate_bwd": ([_vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _ll, _i, _i, _vp], _i),
+    "msseg_focal_mul_fwd": ([_vp, _ll, _vp, _vp, _ll, _i, _i, _vp], _i),
+    "msseg_focal_mul_bwd": ([_vp, _vp, _ll, _vp, _vp, _ll, _vp, _ll, _i, _i, _vp], _i),
     "msseg_interp_trilinear_fwd": ([_vp, _ll, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "msseg_interp_trilinear_bwd_workspace_bytes": ([_i, _i, _i, _i, _i, _i, _i, _i], _sz),
     "msseg_interp_trilinear_bwd": ([_vp, _ll, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp], _i),
@@ -938,6 +946,78 @@ def dwconv3d_k3_wgrad(x, dy, dw, dbias, acc_w=False, acc_b=False):
     sc = scratch(x.device)
     _ck(lib().msseg_dwconv3d_k3_wgrad(_p(x), ld(x), _p(dy), ld(dy), _p(dw), _p(dbias), int(acc_w), int(acc_b), N, D, H, W, C,
                                       _p(sc), sc.numel(), dt(x), _stream()), "dwconv3d_k3_wgrad")
+
+
+def dwconv3d(x, w_taps, y, K, flip=False):
+    """depthwise conv, odd K in 3..11, stride 1, pad K // 2, no bias, on channels-last x (a channel slice of a wider buffer is
+    fine); w_taps [K^3, C] (tap-major, dtype of x); flip: the input gradient"""
+    if w_taps.dtype != x.dtype or y.dtype != x.dtype:
+        raise ValueError("dwconv3d: the weight table and the output must have the activation dtype")
+    _need_gpu(x, w_taps, y)
+    N, D, H, W, C = x.shape
+    if tuple(w_taps.shape) != (K ** 3, C) or not w_taps.is_contiguous() or tuple(y.shape) != tuple(x.shape):
+        raise ValueError(f"dwconv3d: weight table {tuple(w_taps.shape)} / output {tuple(y.shape)} do not fit x {tuple(x.shape)}, K {K}")
+    _ck(lib().msseg_dwconv3d_fwd(_p(x), ld(x), _p(w_taps), _p(y), ld(y), N, D, H, W, C, K, int(flip), dt(x), _stream()),
+        "dwconv3d_fwd")
+    return y
+
+
+def dwconv3d_wgrad(x, dy, dw, K, accumulate=False):
+    """dw fp32 [C, 1, K, K, K] (+)= the weight gradient of dwconv3d; deterministic (fixed-order partial rows in the workspace)"""
+    _need_gpu(x, dy, dw)
+    N, D, H, W, C = x.shape
+    if dw.dtype != torch.float32 or dw.numel() != C * K ** 3 or not dw.is_contiguous() or tuple(dy.shape) != tuple(x.shape):
+        raise ValueError("dwconv3d_wgrad: dw must be contiguous fp32 [C, 1, K, K, K] and dy shaped like x")
+    ws = workspace(lib().msseg_dwconv3d_wgrad_workspace_bytes(N, D, H, W, C, K, dt(x)), x.device)
+    _ck(lib().msseg_dwconv3d_wgrad(_p(x), ld(x), _p(dy), ld(dy), _p(dw), int(accumulate), N, D, H, W, C, K, _p(ws), ws.numel(),
+                                   dt(x), _stream()), "dwconv3d_wgrad")
+    return dw
+
+
+def focal_spatial_sum(x, out0, out1=None, g=None, m_in=None, scale=1.0, mode=0):
+    """out0[n, c] = scale * sum over the voxels of x[n, ..., c] (* g[n, ..., 0], a one-channel view); mode 0 also writes
+    out1 = GELU(out0), mode 1 multiplies by gelu'(m_in).  fp32 [N, C] results, fixed-order sums."""
+    _need_gpu(x, out0)
+    N, S, Cc = _nsc(x)
+    sc = scratch(x.device)
+    _ck(lib().msseg_focal_spatial_sum(_p(x), ld(x), _p(g), ld(g) if g is not None else 0, _p(m_in), _p(out0), _p(out1),
+                                      float(scale), int(mode), N, S, Cc, _p(sc), sc.numel(), dt(x), _stream()),
+        "focal_spatial_sum")
+    return out0
+
+
+def focal_aggregate_fwd(c1, c2, gates, gm, out):
+    """out = c1 * g0 + c2 * g1 + gm[n, c] * g2; gates: a [..., >= 3] channel slice of a wider buffer; gm fp32 [N, C]"""
+    _need_gpu(c1, c2, gates, gm, out)
+    N, S, Cc = _nsc(c1)
+    _ck(lib().msseg_focal_aggregate_fwd(_p(c1), _p(c2), _p(gates), ld(gates), _p(gm), _p(out), N, S, Cc, dt(c1), _stream()),
+        "focal_aggregate_fwd")
+    return out
+
+
+def focal_aggregate_bwd(da, c1, c2, gates, gm, dmv, dc1, dc2, dgates):
+    """dc1 = da * g0, dc2 = da * g1 + dmv[n, c], dgates[..., :3] = sum_c da * (c1, c2, gm), dgates[..., 3:] = 0"""
+    _need_gpu(da, c1, c2, gates, gm, dmv, dc1, dc2, dgates)
+    N, S, Cc = _nsc(c1)
+    _ck(lib().msseg_focal_aggregate_bwd(_p(da), _p(c1), _p(c2), _p(gates), ld(gates), _p(gm), _p(dmv), _p(dc1), _p(dc2),
+                                        _p(dgates), ld(dgates), dgates.shape[-1], N, S, Cc, dt(c1), _stream()),
+        "focal_aggregate_bwd")
+
+
+def focal_mul_fwd(q, h, y):
+    """y = q * h; q may be a channel slice of a wider buffer"""
+    _need_gpu(q, h, y)
+    Cc = h.shape[-1]
+    _ck(lib().msseg_focal_mul_fwd(_p(q), ld(q), _p(h), _p(y), h.numel() // Cc, Cc, dt(h), _stream()), "focal_mul_fwd")
+    return y
+
+
+def focal_mul_bwd(dy, q, h, dq, dh):
+    """dq = dy * h (dq may be a channel slice of a wider buffer), dh = dy * q"""
+    _need_gpu(dy, q, h, dq, dh)
+    Cc = h.shape[-1]
+    _ck(lib().msseg_focal_mul_bwd(_p(dy), _p(q), ld(q), _p(h), _p(dq), ld(dq), _p(dh), h.numel() // Cc, Cc, dt(h), _stream()),
+        "focal_mul_bwd")
 
 
 def interp_trilinear(x, y):

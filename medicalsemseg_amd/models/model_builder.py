@@ -18,6 +18,10 @@ for the models on the hot path.
 * ``cfg.model == 'SwinUNETR'`` -- the vendored MONAI variant of ``models/segmentors/swin_unetr_official.py`` (window 7,
   ``feature_size = cfg.hidden_dim``), the literal "Swin-UNETR 48-feat" of BASELINE.json configs[3] (the reference keeps
   the class but wires no ``build_model`` branch to it).
+* ``cfg.model == 'FocalNetUNETR'`` -- the ``FocalNet`` encoder (focal modulation: two large depthwise convolutions per
+  block instead of window attention) inside ``SwinUNETRCustom``, the branch at ``model_builder.py:225-241``.
+  ``cfg.window_size`` gives the focal windows (one odd value in 3..9, or one per stage), ``cfg.patch_size`` is 2 or 4 and
+  ``cfg.depths`` has four stages (the reference's ``out_indices=(0, 1, 2, 3)``).
 Every returned module obeys the engine contract ``model((vol, rel_crop_loc, affine_xyz)) -> logits`` and keeps the
 reference's / MONAI's state-dict key layout.  ``cfg.compute_dtype``: 'bf16' (default) or 'f32'.
 """
@@ -27,7 +31,7 @@ import torch
 
 from .unet import UNET_FEATURES, UNet
 
-OUT_OF_SCOPE = ("GCViTUNETR", "FocalNetUNETR")
+OUT_OF_SCOPE = ("GCViTUNETR",)
 
 
 def _dtype(cfg):
@@ -62,6 +66,32 @@ def build_model(cfg):
         return SwinUNETRCustom(encoder, in_channels=cfg.in_chans, out_channels=cfg.output_dim,
                                img_size=_t3(cfg.vol_size), hidden_size=cfg.hidden_dim, patch_size=_t3(cfg.patch_size),
                                compute_dtype=_dtype(cfg))
+    if name == "FocalNetUNETR":                                 # model_builder.py:225-241
+        from .focalnet import MAX_WINDOW, MIN_WINDOW, FocalNet
+        from .swin_unetr import SwinUNETRCustom
+        for flag in ("learned_cls_vectors", "rel_crop_pos_emb", "abs_pos_emb", "global_token", "rel_pos_bias_affine"):
+            if getattr(cfg, flag, False):
+                raise NotImplementedError(f"--{flag} is not implemented for FocalNetUNETR (the reference's FocalNet takes no such option)")
+        ps = _t3(cfg.patch_size)
+        if len(set(ps)) != 1 or ps[0] not in (2, 4):
+            raise NotImplementedError(f"--patch_size {cfg.patch_size}: FocalNetUNETR is implemented for patch size 2 or 4")
+        if len(cfg.depths) != 4:
+            raise NotImplementedError(f"--depths {list(cfg.depths)}: FocalNetUNETR takes four stages (the reference builds "
+                                      f"FocalNet with out_indices=(0, 1, 2, 3) and fails otherwise)")
+        fw = list(cfg.window_size) if isinstance(cfg.window_size, (tuple, list)) else [cfg.window_size]
+        if len(fw) == 1:
+            fw = fw * len(cfg.depths)
+        if len(fw) != len(cfg.depths):
+            raise NotImplementedError(f"--window_size {fw}: one focal window, or one per stage ({len(cfg.depths)})")
+        for w in fw:
+            if int(w) != w or w % 2 == 0 or not MIN_WINDOW <= w <= MAX_WINDOW:
+                raise NotImplementedError(f"--window_size {w}: focal windows are odd and in {MIN_WINDOW}..{MAX_WINDOW} (depthwise "
+                                          f"kernels up to 11; an even window fails in the reference itself)")
+        encoder = FocalNet(pretrain_img_size=_t3(cfg.vol_size), patch_size=ps, in_chans=cfg.in_chans, embed_dim=cfg.hidden_dim,
+                           depths=tuple(cfg.depths), focal_windows=tuple(int(w) for w in fw),
+                           mlp_ratio=getattr(cfg, "mlp_ratio", 4.0), compute_dtype=_dtype(cfg))
+        return SwinUNETRCustom(encoder, in_channels=cfg.in_chans, out_channels=cfg.output_dim, img_size=_t3(cfg.vol_size),
+                               hidden_size=cfg.hidden_dim, patch_size=ps, compute_dtype=_dtype(cfg))
     if name == "SwinSegFormer":                                 # model_builder.py:173-189
         from .segformer3d import SegFormerHead
         from .swin_unetr import SwinTransformerNNFormer
@@ -89,5 +119,5 @@ def build_model(cfg):
                          num_heads=tuple(cfg.num_heads), feature_size=cfg.hidden_dim, compute_dtype=_dtype(cfg))
     if name in OUT_OF_SCOPE:
         raise NotImplementedError(f"model '{name}' is a research variant outside this build's hot-path scope "
-                                  f"(SURVEY.md section 2); available: {sorted(UNET_FEATURES)} + ['nnFormerUNETR', 'SwinDepth', 'SwInception', 'SwinSegFormer', 'SegFormer3D', 'SwinUNETR']")
+                                  f"(SURVEY.md section 2); available: {sorted(UNET_FEATURES)} + ['nnFormerUNETR', 'SwinDepth', 'SwInception', 'SwinSegFormer', 'SegFormer3D', 'SwinUNETR', 'FocalNetUNETR']")
     raise ValueError(f"unknown cfg.model '{name}'")

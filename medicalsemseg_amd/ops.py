@@ -602,6 +602,130 @@ class DwConv3Fn(torch.autograd.Function):
         return dx, None, None
 
 
+def _dw_taps(weight, dtype):
+    """depthwise weight [C, 1, K, K, K] -> tap-major table [K^3, C] in the compute dtype"""
+    C = weight.shape[0]
+    return weight.detach().reshape(C, -1).t().to(dtype).contiguous()
+
+
+def _cs(x):
+    """x as the kernels take it: dense, or a 16-byte aligned channel slice of a dense channels-last buffer (no copy)"""
+    epc = 16 // x.element_size()
+    if x.stride(-1) == 1 and x.data_ptr() % 16 == 0:
+        try:
+            if hip.ld(x) % epc == 0:
+                return x
+        except ValueError:
+            pass
+    return x.contiguous()
+
+
+class DwConvFn(torch.autograd.Function):
+    """depthwise Conv3d with an odd kernel K in 3..11, stride 1, padding K // 2, no bias (groups = channels) on a token volume
+    [B, S, H, W, C]; weight [C, 1, K, K, K]: the focal convolutions of /root/reference/models/backbones/focalnet_3d.py:73-81.
+    x may be a channel slice of a wider buffer (read in place)."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        x = _cs(x)
+        K = weight.shape[-1]
+        taps = _dw_taps(weight, x.dtype)
+        ctx.save_for_backward(x, taps)
+        ctx.weight, ctx.K = weight, K
+        return hip.dwconv3d(x, taps, torch.empty(x.shape, dtype=x.dtype, device=x.device), K)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, taps = ctx.saved_tensors
+        dy = _c(dy)
+        w, K = ctx.weight, ctx.K
+        if w.requires_grad:
+            gw, aw = _gbuf(w)
+            hip.dwconv3d_wgrad(x, dy, gw, K, aw)
+        dx = hip.dwconv3d(dy, taps, torch.empty_like(dy), K, flip=True) if ctx.needs_input_grad[0] else None
+        return dx, None
+
+
+def dwconv(x, weight):
+    return DwConvFn.apply(x, weight)
+
+
+class FocalModulationFn(torch.autograd.Function):
+    """The core of a focal modulation block (/root/reference/models/backbones/focalnet_3d.py:89-100) as ONE autograd node.
+    f [B, S, H, W, >= 2C + 3] is the output of the block's Linear `f`: q | ctx | gates are channel ranges of it and are read
+    in place; the backward writes their three gradients into the ranges of one buffer (autograd would otherwise build three
+    zero-padded copies and add them).
+
+        c1 = GELU(dwconv(ctx, w0));  c2 = GELU(dwconv(c1, w1))
+        ctx_all = c1 * g0 + c2 * g1 + GELU(mean_voxels(c2)) * g2
+        out = q * h(ctx_all)                                   (h: a 1x1x1 conv = Linear)"""
+
+    @staticmethod
+    def forward(ctx, f, w0, w1, hw, hb):
+        f = _c(f)
+        C, T = hw.shape[0], f.dtype
+        B = f.shape[0]
+        if f.shape[-1] < 2 * C + 3:
+            raise ValueError(f"focal modulation: f has {f.shape[-1]} channels, needs 2 * {C} + 3")
+        q, cx, gates = f[..., :C], f[..., C:2 * C], f[..., 2 * C:]
+        S = f.numel() // (B * f.shape[-1])
+        t0, t1 = _dw_taps(w0, T), _dw_taps(w1, T)
+        new = lambda: torch.empty(f.shape[:-1] + (C,), dtype=T, device=f.device)
+        c1pre = hip.dwconv3d(cx, t0, new(), w0.shape[-1])
+        c1 = hip.gelu_fwd(c1pre, new())
+        c2pre = hip.dwconv3d(c1, t1, new(), w1.shape[-1])
+        c2 = hip.gelu_fwd(c2pre, new())
+        m = torch.empty(B, C, dtype=torch.float32, device=f.device)
+        gm = torch.empty_like(m)
+        hip.focal_spatial_sum(c2, m, gm, scale=1.0 / S, mode=0)
+        ca = hip.focal_aggregate_fwd(c1, c2, gates, gm, new())
+        wp = _packed(hw, T, "f", lambda: hip.pack_conv_k1(hw.detach().reshape(C, C), T))
+        hm = new()
+        hip.conv3d_k1(ca, wp, hb, hm, C, C)
+        y = hip.focal_mul_fwd(q, hm, new())
+        ctx.save_for_backward(f, c1pre, c1, c2pre, c2, m, gm, ca, hm, t0, t1)
+        ctx.params = (w0, w1, hw, hb)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        f, c1pre, c1, c2pre, c2, m, gm, ca, hm, t0, t1 = ctx.saved_tensors
+        w0, w1, hw, hb = ctx.params
+        dy = _c(dy)
+        C, T = hw.shape[0], f.dtype
+        B = f.shape[0]
+        S = f.numel() // (B * f.shape[-1])
+        q, cx, gates = f[..., :C], f[..., C:2 * C], f[..., 2 * C:]
+        df = torch.empty_like(f)
+        dhm = torch.empty_like(hm)
+        hip.focal_mul_bwd(dy, q, hm, df[..., :C], dhm)
+        wpd = _packed(hw, T, "d", lambda: hip.pack_conv_k1(hw.detach().reshape(C, C), T, dgrad=True))
+        da = torch.empty_like(ca)
+        hip.conv3d_k1(dhm, wpd, None, da, C, C)
+        _linear_param_grads(ca, dhm, hw, hb, C, C, hw.requires_grad, hb is not None and hb.requires_grad)
+        # the mean's gradient: sum_v da * g2 per (sample, channel), times gelu'(mean) / S
+        dmv = torch.empty_like(m)
+        hip.focal_spatial_sum(da, dmv, None, g=gates[..., 2:3], m_in=m, scale=1.0 / S, mode=1)
+        dc1, dc2 = torch.empty_like(c1), torch.empty_like(c2)
+        hip.focal_aggregate_bwd(da, c1, c2, gates, gm, dmv, dc1, dc2, df[..., 2 * C:])
+        dc2pre = hip.gelu_bwd(c2pre, dc2, torch.empty_like(dc2))
+        if w1.requires_grad:
+            g, acc = _gbuf(w1)
+            hip.dwconv3d_wgrad(c1, dc2pre, g, w1.shape[-1], acc)
+        back = hip.dwconv3d(dc2pre, t1, torch.empty_like(dc2pre), w1.shape[-1], flip=True)
+        dc1 = hip.axpy_rows(dc1, back, None, torch.empty_like(dc1))
+        dc1pre = hip.gelu_bwd(c1pre, dc1, torch.empty_like(dc1))
+        if w0.requires_grad:
+            g, acc = _gbuf(w0)
+            hip.dwconv3d_wgrad(cx, dc1pre, g, w0.shape[-1], acc)
+        hip.dwconv3d(dc1pre, t0, df[..., C:2 * C], w0.shape[-1], flip=True)
+        return df, None, None, None, None
+
+
+def focal_modulation(f, w0, w1, hw, hb):
+    return FocalModulationFn.apply(f, w0, w1, hw, hb)
+
+
 class AvgPool3Fn(torch.autograd.Function):
     """nn.AvgPool3d(kernel_size=3, stride=1, padding=1) (count_include_pad: every window divides by 27) on a token volume
     (/root/reference/models/backbones/swinception.py:113-116): the depthwise k3 kernel with unit taps and the fp32 sum scaled
