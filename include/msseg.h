@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MSSEG_ABI_VERSION 1
+#define MSSEG_ABI_VERSION 2
 
 #define MSSEG_OK 0
 #define MSSEG_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -199,20 +199,15 @@ int msseg_deconv_k4s4_fwd(const void* x, long long ldx, const void* wp, const fl
 /* input gradient of the above: dy [N,4D,4H,4W,Cout] -> dx [N,D,H,W,Cin]. */
 int msseg_deconv_k4s4_bwd_data(const void* dy, long long lddy, const void* wp, void* dx, long long lddx,
                                int N, int D, int H, int W, int Cin, int Cout, int dtype, msseg_stream_t stream);
-/* The two flat input-gradient kernels with the InstanceNorm-backward sums of the RECEIVING layer fused into the epilogue
+/* The flat 1x1x1 input-gradient kernel with the InstanceNorm-backward sums of the RECEIVING layer fused into the epilogue
  * (arguments as msseg_conv3d_k3_dgrad_inbwd): the gradient that reaches the second conv+norm unit of a UNet level comes
- * from the 1x1x1 output conv (level 0) or from a transposed conv (other decoder levels / the bottleneck).
- * k1: dy [N*S, Cin] -> da [N*S, Cout], S voxels per sample.  deconv: dy [N,2D,2H,2W,Cout] -> dx [N,D,H,W,Cin]. */
+ * from the 1x1x1 output conv (level 0) or from a transposed conv (other decoder levels / the bottleneck:
+ * msseg_deconv_k2s2_bwd_fused below).  dy [N*S, Cin] -> da [N*S, Cout], S voxels per sample. */
 int msseg_conv3d_k1_dgrad_inbwd(const void* dy, long long lddy, const void* wp, void* da, long long ldda, int N,
                                 long long S, int Cin, int Cout, const void* yraw, long long ldyraw, const void* act,
                                 long long ldact, const float* fwd_stats, float slope, float eps, float* red,
                                 float* dgamma, float* dbeta, int accumulate, void* scratch, size_t scratch_bytes,
                                 int dtype, msseg_stream_t stream);
-int msseg_deconv_k2s2_bwd_data_inbwd(const void* dy, long long lddy, const void* wp, void* dx, long long lddx, int N,
-                                     int D, int H, int W, int Cin, int Cout, const void* yraw, long long ldyraw,
-                                     const void* act, long long ldact, const float* fwd_stats, float slope, float eps,
-                                     float* red, float* dgamma, float* dbeta, int accumulate, void* scratch,
-                                     size_t scratch_bytes, int dtype, msseg_stream_t stream);
 /* Input gradient of ConvTranspose3d k2 s2 with everything the pass over dy can produce: dx, optionally (yraw != NULL) the
  * InstanceNorm-backward sums red[N][Cin][2] (+ dgamma / dbeta) of the layer that receives dx, and optionally
  * (dbias != NULL) the bias gradient dbias[Cout] (+)= sum over all fine voxels of dy.  bf16 layers with Cin in {32, 64},
@@ -288,16 +283,12 @@ int msseg_conv3d_k3_small_stage_groups(int N, int D, int H, int W, int Cin, int 
 size_t msseg_conv3d_k3_small_workspace_bytes(int N, int D, int H, int W, int Cin, int Cout);
 int msseg_conv3d_k3_small_partials(const void* x, long long ldx, const void* wp, float* part, size_t part_bytes, int N,
                                    int D, int H, int W, int Cin, int Cout, msseg_stream_t stream);
+/* residual (nullable, voxel stride ldr) is added before the LeakyReLU: act = lrelu(instance_norm(y) * gamma + beta +
+ * residual) -- the second convolution of MONAI's UnetResBlock (models/segmentors/swin_unetr.py:73-128 of the reference) */
 int msseg_conv3d_k3_small_fwd_finish(const float* part, int nstages, const float* bias, const float* gamma,
                                      const float* beta, float eps, float slope, void* yraw, long long ldy, void* act,
-                                     long long lda, void* pooled, long long ldp, float* stats, int N, int D, int H, int W,
-                                     int Cout, msseg_stream_t stream);
-/* ... with an optional residual added before the LeakyReLU: act = lrelu(instance_norm(y) * gamma + beta + residual) -- the
- * second convolution of MONAI's UnetResBlock (models/segmentors/swin_unetr.py:73-128 of the reference) */
-int msseg_conv3d_k3_small_fwd_finish_res(const float* part, int nstages, const float* bias, const float* gamma,
-                                         const float* beta, float eps, float slope, void* yraw, long long ldy, void* act,
-                                         long long lda, const void* residual, long long ldr, void* pooled, long long ldp,
-                                         float* stats, int N, int D, int H, int W, int Cout, msseg_stream_t stream);
+                                     long long lda, const void* residual, long long ldr, void* pooled, long long ldp,
+                                     float* stats, int N, int D, int H, int W, int Cout, msseg_stream_t stream);
 int msseg_conv3d_k3_small_bwd_finish(const float* part, int nstages, void* dx, long long lddx, const void* unit_yraw,
                                      long long lduy, const float* unit_stats, const float* unit_gamma,
                                      const float* unit_beta, float eps, float slope, float* dgamma, float* dbeta,
@@ -459,52 +450,38 @@ int msseg_axpy_rows(const void* a, const void* b, const float* scale, void* y, i
  * ------------------------------------------------------------------------------------------- */
 /* Shifted-window attention between the qkv and proj Linears (swin_nnformer.py:128-196 inside :235-289):
  * qkv [B,S,H,W,3C] (channel = which*C + head*hd + e) -> out [B,S,H,W,C].  Window partition, cyclic shift, zero
- * padding to a window multiple (padded tokens carry qkv_bias), the relative-position bias table
- * [(2ws-1)^3][heads] and the -100 region mask are all applied through addressing; lse [B*nW][heads][ws^3] is
- * saved for the backward.  head_dim in {8,16,32}. */
+ * padding to a window multiple (padded tokens carry qkv_bias), the relative-position bias table and the -100 region
+ * mask are all applied through addressing; lse [B*nW][heads][ws^3] is saved for the backward.  head_dim in {8,16,32};
+ * bf16 with head_dim 16 / 32, C % 8 == 0, ws^3 <= 352 and at most 4095 table rows runs on the MFMA kernels
+ * (attention_mfma.hip; the backward only where its LDS image fits), every other case on the fp32-math vector kernels.
+ *   bias_ws       the window the bias table was built for: the table has M3 = (2*bias_ws-1)^3 rows of `heads` floats and
+ *                 token i of a window takes the relative position of index position decode_{bias_ws}(i).  Default
+ *                 bias_ws == ws (0 means ws).  bias_ws > ws is MONAI SwinUNETR's `index[:n, :n]` on a stage whose
+ *                 window is clamped to a smaller grid (swin_unetr_official.py:375-385, 477-480).
+ *   table_stride  default 0: one table [M3][heads] shared by every sample.  Otherwise one table PER SAMPLE: sample b's
+ *                 windows read table + b * table_stride and the backward adds sample b's table gradient to
+ *                 dtable + b * table_stride (table_stride >= M3 * heads, in floats).
+ *   backward      dqkv is fully written for every token; dtable (nullable = not wanted) is ACCUMULATED (caller
+ *                 zero-fills when needed).
+ *   workspace     default NULL: the table gradient is summed with LDS float atomics.  With a workspace of at least
+ *                 msseg_window_attention_bwd_workspace_bytes(same shape arguments) bytes and a non-NULL dtable, the
+ *                 bias-table gradient (swin_nnformer.py:147-155 in reverse) is computed without atomics: dS tiles in
+ *                 bf16 -> sum over windows (of one sample at a time with per-sample tables, so the size grows with B)
+ *                 -> gather per table entry, deterministic.  The query returns 0 when this shape/dtype has no use for
+ *                 a workspace (only the bf16 MFMA backward uses one); a workspace is then ignored. */
 int msseg_window_attention_fwd(const void* qkv, const float* qkv_bias, const float* table, void* out, float* lse, int B,
-                               int S, int H, int W, int C, int heads, int ws, int shift, int dtype,
-                               msseg_stream_t stream);
-/* dqkv fully written for every token; dtable (nullable) ACCUMULATED (caller zero-fills when needed). */
+                               int S, int H, int W, int C, int heads, int ws, int shift, int bias_ws, long long table_stride,
+                               int dtype, msseg_stream_t stream);
 int msseg_window_attention_bwd(const void* qkv, const float* qkv_bias, const float* table, const void* out,
                                const float* lse, const void* dout, void* dqkv, float* dtable, int B, int S, int H, int W,
-                               int C, int heads, int ws, int shift, int dtype, msseg_stream_t stream);
-/* Same with a caller workspace (bytes from msseg_window_attention_bwd_workspace_bytes; 0 = this shape/dtype has no use
- * for one).  With it the bias-table gradient (swin_nnformer.py:147-155 in reverse) is computed without atomics: dS tiles
- * in bf16 -> sum over windows -> gather per table entry, deterministic.  workspace == NULL behaves as the call above. */
-size_t msseg_window_attention_bwd_workspace_bytes(int B, int S, int H, int W, int C, int heads, int ws, int shift, int dtype);
-/* Forms with a separate BIAS window: the table has (2*bias_ws-1)^3 rows and token i of a window takes the relative
- * position of index position decode_{bias_ws}(i) -- MONAI SwinUNETR builds table and index for window 7 and slices the
- * index [:n, :n] when the window is clamped to a smaller grid (swin_unetr_official.py:375-385, 477-480).  bias_ws == ws is
- * the plain case (bf16 then runs on the MFMA kernels); bias_ws > ws runs on the exact-fp32-math kernels. */
-int msseg_window_attention_fwd2(const void* qkv, const float* qkv_bias, const float* table, void* out, float* lse, int B,
-                                int S, int H, int W, int C, int heads, int ws, int shift, int bias_ws, int dtype,
-                                msseg_stream_t stream);
-int msseg_window_attention_bwd2(const void* qkv, const float* qkv_bias, const float* table, const void* out,
-                                const float* lse, const void* dout, void* dqkv, float* dtable, int B, int S, int H, int W,
-                                int C, int heads, int ws, int shift, int bias_ws, int dtype, void* workspace,
-                                size_t workspace_bytes, msseg_stream_t stream);
-int msseg_window_attention_bwd_ws(const void* qkv, const float* qkv_bias, const float* table, const void* out,
-                                  const float* lse, const void* dout, void* dqkv, float* dtable, int B, int S, int H, int W,
-                                  int C, int heads, int ws, int shift, int dtype, void* workspace, size_t workspace_bytes,
-                                  msseg_stream_t stream);
-/* Forms with one bias table PER SAMPLE: sample b's windows read table + b * table_stride and the backward ACCUMULATES the
- * table gradient of sample b into dtable + b * table_stride (caller zero-fills; table_stride >= (2*bias_ws-1)^3 * heads, or
- * 0 = the calls above).  The workspace path then sums dS over the windows of one sample at a time, so its workspace grows
- * with B: size it with msseg_window_attention_bwd3_workspace_bytes. */
-int msseg_window_attention_fwd3(const void* qkv, const float* qkv_bias, const float* table, void* out, float* lse, int B,
-                                int S, int H, int W, int C, int heads, int ws, int shift, int bias_ws, long long table_stride,
-                                int dtype, msseg_stream_t stream);
-int msseg_window_attention_bwd3(const void* qkv, const float* qkv_bias, const float* table, const void* out,
-                                const float* lse, const void* dout, void* dqkv, float* dtable, int B, int S, int H, int W,
-                                int C, int heads, int ws, int shift, int bias_ws, long long table_stride, int dtype,
-                                void* workspace, size_t workspace_bytes, msseg_stream_t stream);
-size_t msseg_window_attention_bwd3_workspace_bytes(int B, int S, int H, int W, int C, int heads, int ws, int shift,
-                                                   int bias_ws, long long table_stride, int dtype);
+                               int C, int heads, int ws, int shift, int bias_ws, long long table_stride, int dtype,
+                               void* workspace, size_t workspace_bytes, msseg_stream_t stream);
+size_t msseg_window_attention_bwd_workspace_bytes(int B, int S, int H, int W, int C, int heads, int ws, int shift,
+                                                  int bias_ws, long long table_stride, int dtype);
 /* Spacing-conditioned relative position bias (swin_nnformer.py:89-97, :157-166, `--rel_pos_bias_affine`): the per-sample
  * tables T [B][M3][heads] fp32 = table [M3][heads] + lin_b[0] + sum_k lin_w[k] * aff[b][k] * emb [M3][heads][3], for the
- * *3 calls above with table_stride = M3 * heads.  aff [B][3] fp32 holds one row per sample.  Every input is read on the
- * device (no host synchronisation). */
+ * attention calls above with table_stride = M3 * heads.  aff [B][3] fp32 holds one row per sample.  Every input is read on
+ * the device (no host synchronisation). */
 int msseg_rel_bias_affine_fold(const float* table, const float* emb, const float* lin_w, const float* lin_b,
                                const float* aff, float* T, int B, int M3, int heads, msseg_stream_t stream);
 /* From the per-sample table gradient dT [B][M3][heads]: dtable [M3][heads], demb [M3][heads][3], dlin_w [3], dlin_b [1]
@@ -600,22 +577,15 @@ int msseg_sumsq(const float* x, long long n, float* out, float* partials, int n_
 /* ---------------------------------------------------------------------------------------------
  * Sliding-window inference (engine/utils.py:120-151): gather windows, weighted blend, normalise.
  * ------------------------------------------------------------------------------------------- */
-/* out[c][vol] += imp[roi] * win[c][roi] placed at start (z,y,x); cnt[vol] += imp (one channel).
- * win: channels-last [roi][ld] when ld > 0, NCDHW when ld == 0. */
-int msseg_sw_blend(const void* win, long long ld, int dtype, const float* imp, float* out, float* cnt,
-                   int C, int VD, int VH, int VW, int RD, int RH, int RW, int z0, int y0, int x0,
-                   msseg_stream_t stream);
-/* win[c][roi] (NCDHW, dtype) = vol[c][window at (z0,y0,x0)] with `cval` outside the volume. */
-int msseg_sw_gather(const float* vol, void* win, int dtype, int C, int VD, int VH, int VW, int RD, int RH, int RW,
-                    int z0, int y0, int x0, float cval, msseg_stream_t stream);
 int msseg_sw_normalize(float* out, const float* cnt, int C, long long V, msseg_stream_t stream);
-/* Batched forms (one launch per window batch; the reference's loop body engine/utils.py:120-148 for `sw_batch_size`
- * windows at once).  table: device int32 [nwin][4] = (sample b, z0, y0, x0); b < 0 = unused slot.
+/* One launch per window batch (the reference's loop body engine/utils.py:120-148 for `sw_batch_size` windows at
+ * once).  imp: fp32 [roi] importance map; cnt has one channel.
+ * table: device int32 [nwin][4] = (sample b, z0, y0, x0); b < 0 = unused slot.
  * gather: win[j] = window j of vol[b] (fp32 [B][C][VD][VH][VW], sample stride vol_bstride elements), `cval` outside;
  *         win layout NCDHW [nwin][C][roi] when ldw == 0, channels-last [nwin][roi][ldw] otherwise.
  * blend : out[b][c][vol] += imp * win[j][c], cnt[b][vol] += imp for every window of the table, each output voxel
- *         accumulated in table order with the reference's roundings (bit-identical to nwin sequential msseg_sw_blend
- *         calls); windows of one batch may overlap.  nwin <= 256, C <= 16. */
+ *         accumulated in table order with the reference's roundings (bit-identical to blending the nwin windows one
+ *         after the other); windows of one batch may overlap.  nwin <= 256, C <= 16. */
 int msseg_sw_gather_batch(const float* vol, long long vol_bstride, void* win, long long ldw, int dtype, const int* table,
                           int nwin, int C, int VD, int VH, int VW, int RD, int RH, int RW, float cval,
                           msseg_stream_t stream);

@@ -494,7 +494,7 @@ inline int grid_for(long long total, int per_thread = 4) {
     return (int)b;
 }
 
-int fill_attn(AttnParams& p, int B, int S, int H, int W, int C, int heads, int ws, int shift, int bias_ws = 0) {
+int fill_attn(AttnParams& p, int B, int S, int H, int W, int C, int heads, int ws, int shift, int bias_ws) {
     if (B < 1 || S < 1 || H < 1 || W < 1 || heads < 1 || C % heads || ws < 1 || shift < 0 || shift >= ws)
         MSSEG_FAIL(MSSEG_EINVAL, "window_attention: bad shape");
     if (bias_ws == 0) bias_ws = ws;
@@ -539,19 +539,6 @@ static int attn_set_lds(const void* kern, size_t smem) {
     return MSSEG_OK;
 }
 
-int msseg_window_attention_fwd(const void* qkv, const float* qkv_bias, const float* table, void* out, float* lse, int B,
-                               int S, int H, int W, int C, int heads, int ws, int shift, int dtype,
-                               msseg_stream_t stream) {
-    return msseg_window_attention_fwd2(qkv, qkv_bias, table, out, lse, B, S, H, W, C, heads, ws, shift, ws, dtype, stream);
-}
-
-int msseg_window_attention_fwd2(const void* qkv, const float* qkv_bias, const float* table, void* out, float* lse, int B,
-                                int S, int H, int W, int C, int heads, int ws, int shift, int bias_ws, int dtype,
-                                msseg_stream_t stream) {
-    return msseg_window_attention_fwd3(qkv, qkv_bias, table, out, lse, B, S, H, W, C, heads, ws, shift, bias_ws, 0, dtype,
-                                       stream);
-}
-
 static int check_tab_stride(const AttnParams& p, long long table_stride) {
     if (table_stride != 0 && table_stride < (long long)p.M3 * p.heads)
         MSSEG_FAIL(MSSEG_EINVAL, "window_attention: table stride %lld smaller than one table (%d x %d)", table_stride, p.M3,
@@ -559,9 +546,9 @@ static int check_tab_stride(const AttnParams& p, long long table_stride) {
     return MSSEG_OK;
 }
 
-int msseg_window_attention_fwd3(const void* qkv, const float* qkv_bias, const float* table, void* out, float* lse, int B,
-                                int S, int H, int W, int C, int heads, int ws, int shift, int bias_ws, long long table_stride,
-                                int dtype, msseg_stream_t stream) {
+int msseg_window_attention_fwd(const void* qkv, const float* qkv_bias, const float* table, void* out, float* lse, int B,
+                               int S, int H, int W, int C, int heads, int ws, int shift, int bias_ws, long long table_stride,
+                               int dtype, msseg_stream_t stream) {
     if (!qkv || !table || !out || !lse) MSSEG_FAIL(MSSEG_EINVAL, "window_attention_fwd: null pointer");
     AttnParams p{};
     if (int rc = fill_attn(p, B, S, H, W, C, heads, ws, shift, bias_ws)) return rc;
@@ -591,15 +578,8 @@ static bool attn_bwd_on_mfma(const AttnParams& p, int C, int dtype) {
            !getenv("MSSEG_ATTN_NO_MFMA");
 }
 
-size_t msseg_window_attention_bwd_workspace_bytes(int B, int S, int H, int W, int C, int heads, int ws, int shift, int dtype) {
-    AttnParams p{};
-    if (fill_attn(p, B, S, H, W, C, heads, ws, shift) != MSSEG_OK) return 0;
-    if (!attn_bwd_on_mfma(p, C, dtype) || getenv("MSSEG_ATTN_BWD_NO_WS")) return 0;
-    return msseg_window_attention_bwd_mfma_ws_bytes(p);
-}
-
-size_t msseg_window_attention_bwd3_workspace_bytes(int B, int S, int H, int W, int C, int heads, int ws, int shift,
-                                                   int bias_ws, long long table_stride, int dtype) {
+size_t msseg_window_attention_bwd_workspace_bytes(int B, int S, int H, int W, int C, int heads, int ws, int shift,
+                                                  int bias_ws, long long table_stride, int dtype) {
     AttnParams p{};
     if (fill_attn(p, B, S, H, W, C, heads, ws, shift, bias_ws) != MSSEG_OK) return 0;
     p.tab_stride = table_stride;
@@ -607,26 +587,10 @@ size_t msseg_window_attention_bwd3_workspace_bytes(int B, int S, int H, int W, i
     return msseg_window_attention_bwd_mfma_ws_bytes(p);
 }
 
-int msseg_window_attention_bwd_ws(const void* qkv, const float* qkv_bias, const float* table, const void* out,
-                                  const float* lse, const void* dout, void* dqkv, float* dtable, int B, int S, int H, int W,
-                                  int C, int heads, int ws, int shift, int dtype, void* workspace, size_t workspace_bytes,
-                                  msseg_stream_t stream) {
-    return msseg_window_attention_bwd2(qkv, qkv_bias, table, out, lse, dout, dqkv, dtable, B, S, H, W, C, heads, ws, shift, ws,
-                                       dtype, workspace, workspace_bytes, stream);
-}
-
-int msseg_window_attention_bwd2(const void* qkv, const float* qkv_bias, const float* table, const void* out,
-                                const float* lse, const void* dout, void* dqkv, float* dtable, int B, int S, int H, int W,
-                                int C, int heads, int ws, int shift, int bias_ws, int dtype, void* workspace,
-                                size_t workspace_bytes, msseg_stream_t stream) {
-    return msseg_window_attention_bwd3(qkv, qkv_bias, table, out, lse, dout, dqkv, dtable, B, S, H, W, C, heads, ws, shift,
-                                       bias_ws, 0, dtype, workspace, workspace_bytes, stream);
-}
-
-int msseg_window_attention_bwd3(const void* qkv, const float* qkv_bias, const float* table, const void* out,
-                                const float* lse, const void* dout, void* dqkv, float* dtable, int B, int S, int H, int W,
-                                int C, int heads, int ws, int shift, int bias_ws, long long table_stride, int dtype,
-                                void* workspace, size_t workspace_bytes, msseg_stream_t stream) {
+int msseg_window_attention_bwd(const void* qkv, const float* qkv_bias, const float* table, const void* out,
+                               const float* lse, const void* dout, void* dqkv, float* dtable, int B, int S, int H, int W,
+                               int C, int heads, int ws, int shift, int bias_ws, long long table_stride, int dtype,
+                               void* workspace, size_t workspace_bytes, msseg_stream_t stream) {
     if (!qkv || !table || !out || !lse || !dout || !dqkv) MSSEG_FAIL(MSSEG_EINVAL, "window_attention_bwd: null pointer");
     AttnParams p{};
     if (int rc = fill_attn(p, B, S, H, W, C, heads, ws, shift, bias_ws)) return rc;
@@ -654,13 +618,6 @@ int msseg_window_attention_bwd3(const void* qkv, const float* qkv_bias, const fl
     else MSSEG_FAIL(MSSEG_EINVAL, "window_attention_bwd: bad dtype");
     MSSEG_CHECK_LAUNCH("window_attention_bwd");
     return MSSEG_OK;
-}
-
-int msseg_window_attention_bwd(const void* qkv, const float* qkv_bias, const float* table, const void* out,
-                               const float* lse, const void* dout, void* dqkv, float* dtable, int B, int S, int H, int W,
-                               int C, int heads, int ws, int shift, int dtype, msseg_stream_t stream) {
-    return msseg_window_attention_bwd_ws(qkv, qkv_bias, table, out, lse, dout, dqkv, dtable, B, S, H, W, C, heads, ws, shift,
-                                         dtype, nullptr, 0, stream);
 }
 
 int msseg_layernorm_fwd(const void* x, long long ldx, const float* gamma, const float* beta, void* y, long long ldy,

@@ -513,20 +513,13 @@ int msseg_conv3d_k3_small_partials(const void* x, long long ldx, const void* wp,
     return MSSEG_OK;
 }
 
-/* y = sum of the stages + bias (bf16, voxel stride ldy); stats[N][Cout][2] of y; act = lrelu(instance_norm(y) * gamma + beta)
- * (voxel stride lda: may be a channel slice of a concat buffer); pooled (optional) = max_pool3d(act, 2) */
+/* y = sum of the stages + bias (bf16, voxel stride ldy); stats[N][Cout][2] of y; act = lrelu(instance_norm(y) * gamma + beta
+ * + residual) (voxel stride lda: may be a channel slice of a concat buffer; residual optional, voxel stride ldr); pooled
+ * (optional) = max_pool3d(act, 2) */
 int msseg_conv3d_k3_small_fwd_finish(const float* part, int nstages, const float* bias, const float* gamma,
                                      const float* beta, float eps, float slope, void* yraw, long long ldy, void* act,
-                                     long long lda, void* pooled, long long ldp, float* stats, int N, int D, int H, int W,
-                                     int Cout, msseg_stream_t stream) {
-    return msseg_conv3d_k3_small_fwd_finish_res(part, nstages, bias, gamma, beta, eps, slope, yraw, ldy, act, lda, nullptr, 0,
-                                                pooled, ldp, stats, N, D, H, W, Cout, stream);
-}
-
-int msseg_conv3d_k3_small_fwd_finish_res(const float* part, int nstages, const float* bias, const float* gamma,
-                                         const float* beta, float eps, float slope, void* yraw, long long ldy, void* act,
-                                         long long lda, const void* residual, long long ldr, void* pooled, long long ldp,
-                                         float* stats, int N, int D, int H, int W, int Cout, msseg_stream_t stream) {
+                                     long long lda, const void* residual, long long ldr, void* pooled, long long ldp,
+                                     float* stats, int N, int D, int H, int W, int Cout, msseg_stream_t stream) {
     if (residual && (ldr % 4 || ((uintptr_t)residual & 7)))
         MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_small_fwd_finish: the residual must be 8-byte aligned with a stride that is a multiple of 4");
     if (!part || !yraw || !act || !stats || nstages < 1 || nstages > NKG_MAX)

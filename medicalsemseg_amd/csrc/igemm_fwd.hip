@@ -1094,15 +1094,4 @@ int msseg_deconv_k2s2_bwd_fused(const void* dy, long long lddy, const void* wp, 
     return MSSEG_OK;
 }
 
-int msseg_deconv_k2s2_bwd_data_inbwd(const void* dy, long long lddy, const void* wp, void* dx, long long lddx, int N,
-                                     int D, int H, int W, int Cin, int Cout, const void* yraw, long long ldyraw,
-                                     const void* act, long long ldact, const float* fwd_stats, float slope, float eps,
-                                     float* red, float* dgamma, float* dbeta, int accumulate, void* scratch,
-                                     size_t scratch_bytes, int dtype, msseg_stream_t stream) {
-    if (!yraw || !act || !fwd_stats || !red) MSSEG_FAIL(MSSEG_EINVAL, "deconv_k2s2_bwd_data_inbwd: null pointer");
-    return msseg_deconv_k2s2_bwd_fused(dy, lddy, wp, dx, lddx, N, D, H, W, Cin, Cout, yraw, ldyraw, act, ldact, fwd_stats,
-                                       slope, eps, red, dgamma, dbeta, accumulate, nullptr, 0, scratch, scratch_bytes, dtype,
-                                       stream);
-}
-
 }  // extern "C"

@@ -339,48 +339,11 @@ __global__ __launch_bounds__(256) void dice_ce_bwd_kernel(const T* __restrict__ 
 }
 
 // ---------------- sliding window ----------------
-template <typename T>
-__global__ void sw_blend_kernel(const T* __restrict__ win, long long ld, const float* __restrict__ imp,
-                                float* __restrict__ out, float* __restrict__ cnt, int C, int VD, int VH, int VW,
-                                int RD, int RH, int RW, int z0, int y0, int x0) {
-#pragma clang fp contract(off)  // mul then add with two roundings, bit-identical to torch's `out[idx] += imp * seg`
-    const long long R = (long long)RD * RH * RW, V = (long long)VD * VH * VW;
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < R; i += (long long)gridDim.x * 256) {
-        const int rx = (int)(i % RW), ry = (int)((i / RW) % RH), rz = (int)(i / ((long long)RW * RH));
-        const long long v = ((long long)(z0 + rz) * VH + (y0 + ry)) * VW + (x0 + rx);
-        const float w = imp[i];
-        for (int c = 0; c < C; ++c) {
-            const float val = ld > 0 ? DT<T>::ld(win + i * ld + c) : DT<T>::ld(win + c * R + i);
-            const float prod = w * val;
-            out[c * V + v] = out[c * V + v] + prod;
-        }
-        cnt[v] += w;
-    }
-}
-
 __global__ void sw_normalize_kernel(float* out, const float* cnt, int C, long long V) {
     const long long total = (long long)C * V;
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256)
         out[i] = out[i] / cnt[i % V];
 }
-
-template <typename T>
-__global__ void sw_gather_kernel(const float* __restrict__ vol, T* __restrict__ win, int C, int VD, int VH, int VW,
-                                 int RD, int RH, int RW, int z0, int y0, int x0, float cval) {
-    const long long R = (long long)RD * RH * RW, V = (long long)VD * VH * VW;
-    const long long total = R * C;
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const long long ri = i % R;
-        const int c = (int)(i / R);
-        const int rx = (int)(ri % RW), ry = (int)((ri / RW) % RH), rz = (int)(ri / ((long long)RW * RH));
-        const int z = z0 + rz, y = y0 + ry, x = x0 + rx;
-        float v = cval;
-        if ((unsigned)z < (unsigned)VD && (unsigned)y < (unsigned)VH && (unsigned)x < (unsigned)VW)
-            v = vol[c * V + ((long long)z * VH + y) * VW + x];
-        DT<T>::st(win + i, v);
-    }
-}
-
 
 // ---- batched forms: one launch per window batch, window starts in a device-resident table ----------------
 // table[j] = (b, z0, y0, x0); b < 0 marks an unused slot (short last batch).
@@ -598,44 +561,11 @@ int msseg_dice_ce_bwd(const void* logits, long long ld, int dtype, const void* l
                 smooth_dr, (hipStream_t)stream);
 }
 
-int msseg_sw_blend(const void* win, long long ld, int dtype, const float* imp, float* out, float* cnt, int C, int VD,
-                   int VH, int VW, int RD, int RH, int RW, int z0, int y0, int x0, msseg_stream_t stream) {
-    if (!win || !imp || !out || !cnt || C < 1) MSSEG_FAIL(MSSEG_EINVAL, "sw_blend: bad args");
-    if (z0 < 0 || y0 < 0 || x0 < 0 || z0 + RD > VD || y0 + RH > VH || x0 + RW > VW)
-        MSSEG_FAIL(MSSEG_EINVAL, "sw_blend: window (%d,%d,%d)+(%d,%d,%d) outside volume (%d,%d,%d)", z0, y0, x0, RD, RH,
-                   RW, VD, VH, VW);
-    const int g = grid_for((long long)RD * RH * RW, 1);
-    if (dtype == MSSEG_F32)
-        hipLaunchKernelGGL(sw_blend_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)win, ld, imp,
-                           out, cnt, C, VD, VH, VW, RD, RH, RW, z0, y0, x0);
-    else if (dtype == MSSEG_BF16)
-        hipLaunchKernelGGL(sw_blend_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)win, ld,
-                           imp, out, cnt, C, VD, VH, VW, RD, RH, RW, z0, y0, x0);
-    else MSSEG_FAIL(MSSEG_EINVAL, "sw_blend: bad dtype");
-    MSSEG_CHECK_LAUNCH("sw_blend");
-    return MSSEG_OK;
-}
-
 int msseg_sw_normalize(float* out, const float* cnt, int C, long long V, msseg_stream_t stream) {
     if (!out || !cnt || C < 1 || V < 1) MSSEG_FAIL(MSSEG_EINVAL, "sw_normalize: bad args");
     hipLaunchKernelGGL(sw_normalize_kernel, dim3(grid_for((long long)C * V)), dim3(256), 0, (hipStream_t)stream, out, cnt,
                        C, V);
     MSSEG_CHECK_LAUNCH("sw_normalize");
-    return MSSEG_OK;
-}
-
-int msseg_sw_gather(const float* vol, void* win, int dtype, int C, int VD, int VH, int VW, int RD, int RH, int RW, int z0,
-                    int y0, int x0, float cval, msseg_stream_t stream) {
-    if (!vol || !win || C < 1) MSSEG_FAIL(MSSEG_EINVAL, "sw_gather: bad args");
-    const int g = grid_for((long long)C * RD * RH * RW);
-    if (dtype == MSSEG_F32)
-        hipLaunchKernelGGL(sw_gather_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, vol, (float*)win, C, VD, VH,
-                           VW, RD, RH, RW, z0, y0, x0, cval);
-    else if (dtype == MSSEG_BF16)
-        hipLaunchKernelGGL(sw_gather_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, vol, (bf16_t*)win, C, VD,
-                           VH, VW, RD, RH, RW, z0, y0, x0, cval);
-    else MSSEG_FAIL(MSSEG_EINVAL, "sw_gather: bad dtype");
-    MSSEG_CHECK_LAUNCH("sw_gather");
     return MSSEG_OK;
 }
 

@@ -5,7 +5,7 @@ function that feeds ``(window, centers, affine)`` tuples to the predictor): cons
 ``scan_interval = int(roi * (1 - overlap))``, dense windows in row-major order with the last start clamped,
 Gaussian (sigma = 0.125 * roi) or constant importance map, blend of raw LOGITS ``out += w * logit; cnt += w``,
 ``out / cnt``, crop of the padding.  Differences, all result-preserving: the window gather, blend and
-normalise are HIP kernels (``msseg_sw_gather/_blend/_normalize``); the count map has one channel instead of
+normalise are HIP kernels (``msseg_sw_gather_batch/_blend_batch/_normalize``); the count map has one channel instead of
 ``classes`` identical ones; under ``torch.distributed`` the accumulators are updated batch by batch (memory O(volume), like the reference); with
 ``shard_ranks=True`` window batches are dealt round-robin to the ranks and each step's logits are exchanged with one
 all-gather, after which every rank blends the step's windows in the reference order (bit-identical to the single-GPU

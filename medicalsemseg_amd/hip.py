@@ -58,24 +58,14 @@ SIGNATURES = {
                                      _vp, _vp, _i, _vp, _sz, _i, _vp], _i),
     "msseg_conv3d_k1_dgrad_inbwd": ([_vp, _ll, _vp, _vp, _ll, _i, _ll, _i, _i, _vp, _ll, _vp, _ll, _vp, _f, _f, _vp,
                                      _vp, _vp, _i, _vp, _sz, _i, _vp], _i),
-    "msseg_deconv_k2s2_bwd_data_inbwd": ([_vp, _ll, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp, _ll, _vp, _ll, _vp, _f, _f,
-                                          _vp, _vp, _vp, _i, _vp, _sz, _i, _vp], _i),
     "msseg_deconv_k2s2_bwd_fused": ([_vp, _ll, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp, _ll, _vp, _ll, _vp, _f, _f,
                                      _vp, _vp, _vp, _i, _vp, _i, _vp, _sz, _i, _vp], _i),
     "msseg_conv3d_k3s2_fwd": ([_vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "msseg_zero_stuff2": ([_vp, _ll, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "msseg_window_attention_fwd": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "msseg_window_attention_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "msseg_window_attention_bwd_ws": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp,
-                                       _sz, _vp], _i),
-    "msseg_window_attention_fwd2": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "msseg_window_attention_bwd2": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp,
-                                     _sz, _vp], _i),
-    "msseg_window_attention_bwd_workspace_bytes": ([_i, _i, _i, _i, _i, _i, _i, _i, _i], _sz),
-    "msseg_window_attention_fwd3": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _ll, _i, _vp], _i),
-    "msseg_window_attention_bwd3": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _ll, _i,
-                                     _vp, _sz, _vp], _i),
-    "msseg_window_attention_bwd3_workspace_bytes": ([_i, _i, _i, _i, _i, _i, _i, _i, _i, _ll, _i], _sz),
+    "msseg_window_attention_fwd": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _ll, _i, _vp], _i),
+    "msseg_window_attention_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _ll, _i,
+                                    _vp, _sz, _vp], _i),
+    "msseg_window_attention_bwd_workspace_bytes": ([_i, _i, _i, _i, _i, _i, _i, _i, _i, _ll, _i], _sz),
     "msseg_rel_bias_affine_fold": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp], _i),
     "msseg_rel_bias_affine_grad_workspace_bytes": ([_i, _i], _sz),
     "msseg_rel_bias_affine_grad": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp], _i),
@@ -134,9 +124,7 @@ SIGNATURES = {
     "msseg_dice_ce_bwd": ([_vp, _ll, _i, _vp, _i, _vp, _vp, _vp, _ll, _i, _ll, _i, _f, _f, _vp], _i),
     "msseg_adamw_step": ([_vp, _vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _f, _i, _vp, _vp, _vp], _i),
     "msseg_sumsq": ([_vp, _ll, _vp, _vp, _i, _vp], _i),
-    "msseg_sw_blend": ([_vp, _ll, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "msseg_sw_normalize": ([_vp, _vp, _i, _ll, _vp], _i),
-    "msseg_sw_gather": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp], _i),
     "msseg_box_copy": ([_vp, _ll, _i, _i, _i, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp], _i),
     "msseg_merge_gather_fwd": ([_vp, _ll, _i, _i, _i, _vp, _ll, _i, _i, C.c_uint, _i, _vp], _i),
     "msseg_merge_gather_bwd": ([_vp, _ll, _vp, _ll, _i, _i, _i, _i, _i, C.c_uint, _i, _vp], _i),
@@ -158,10 +146,8 @@ SIGNATURES = {
     "msseg_conv3d_k3_small_workspace_bytes": ([_i, _i, _i, _i, _i, _i], _sz),
     "msseg_conv3d_k3_small_stage_groups": ([_i, _i, _i, _i, _i, _i], _i),
     "msseg_conv3d_k3_small_partials": ([_vp, _ll, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "msseg_conv3d_k3_small_fwd_finish": ([_vp, _i, _vp, _vp, _vp, _f, _f, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _i, _i, _i, _i,
-                                          _i, _vp], _i),
-    "msseg_conv3d_k3_small_fwd_finish_res": ([_vp, _i, _vp, _vp, _vp, _f, _f, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _i, _i, _i, _i,
-                                              _i, _vp], _i),
+    "msseg_conv3d_k3_small_fwd_finish": ([_vp, _i, _vp, _vp, _vp, _f, _f, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _i, _i,
+                                          _i, _i, _i, _vp], _i),
     "msseg_conv3d_k3_small_bwd_finish": ([_vp, _i, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _f, _f, _vp, _vp, _i, _i, _i, _i, _i,
                                           _i, _vp], _i),
     "msseg_avgpool3d_k3": ([_vp, _ll, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp], _i),
@@ -190,7 +176,7 @@ def load_library(path: Optional[str] = None):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res
-    if lib.msseg_abi_version() != 1:
+    if lib.msseg_abi_version() != 2:
         raise RuntimeError("libmsseg_hip.so ABI version mismatch")
     _lib = lib
     return lib
@@ -616,10 +602,10 @@ def conv3d_k3_small_fwd_finish(part, nstages, bias, gamma, beta, eps, slope, yra
     """residual (optional, same shape as act): act = lrelu(instance_norm(y) * gamma + beta + residual)"""
     _need_gpu(part, yraw, act, stats)
     N, D, H, W, cout = yraw.shape
-    _ck(lib().msseg_conv3d_k3_small_fwd_finish_res(_p(part), nstages, _p(bias), _p(gamma), _p(beta), eps, slope, _p(yraw), ld(yraw),
-                                                   _p(act), ld(act), _p(residual), ld(residual) if residual is not None else 0,
-                                                   _p(pooled), ld(pooled) if pooled is not None else 0,
-                                                   _p(stats), N, D, H, W, cout, _stream()), "conv3d_k3_small_fwd_finish")
+    _ck(lib().msseg_conv3d_k3_small_fwd_finish(_p(part), nstages, _p(bias), _p(gamma), _p(beta), eps, slope, _p(yraw), ld(yraw),
+                                               _p(act), ld(act), _p(residual), ld(residual) if residual is not None else 0,
+                                               _p(pooled), ld(pooled) if pooled is not None else 0,
+                                               _p(stats), N, D, H, W, cout, _stream()), "conv3d_k3_small_fwd_finish")
 
 
 def conv3d_k3_small_bwd_finish(part, nstages, dx, unit=None, dgamma=None, dbeta=None, accumulate=False):
@@ -707,20 +693,6 @@ def conv3d_k1_dgrad_inbwd(dy, wp, da, cin, cout, yraw, act, fwd_stats, slope, ep
     _ck(lib().msseg_conv3d_k1_dgrad_inbwd(_p(dy), ld(dy), _p(wp), _p(da), ld(da), N, S, cin, cout, _p(yraw), ld(yraw),
                                           _p(act), ld(act), _p(fwd_stats), slope, eps, _p(red), _p(dgamma), _p(dbeta),
                                           int(accumulate), _p(sc), sc.numel(), dt(dy), _stream()), "conv3d_k1_dgrad_inbwd")
-    return red
-
-
-def deconv_k2s2_bwd_data_inbwd(dy, wp, dx, cin, cout, yraw, act, fwd_stats, slope, eps, dgamma=None, dbeta=None,
-                               accumulate=False):
-    """dx of ConvTranspose3d k2 s2 + the InstanceNorm-backward sums of the layer that receives dx.  Returns red[N][cin][2]."""
-    _need_gpu(dy, wp, dx, yraw, act, fwd_stats)
-    N, D, H, W = dx.shape[:4]
-    red = torch.empty(N, cin, 2, dtype=torch.float32, device=dy.device)
-    sc = scratch(dy.device)
-    _ck(lib().msseg_deconv_k2s2_bwd_data_inbwd(_p(dy), ld(dy), _p(wp), _p(dx), ld(dx), N, D, H, W, cin, cout, _p(yraw),
-                                               ld(yraw), _p(act), ld(act), _p(fwd_stats), slope, eps, _p(red),
-                                               _p(dgamma), _p(dbeta), int(accumulate), _p(sc), sc.numel(), dt(dy),
-                                               _stream()), "deconv_k2s2_bwd_data_inbwd")
     return red
 
 
@@ -1290,31 +1262,10 @@ def sumsq(x, out, partials):
 # --------------------------------------------------------------------------------------------
 # sliding window
 # --------------------------------------------------------------------------------------------
-def sw_blend(win, imp, out, cnt, start, channels_last_ld=0):
-    """win: [C, *roi] (NCDHW, ld 0) ; out: [C, *vol] fp32 ; cnt: [*vol] fp32."""
-    _need_gpu(win, imp, out, cnt)
-    Cc = out.shape[0]
-    VD, VH, VW = out.shape[1:]
-    RD, RH, RW = imp.shape
-    _ck(lib().msseg_sw_blend(_p(win), channels_last_ld, dt(win), _p(imp), _p(out), _p(cnt), Cc, VD, VH, VW, RD, RH, RW,
-                             int(start[0]), int(start[1]), int(start[2]), _stream()), "sw_blend")
-
-
 def sw_normalize(out, cnt):
     _need_gpu(out, cnt)
     _ck(lib().msseg_sw_normalize(_p(out), _p(cnt), out.shape[0], cnt.numel(), _stream()), "sw_normalize")
     return out
-
-
-def sw_gather(vol, win, start, cval=0.0):
-    """vol: [C, *vol] fp32 ; win: [C, *roi] (dtype of win)."""
-    _need_gpu(vol, win)
-    Cc = vol.shape[0]
-    VD, VH, VW = vol.shape[1:]
-    RD, RH, RW = win.shape[1:]
-    _ck(lib().msseg_sw_gather(_p(vol), _p(win), dt(win), Cc, VD, VH, VW, RD, RH, RW, int(start[0]), int(start[1]),
-                              int(start[2]), float(cval), _stream()), "sw_gather")
-    return win
 
 
 def sw_gather_batch(vol, win, table, nwin, cval=0.0, channels_last_ld=0):
@@ -1560,63 +1511,48 @@ def zero_stuff2(dy, out):
     return out
 
 
+def _attn_table_stride(table, B, heads, bws):
+    """0 for a shared bias table [M3, heads]; M3 * heads for per-sample tables [B, M3, heads] fp32 contiguous"""
+    if table.dim() != 3:
+        return 0
+    assert table.is_contiguous() and table.dtype == torch.float32
+    assert table.shape == (B, (2 * bws - 1) ** 3, heads), table.shape
+    return table[0].numel()
+
+
 def window_attention_fwd(qkv, qkv_bias, table, out, heads, ws, shift, bias_ws=None):
-    """qkv [B,S,H,W,3C] contiguous -> out [B,S,H,W,C]; returns lse for the backward.  bias_ws: window edge the bias table
-    was built for (MONAI SwinUNETR: 7 even where the window is clamped to a smaller grid)."""
+    """qkv [B,S,H,W,3C] contiguous -> out [B,S,H,W,C]; returns lse for the backward.  table: [M3, heads] shared by every
+    sample, or [B, M3, heads] with one table per sample.  bias_ws: window edge the bias table was built for (MONAI
+    SwinUNETR: 7 even where the window is clamped to a smaller grid)."""
     _need_gpu(qkv, table, out)
     assert qkv.is_contiguous() and out.is_contiguous()
     B, S, H, W, C3 = qkv.shape
-    Cc = C3 // 3
+    bws = bias_ws or ws
     nW = -(-S // ws) * -(-H // ws) * -(-W // ws)
     lse = torch.empty(B * nW, heads, ws ** 3, dtype=torch.float32, device=qkv.device)
-    _ck(lib().msseg_window_attention_fwd2(_p(qkv), _p(qkv_bias), _p(table), _p(out), _p(lse), B, S, H, W, Cc, heads, ws,
-                                          shift, bias_ws or ws, dt(qkv), _stream()), "window_attention_fwd")
+    _ck(lib().msseg_window_attention_fwd(_p(qkv), _p(qkv_bias), _p(table), _p(out), _p(lse), B, S, H, W, C3 // 3, heads, ws,
+                                         shift, bws, _attn_table_stride(table, B, heads, bws), dt(qkv), _stream()),
+        "window_attention_fwd")
     return lse
 
 
 def window_attention_bwd(qkv, qkv_bias, table, out, lse, dout, dqkv, dtable, heads, ws, shift, bias_ws=None):
+    """backward of window_attention_fwd; dtable (nullable, shaped like table) is ACCUMULATED, per sample for per-sample
+    tables"""
     _need_gpu(qkv, table, out, lse, dout, dqkv)
     assert qkv.is_contiguous() and out.is_contiguous() and dout.is_contiguous() and dqkv.is_contiguous()
     B, S, H, W, C3 = qkv.shape
-    wsb = 0
     bws = bias_ws or ws
-    if dtable is not None:
-        wsb = int(lib().msseg_window_attention_bwd_workspace_bytes(B, S, H, W, C3 // 3, heads, ws, shift, dt(qkv)))
-    work = torch.empty(wsb, dtype=torch.uint8, device=qkv.device) if wsb else None
-    _ck(lib().msseg_window_attention_bwd2(_p(qkv), _p(qkv_bias), _p(table), _p(out), _p(lse), _p(dout), _p(dqkv),
-                                          _p(dtable), B, S, H, W, C3 // 3, heads, ws, shift, bws, dt(qkv), _p(work), wsb,
-                                          _stream()), "window_attention_bwd")
-    return dqkv
-
-
-def window_attention_fwd_per_sample(qkv, qkv_bias, tables, out, heads, ws, shift):
-    """window_attention_fwd with one bias table per sample: tables [B, (2ws-1)^3, heads] fp32 contiguous"""
-    _need_gpu(qkv, tables, out)
-    assert qkv.is_contiguous() and out.is_contiguous() and tables.is_contiguous() and tables.dtype == torch.float32
-    B, S, H, W, C3 = qkv.shape
-    assert tables.shape == (B, (2 * ws - 1) ** 3, heads), tables.shape
-    nW = -(-S // ws) * -(-H // ws) * -(-W // ws)
-    lse = torch.empty(B * nW, heads, ws ** 3, dtype=torch.float32, device=qkv.device)
-    _ck(lib().msseg_window_attention_fwd3(_p(qkv), _p(qkv_bias), _p(tables), _p(out), _p(lse), B, S, H, W, C3 // 3, heads,
-                                          ws, shift, ws, tables[0].numel(), dt(qkv), _stream()), "window_attention_fwd3")
-    return lse
-
-
-def window_attention_bwd_per_sample(qkv, qkv_bias, tables, out, lse, dout, dqkv, dtables, heads, ws, shift):
-    """backward of window_attention_fwd_per_sample; dtables [B, (2ws-1)^3, heads] (nullable) is ACCUMULATED per sample"""
-    _need_gpu(qkv, tables, out, lse, dout, dqkv)
-    assert qkv.is_contiguous() and out.is_contiguous() and dout.is_contiguous() and dqkv.is_contiguous()
-    B, S, H, W, C3 = qkv.shape
-    stride = tables[0].numel()
+    stride = _attn_table_stride(table, B, heads, bws)
     wsb = 0
-    if dtables is not None:
-        assert dtables.is_contiguous() and dtables.shape == tables.shape
-        wsb = int(lib().msseg_window_attention_bwd3_workspace_bytes(B, S, H, W, C3 // 3, heads, ws, shift, ws, stride,
-                                                                     dt(qkv)))
+    if dtable is not None:
+        assert stride == 0 or (dtable.is_contiguous() and dtable.shape == table.shape)
+        wsb = int(lib().msseg_window_attention_bwd_workspace_bytes(B, S, H, W, C3 // 3, heads, ws, shift, bws, stride,
+                                                                    dt(qkv)))
     work = torch.empty(wsb, dtype=torch.uint8, device=qkv.device) if wsb else None
-    _ck(lib().msseg_window_attention_bwd3(_p(qkv), _p(qkv_bias), _p(tables), _p(out), _p(lse), _p(dout), _p(dqkv),
-                                          _p(dtables), B, S, H, W, C3 // 3, heads, ws, shift, ws, stride, dt(qkv), _p(work),
-                                          wsb, _stream()), "window_attention_bwd3")
+    _ck(lib().msseg_window_attention_bwd(_p(qkv), _p(qkv_bias), _p(table), _p(out), _p(lse), _p(dout), _p(dqkv),
+                                         _p(dtable), B, S, H, W, C3 // 3, heads, ws, shift, bws, stride, dt(qkv), _p(work),
+                                         wsb, _stream()), "window_attention_bwd")
     return dqkv
 
 

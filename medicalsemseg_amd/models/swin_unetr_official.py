@@ -10,7 +10,7 @@ Parameter / buffer names equal the reference's state-dict keys (``swinViT.layers
 Same execution model as ``models/swin_unetr.py``: channels-last token volumes, the encoder a chain of single-kernel
 autograd ops, the conv decoder ONE autograd node over ``layers.py``.  Window padding is explicit here (pad -> attention on
 a whole number of windows -> crop), so that the padded tokens' ``qkv.bias`` gradient is exact; the clamped stage passes
-``bias_ws = 7`` to the attention kernel (``msseg_window_attention_fwd2``).  Only cubic volumes / windows are implemented.
+``bias_ws = 7`` to the attention kernel (``msseg_window_attention_fwd``).  Only cubic volumes / windows are implemented.
 """
 from __future__ import annotations
 

@@ -420,7 +420,7 @@ class WindowAttnAffineFn(torch.autograd.Function):
         hip.rel_bias_affine_fold(*prm, aff, tabs)
         out = torch.empty(B, S, H, W, C3 // 3, dtype=qkv.dtype, device=qkv.device)
         qb = qkv_bias.detach() if qkv_bias is not None else None
-        lse = hip.window_attention_fwd_per_sample(qkv, qb, tabs, out, heads, ws, shift)
+        lse = hip.window_attention_fwd(qkv, qb, tabs, out, heads, ws, shift)
         ctx.save_for_backward(qkv, qb, tabs, out, lse, aff, prm[1], prm[2])
         ctx.cfg = (heads, ws, shift)
         ctx.params = (table, emb, lin_w, lin_b)
@@ -433,7 +433,7 @@ class WindowAttnAffineFn(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         want = [ctx.needs_input_grad[i] for i in (2, 3, 4, 5)]
         dT = torch.zeros_like(tabs) if any(want) else None
-        hip.window_attention_bwd_per_sample(qkv, qb, tabs, out, lse, _c(dout), dqkv, dT, heads, ws, shift)
+        hip.window_attention_bwd(qkv, qb, tabs, out, lse, _c(dout), dqkv, dT, heads, ws, shift)
         bufs, ret = [None] * 4, [None] * 4
         flags = 0
         if dT is not None:

@@ -1,4 +1,6 @@
-"""CPU-side checks of the C-ABI library: it loads and exports every symbol include/msseg.h declares."""
+"""CPU-side checks of the C-ABI library: it loads and exports every symbol include/msseg.h declares, and the ctypes table
+of hip.py agrees with the header's prototypes."""
+import ctypes as C
 import os
 import re
 
@@ -24,8 +26,43 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/msseg.h but not exported"
         assert n in hip.SIGNATURES, f"{n} has no ctypes signature in hip.py"
-    assert lib.msseg_abi_version() == 1
+    assert lib.msseg_abi_version() == 2
     assert lib.msseg_cout_block(32) == 32 and lib.msseg_cout_block(48) == 48 and lib.msseg_cout_block(3) == 16
+
+
+def test_signatures_cover_exactly_the_header():
+    from medicalsemseg_amd import hip
+    assert set(hip.SIGNATURES) == set(_declared())
+
+
+_SCALARS = {"int": C.c_int, "long long": C.c_longlong, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
+            "unsigned": C.c_uint, "msseg_stream_t": C.c_void_p}
+
+
+def _ctype(ctype, func):
+    """ctypes class of a C type as written in include/msseg.h (qualifiers and spacing normalised)"""
+    t = " ".join(ctype.replace("const", " ").replace("*", " * ").split())
+    if t == "char *":
+        return C.c_char_p
+    if t == "float *" and func == "msseg_ktimer_get":
+        return C.POINTER(C.c_float)
+    return C.c_void_p if t.endswith("*") else _SCALARS[t]
+
+
+def test_signature_types_match_header():
+    from medicalsemseg_amd import hip
+    txt = open(os.path.join(ROOT, "include", "msseg.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"^\s*#.*$", "", txt, flags=re.M)
+    protos = re.findall(r"([\w\s*]+?)\b(msseg_\w+)\s*\(([^()]*)\)\s*;", txt)
+    assert {name for _, name, _ in protos} == set(_declared())
+    for ret, name, args in protos:
+        args = [] if args.strip() == "void" else [re.sub(r"\w+\s*$", "", a) for a in args.split(",")]
+        want_args, want_ret = hip.SIGNATURES[name]
+        assert len(want_args) == len(args), f"{name}: {len(want_args)} ctypes arguments, {len(args)} in the header"
+        for k, (a, w) in enumerate(zip(args, want_args)):
+            assert _ctype(a, name) is w, f"{name}: argument {k} is `{a.strip()}` in the header, {w.__name__} in hip.py"
+        assert _ctype(ret, name) is want_ret, f"{name}: returns `{ret.strip()}` in the header, {want_ret.__name__} in hip.py"
 
 
 def test_product_refuses_cpu():

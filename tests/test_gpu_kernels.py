@@ -363,27 +363,35 @@ def test_dice_ce(C, lab_dtype):
 
 
 def test_sw_gather_blend():
+    """batch forms on one sample; the repeated start puts two windows of one batch on the same voxels, in table order"""
     from medicalsemseg_amd import hip
     dev = _dev()
     vol = gen(2, 20, 24, 28, seed=1)
-    out = torch.zeros(3, 20, 24, 28, device=dev)
-    cnt = torch.zeros(20, 24, 28, device=dev)
     imp = gen(8, 8, 12, seed=2).abs() + 0.1
+    starts = [(0, 0, 0), (4, 8, 6), (12, 16, 16), (4, 8, 6)]
+    wins = torch.stack([gen(3, 8, 8, 12, seed=10 + i) for i in range(4)])
     oref, cref = torch.zeros(3, 20, 24, 28), torch.zeros(20, 24, 28)
-    for i, st in enumerate([(0, 0, 0), (4, 8, 6), (12, 16, 16), (4, 8, 6)]):
-        w = gen(3, 8, 8, 12, seed=10 + i)
-        hip.sw_blend(w.to(dev), imp.to(dev), out, cnt, st)
+    for w, st in zip(wins, starts):
         sl = (slice(None), slice(st[0], st[0] + 8), slice(st[1], st[1] + 8), slice(st[2], st[2] + 12))
         oref[sl] += imp * w
         cref[sl[1:]] += imp
-    # same fp32 operation order as the reference loop -> bit-exact
-    assert torch.equal(cnt.cpu(), cref), f"cnt max diff {float((cnt.cpu() - cref).abs().max())}"
-    assert torch.equal(out.cpu(), oref), f"out max diff {float((out.cpu() - oref).abs().max())}"
-    win = torch.empty(2, 8, 8, 12, device=dev)
-    hip.sw_gather(vol.to(dev), win, (14, 20, 20), cval=-3.0)
+    table = torch.tensor([(0,) + st for st in starts] + [(-1, 0, 0, 0)], dtype=torch.int32, device=dev)
+    wd = torch.cat([wins, torch.zeros(1, 3, 8, 8, 12)]).to(dev)       # the unused slot's window is never read
+    # (a) one launch, 5-row table with an unused last slot; (b) two launches of two windows onto the same accumulators
+    for launches in ([(0, 5)], [(0, 2), (2, 2)]):
+        out = torch.zeros(1, 3, 20, 24, 28, device=dev)
+        cnt = torch.zeros(1, 20, 24, 28, device=dev)
+        for first, n in launches:
+            hip.sw_blend_batch(wd[first:first + n], imp.to(dev), out, cnt, table[first:first + n], n)
+        # same fp32 operation order as the reference loop -> bit-exact
+        assert torch.equal(cnt[0].cpu(), cref), f"cnt max diff {float((cnt[0].cpu() - cref).abs().max())}"
+        assert torch.equal(out[0].cpu(), oref), f"out max diff {float((out[0].cpu() - oref).abs().max())}"
+    win = torch.empty(1, 2, 8, 8, 12, device=dev)
+    gtab = torch.tensor([(0, 14, 20, 20)], dtype=torch.int32, device=dev)
+    hip.sw_gather_batch(vol[None].to(dev), win, gtab, 1, cval=-3.0)
     ref = torch.full((2, 8, 8, 12), -3.0)
     ref[:, :6, :4, :8] = vol[:, 14:20, 20:24, 20:28]
-    assert torch.equal(win.cpu(), ref)
+    assert torch.equal(win[0].cpu(), ref)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
