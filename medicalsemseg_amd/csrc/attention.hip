@@ -112,10 +112,11 @@ __global__ __launch_bounds__(256) void win_attn_fwd_kernel(const AttnParams p) {
 template <typename T, int HD>
 __global__ __launch_bounds__(256) void win_attn_bwd_kernel(const AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const bool two = p.bwd_two_phase;  // K and Q share one array, V and dO the other: K, V staged for phase A, Q, dO for phase B
     float* qS = (float*)smem;          // [N][HD]  (already scaled)
-    float* kS = qS + p.N * HD;
+    float* kS = two ? qS : qS + p.N * HD;
     float* vS = kS + p.N * HD;
-    float* dS = vS + p.N * HD;         // dO [N][HD]
+    float* dS = two ? vS : vS + p.N * HD;   // dO [N][HD]
     float* lseS = dS + p.N * HD;       // [N]
     float* delS = lseS + p.N;          // [N]  delta_i = dO_i . O_i
     float* tabS = delS + p.N;          // [M3]
@@ -148,22 +149,20 @@ __global__ __launch_bounds__(256) void win_attn_bwd_kernel(const AttnParams p) {
             __syncthreads();
             float* dtab = p.dtab_all_heads ? dtabS + h * p.M3 : dtabS;
             for (int i = threadIdx.x; i < p.M3; i += 256) tabS[i] = table[(long long)i * p.heads + h];
+            // channel ch of [0, 3C) of token t (a padded token: the bias, rounded as a stored token would be); dO of a padded token is 0
+            auto qkv_at = [&](int t, int ch) -> float {
+                if (t >= 0) return DT<T>::ld(qkv + (long long)t * 3 * p.C + ch);
+                float v = p.qkv_bias ? p.qkv_bias[ch] : 0.f;
+                if (sizeof(T) == 2) v = (float)(bf16_t)v;
+                return v;
+            };
+            auto dout_at = [&](int t, int c) -> float { return t >= 0 ? DT<T>::ld(dout + (long long)t * p.C + c) : 0.f; };
             for (int i = threadIdx.x; i < p.N * HD; i += 256) {
                 const int j = i / HD, e = i % HD;
                 const int t = tok[j];
                 const int c = h * HD + e;
-                float qv, kv, vv, dov = 0.f;
-                if (t >= 0) {
-                    const T* row = qkv + (long long)t * 3 * p.C;
-                    qv = DT<T>::ld(row + c); kv = DT<T>::ld(row + p.C + c); vv = DT<T>::ld(row + 2 * p.C + c);
-                    dov = DT<T>::ld(dout + (long long)t * p.C + c);
-                } else {
-                    qv = p.qkv_bias ? p.qkv_bias[c] : 0.f;
-                    kv = p.qkv_bias ? p.qkv_bias[p.C + c] : 0.f;
-                    vv = p.qkv_bias ? p.qkv_bias[2 * p.C + c] : 0.f;
-                    if (sizeof(T) == 2) { qv = (float)(bf16_t)qv; kv = (float)(bf16_t)kv; vv = (float)(bf16_t)vv; }
-                }
-                qS[i] = qv * p.scale; kS[i] = kv; vS[i] = vv; dS[i] = dov;
+                if (!two) { qS[i] = qkv_at(t, c) * p.scale; dS[i] = dout_at(t, c); }
+                kS[i] = qkv_at(t, p.C + c); vS[i] = qkv_at(t, 2 * p.C + c);
             }
             for (int i = threadIdx.x; i < p.N; i += 256) {
                 lseS[i] = p.lse[((long long)wb * p.heads + h) * p.N + i];
@@ -181,7 +180,11 @@ __global__ __launch_bounds__(256) void win_attn_bwd_kernel(const AttnParams p) {
             for (int i = threadIdx.x; i < p.N; i += 256) {
                 float q[HD], dq[HD], dO[HD];
 #pragma unroll
-                for (int e = 0; e < HD; ++e) { q[e] = qS[i * HD + e]; dO[e] = dS[i * HD + e]; dq[e] = 0.f; }
+                for (int e = 0; e < HD; ++e) {
+                    if (two) { q[e] = qkv_at(tok[i], h * HD + e) * p.scale; dO[e] = dout_at(tok[i], h * HD + e); }
+                    else { q[e] = qS[i * HD + e]; dO[e] = dS[i * HD + e]; }
+                    dq[e] = 0.f;
+                }
                 const float lse = lseS[i], del = delS[i];
                 const int ri = regS[i], ci = codeS[i] + off;
                 const bool live = tok[i] >= 0;
@@ -204,11 +207,23 @@ __global__ __launch_bounds__(256) void win_attn_bwd_kernel(const AttnParams p) {
                     for (int e = 0; e < HD; ++e) DT<T>::st(dqkv + (long long)t * 3 * p.C + h * HD + e, dq[e] * p.scale);
                 }
             }
+            if (two) {   // every thread is done with K and V: Q and dO take their place
+                __syncthreads();
+                for (int i = threadIdx.x; i < p.N * HD; i += 256) {
+                    const int t = tok[i / HD], c = h * HD + i % HD;
+                    qS[i] = qkv_at(t, c) * p.scale; dS[i] = dout_at(t, c);
+                }
+                __syncthreads();
+            }
             // phase B: thread = key j -> dK_j, dV_j
             for (int j = threadIdx.x; j < p.N; j += 256) {
                 float k[HD], v[HD], dk[HD], dv[HD];
 #pragma unroll
-                for (int e = 0; e < HD; ++e) { k[e] = kS[j * HD + e]; v[e] = vS[j * HD + e]; dk[e] = dv[e] = 0.f; }
+                for (int e = 0; e < HD; ++e) {
+                    if (two) { k[e] = qkv_at(tok[j], p.C + h * HD + e); v[e] = qkv_at(tok[j], 2 * p.C + h * HD + e); }
+                    else { k[e] = kS[j * HD + e]; v[e] = vS[j * HD + e]; }
+                    dk[e] = dv[e] = 0.f;
+                }
                 const int rj = regS[j], cj = off - codeS[j];
                 for (int i = 0; i < p.N; ++i) {
                     if (tok[i] < 0) continue;  // padded queries produce no output, hence no gradient
@@ -608,7 +623,10 @@ int msseg_window_attention_bwd(const void* qkv, const float* qkv_bias, const flo
         }
         return msseg_window_attention_bwd_mfma(p, (hipStream_t)stream);
     }
-    const size_t base = (size_t)p.N * p.hd * 4 * 4 + (size_t)p.N * 5 * 4 + (size_t)p.M3 * 4;
+    size_t base = (size_t)p.N * p.hd * 4 * 4 + (size_t)p.N * 5 * 4 + (size_t)p.M3 * 4;
+    // Q, K, V, dO of one head do not fit together (head dim 32 at 343 tokens): two arrays, staged once per phase
+    p.bwd_two_phase = base + (size_t)p.M3 * 4 > 160 * 1024 ? 1 : 0;
+    if (p.bwd_two_phase) base -= (size_t)p.N * p.hd * 2 * 4;
     // (per-sample tables: the LDS sums are flushed after every (window, head), into the table of that window's sample)
     p.dtab_all_heads = (table_stride == 0 && base + (size_t)heads * p.M3 * 4 <= 96 * 1024) ? 1 : 0;
     const size_t smem = base + (size_t)(p.dtab_all_heads ? heads : 1) * p.M3 * 4;

@@ -28,6 +28,8 @@ struct AttnParams {
     int Sp, Hp, Wp, nWs, nWh, nWw, N, M3, nwin_total;
     float scale;
     int use_mask;
+    int bwd_two_phase;    // vector backward: K, V (phase A) and Q, dO (phase B) take turns in the same two LDS arrays, for windows whose
+                          // four arrays do not fit together (head dim 32 at 343 tokens)
 };
 
 MSSEG_DEVFN int region_id(int z, int Lp, int ws, int shift) { return z < Lp - ws ? 0 : (z < Lp - shift ? 1 : 2); }

@@ -258,6 +258,10 @@ class _Block(nn.Module):
         """affine: [B, 3] fp32 spacings on the device (ops.expand_affine) or None; used by rel_pos_bias_affine blocks only"""
         a = self.attn
         x, xn = ops.layer_norm_res(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)   # x: the residual, through the node
+        grid = tuple(x.shape[1:4])
+        full = tuple(-(-v // self.ws) * self.ws for v in grid)
+        if full != grid:   # zero tokens AFTER the norm, as the reference pads (swin_nnformer.py:247-251): their qkv is the bias,
+            xn = ops.box_resize(xn, full)   # and its gradient takes their share; cropped below.  Window multiples: untouched
         qkv = ops.linear(xn, a.qkv.weight, a.qkv.bias)
         if a.rel_pos_bias_affine and affine is not None:
             y = ops.WindowAttnAffineFn.apply(qkv, a.qkv.bias, a.relative_position_bias_table, a.rel_pos_bias_affine_emb,
@@ -265,6 +269,8 @@ class _Block(nn.Module):
                                              self.heads, self.ws, self.shift)
         else:
             y = ops.WindowAttnFn.apply(qkv, a.qkv.bias, a.relative_position_bias_table, self.heads, self.ws, self.shift)
+        if full != grid:
+            y = ops.box_resize(y, grid)
         dp = self._dp_scale(x)
         if dp is None:     # no stochastic depth in this step: the residual adds ride on the Linear kernels' epilogues
             x = ops.linear_add(y, a.proj.weight, a.proj.bias, x)

@@ -387,7 +387,8 @@ class WindowAttnFn(torch.autograd.Function):
             else:
                 dtable = torch.zeros_like(tab)
         hip.window_attention_bwd(qkv, qb, tab, out, lse, _c(dout), dqkv, dtable, heads, ws, shift, bias_ws)
-        # gradient w.r.t. qkv_bias through PADDED tokens (only when the grid is not a window multiple) is dropped
+        # no gradient w.r.t. qkv_bias: tokens the KERNEL pads are constants to it.  The models zero-pad the token volume to a window
+        # multiple before the qkv Linear (box_resize), so the bias' share of the padded tokens arrives through that Linear
         return dqkv, None, (None if ctx.table.is_contiguous() else dtable), None, None, None, None
 
 
@@ -447,7 +448,7 @@ class WindowAttnAffineFn(torch.autograd.Function):
                 else:
                     bufs[k] = ret[k] = torch.empty(p.shape, dtype=torch.float32, device=p.device)
             hip.rel_bias_affine_grad(dT, emb, lin_w, aff, *bufs, flags=flags)
-        # gradient w.r.t. qkv_bias through PADDED tokens is dropped, as in WindowAttnFn
+        # no gradient w.r.t. qkv_bias, as in WindowAttnFn: the models pad before the qkv Linear
         return (dqkv, None, *ret, None, None, None, None)
 
 

@@ -1,5 +1,7 @@
 """GPU parity of the Swin path: HIP window attention / Swin block / encoder against the golden vectors produced by
 the REFERENCE's own modules (tests/golden, oracle/gen_golden.py), and the whole Swin-UNETR against the oracle."""
+import copy
+import functools
 import os
 
 import numpy as np
@@ -115,6 +117,79 @@ def test_swin_block_vs_reference_golden(golden_dir, shift):
         r = det_tensor("blk_r", (2, 12 ** 3, 48)).reshape(2, 12, 12, 12, 48).to(DEV)
         (y * r).sum().backward()
         assert _rel(x.grad.reshape(2, -1, 48), g["dx_shift3"]) < 1e-3
+
+
+BLOCK_AFF = [[1.5, 0.8, 2.0], [-0.7, 1.25, 3.0]]
+
+
+@functools.lru_cache(maxsize=None)
+def _block_ref(res, ws, shift, affine):
+    """float64 CPU: oracle.swin.SwinTransformerBlock under the deterministic parameters of the product block; with the
+    spacing-conditioned bias its attention core is tests.attention_ref (pinned to this very block by
+    tests/test_attention_ref_host.py) under per-sample tables folded from table, emb and lin in float64.  One reference serves
+    both dtypes: x and r hold bf16-exact values."""
+    from medicalsemseg_amd.models.swin_unetr import _Block
+    from oracle import swin as O
+    from tests.attention_ref import window_attention_ref
+    dim, heads = 48, 3
+    m = _Block(dim, res, heads, ws, shift, 4.0, True, 0.0, rel_pos_bias_affine=affine)
+    det_fill_(m, "blkpad")
+    ref = O.SwinTransformerBlock(dim, res, heads, ws, shift).double()
+    extra = ref.load_state_dict(m.state_dict(), strict=False)
+    assert not extra.missing_keys and all("rel_pos_bias_affine" in k for k in extra.unexpected_keys)
+    S, H, W = res
+    x = det_tensor("blkpad_x", (2, S, H, W, dim)).bfloat16().double().requires_grad_(True)
+    r = det_tensor("blkpad_r", (2, S, H, W, dim)).bfloat16().double()
+    a = ref.attn
+    params = dict(ref.named_parameters())
+    if affine:
+        emb = m.attn.rel_pos_bias_affine_emb.detach().double().requires_grad_(True)
+        lw = m.attn.rel_pos_bias_affine_lin.weight.detach().double().requires_grad_(True)
+        lb = m.attn.rel_pos_bias_affine_lin.bias.detach().double().requires_grad_(True)
+        aff = torch.tensor(BLOCK_AFF, dtype=torch.float64)
+        tabs = a.relative_position_bias_table[None] + lb + (emb[None] * (lw[0] * aff)[:, None, None, :]).sum(-1)
+        params.update({"attn.rel_pos_bias_affine_emb": emb, "attn.rel_pos_bias_affine_lin.weight": lw,
+                       "attn.rel_pos_bias_affine_lin.bias": lb})
+        qkv = a.qkv(ref.norm1(x))
+        out, _, _ = window_attention_ref(qkv, a.qkv.bias, tabs, heads, ws, shift)
+        h = x + a.proj(out)
+        y = h + ref.mlp(ref.norm2(h))
+    else:
+        full = [-(-v // ws) * ws for v in res]
+        y = ref(x.reshape(2, -1, dim), O.shift_region_mask(*full, ws, shift).double()).reshape(2, S, H, W, dim)
+    (y * r).sum().backward()
+    return m, x.detach(), r, y.detach(), x.grad, {k: p.grad for k, p in params.items()}
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("affine", [False, True])
+@pytest.mark.parametrize("res,ws,shift", [((5, 8, 7), 3, 1), ((10, 10, 10), 6, 3)])
+def test_swin_block_on_padded_grids_vs_float64_oracle(res, ws, shift, affine, dtype):
+    """models.swin_unetr._Block on grids that are no window multiple (10^3 under window 6: 42 % of the windows' tokens are
+    padding) against oracle.swin.SwinTransformerBlock in float64: y, dx and the gradient of EVERY parameter, attn.qkv.bias among
+    them, whose gradient takes the share of the padded tokens (the reference pads before its qkv Linear: Linear(0) = bias).
+    Gates of test_swin_official_encoder_vs_reference_golden for the same quantities in fp32 (features 1e-3, parameter
+    gradients 5e-3; dx under the 1e-3 of test_swin_block_vs_reference_golden), of test_window_attention_vs_reference_golden in
+    bf16 (3e-2, 5e-2).  lin.bias' gradient is a sum of all dS, zero up to rounding: gated against the L1 mass of the table
+    gradient, as tests/test_gpu_affine_bias.py does."""
+    m, x64, r64, y64, dx64, grads = _block_ref(res, ws, shift, affine)       # CPU, before the first GPU call
+    m = copy.deepcopy(m).to(DEV)
+    x = x64.to(DEV, dtype).requires_grad_(True)
+    aff = torch.tensor(BLOCK_AFF, device=DEV) if affine else None
+    y = m(x, aff)
+    (y.float() * r64.to(DEV, torch.float32)).sum().backward()
+    ty, tx, tp = (1e-3, 1e-3, 5e-3) if dtype == torch.float32 else (3e-2, 3e-2, 5e-2)
+    errs = {"y": _rel(y, y64.numpy()), "dx": _rel(x.grad, dx64.numpy())}
+    perrs = {}
+    for name, p in m.named_parameters():
+        assert p.grad is not None and name in grads, name
+        if name.endswith("rel_pos_bias_affine_lin.bias"):
+            perrs[name] = abs(float(p.grad) - float(grads[name])) / float(grads["attn.relative_position_bias_table"].abs().sum())
+        else:
+            perrs[name] = _rel(p.grad, grads[name].numpy())
+    print(f"[{dtype} {res} ws {ws} affine {affine}]", {k: f"{v:.2e}" for k, v in {**errs, **perrs}.items()})
+    assert errs["y"] < ty and errs["dx"] < tx, errs
+    assert max(perrs.values()) < tp, perrs
 
 
 @pytest.mark.parametrize("tag,vol", [("v24", (24, 24, 24)), ("v20", (20, 20, 20))])
