@@ -559,6 +559,28 @@ int msseg_dice_ce_bwd(const void* logits, long long ld, int dtype, const void* l
                       const float* partial, const float* gscale, void* dlogits, long long ldd, int N, long long S,
                       int C, float smooth_nr, float smooth_dr, msseg_stream_t stream);
 
+/* The same four passes for a loss `kind`; the dice_ce_* entry points above are kind MSSEG_LOSS_DICE_CE.
+ *  MSSEG_LOSS_TVERSKY (MONAI TverskyLoss(to_onehot_y, softmax, alpha, beta), no squared prediction): slot 1 of partial is
+ *    sum p, slot 3 stays 0; loss = mean_{n,c}(1 - (I + snr) / (I + alpha*(P - I) + beta*(T - I) + sdr)); loss[3] =
+ *    (tversky, tversky, 0).
+ *  MSSEG_LOSS_DICE_FOCAL (MONAI DiceFocalLoss(to_onehot_y, softmax, squared_pred), gamma 2, lambdas 1): slot 3 of partial
+ *    is the sum of the SIGMOID focal values of the raw logits (MONAI's FocalLoss does not see the softmax flag), the focal
+ *    term their mean over N*C*S elements; loss[3] = (dice + focal, dice, focal).
+ *  alpha, beta are read by MSSEG_LOSS_TVERSKY only.  hard[] does not depend on the kind. */
+#define MSSEG_LOSS_DICE_CE 0
+#define MSSEG_LOSS_TVERSKY 1
+#define MSSEG_LOSS_DICE_FOCAL 2
+int msseg_seg_loss_partials(const void* logits, long long ld, int dtype, const void* labels, int label_dtype,
+                            float* partial, float* hard, int N, long long S, int C, int kind, msseg_stream_t stream);
+int msseg_seg_loss_fwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype, float* partial,
+                       float* hard, float* loss, int N, long long S, int C, float smooth_nr, float smooth_dr, int kind,
+                       float alpha, float beta, void* scratch, size_t scratch_bytes, msseg_stream_t stream);
+int msseg_seg_loss_finalize(const float* partial, float* loss, int N, long long S, int C, float smooth_nr,
+                            float smooth_dr, int kind, float alpha, float beta, msseg_stream_t stream);
+int msseg_seg_loss_bwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype,
+                       const float* partial, const float* gscale, void* dlogits, long long ldd, int N, long long S,
+                       int C, float smooth_nr, float smooth_dr, int kind, float alpha, float beta, msseg_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Optimiser: fused AdamW over one flat fp32 buffer (torch.optim.AdamW(betas=(0.9,0.95), eps=1e-6) of
  * run_training.py:92-93; decay applies where decay_mask[i] != 0 -- timm add_weight_decay semantics).

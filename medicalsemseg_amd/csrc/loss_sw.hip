@@ -1,10 +1,15 @@
-// Dice + cross-entropy loss (single pass over logits/labels forward, single pass backward), hard Dice
-// metric counts, and the sliding-window gather / blend / normalise kernels.
+// Segmentation losses -- Dice + cross-entropy, Tversky, Dice + focal -- as one pass over logits/labels forward and one
+// pass backward (the loss kind is a compile-time parameter of the same kernels), hard Dice metric counts, and the
+// sliding-window gather / blend / normalise kernels.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
 
 enum { LAB_F32 = 0, LAB_BF16 = 1, LAB_U8 = 2, LAB_I64 = 3 };
+// what slots 1 and 3 of partial[n][c][0..3] hold: (sum p^2, -sum t*log p) | (sum p, unused) | (sum p^2, sum focal)
+enum { KIND_DICE_CE = MSSEG_LOSS_DICE_CE, KIND_TVERSKY = MSSEG_LOSS_TVERSKY, KIND_DICE_FOCAL = MSSEG_LOSS_DICE_FOCAL };
 
 MSSEG_DEVFN int load_label(const void* labels, int label_dtype, long long idx) {
     switch (label_dtype) {
@@ -60,8 +65,30 @@ template <int CMAX> MSSEG_DEVFN void softmax_inplace(float* x, int C, float& lse
     lse = mx + logf(sum);
 }
 
+// Sigmoid focal loss (gamma = 2) of ONE logit x against its one-hot target t, as MONAI's FocalLoss computes it inside
+// DiceFocalLoss (which does not hand its softmax flag on): bce = x - x*t - logsigmoid(x), weight = exp(2 * logsigmoid(z))
+// with z = -x * (2t - 1).  L = log1p(exp(-|x|)) serves both: logsigmoid(v) = min(v, 0) - L for v = +-x.
+MSSEG_DEVFN float focal_value(float x, float t) {
+    const float L = log1pf(expf(-fabsf(x)));
+    const float bce = fmaxf(x, 0.f) - x * t + L;
+    const float z = t > 0.f ? -x : x;
+    return expf(2.f * (fminf(z, 0.f) - L)) * bce;
+}
+
+// d focal_value / d x.  With s = sigmoid(z), b = softplus(z) = bce: f = s^2 * b, df/dz = s^2 * (2 * (1 - s) * b + s),
+// dz/dx = -1 where t = 1 and +1 elsewhere; 1 - s = sigmoid(-z) comes from its own logsigmoid, not from a subtraction.
+MSSEG_DEVFN float focal_grad(float x, float t) {
+    const float L = log1pf(expf(-fabsf(x)));
+    const float z = t > 0.f ? -x : x;
+    const float b = fmaxf(z, 0.f) + L;
+    const float s = expf(fminf(z, 0.f) - L), s1 = expf(fminf(-z, 0.f) - L);
+    const float dz = s * s * (2.f * s1 * b + s);
+    return t > 0.f ? -dz : dz;
+}
+
 // partial[n][c][0..3] += (sum p*t, sum p^2, sum t, -sum t*log p); hard[n][c][0..2] += (|P&T|, |P|, |T|)
-template <typename T, int CMAX>
+// (KIND_TVERSKY: slot 1 is sum p, slot 3 stays 0; KIND_DICE_FOCAL: slot 3 is the sum of the focal values)
+template <typename T, int CMAX, int KIND>
 __global__ __launch_bounds__(256) void dice_ce_partials_kernel(const T* __restrict__ logits, long long ld,
                                                                const void* __restrict__ labels, int label_dtype,
                                                                float* partial, float* hard, long long S, int C,
@@ -95,9 +122,11 @@ __global__ __launch_bounds__(256) void dice_ce_partials_kernel(const T* __restri
             if (c < C) {
                 const float t = (lab == c) ? 1.f : 0.f;
                 acc[c][0] += x[c] * t;
-                acc[c][1] += x[c] * x[c];
+                if constexpr (KIND == KIND_TVERSKY) acc[c][1] += x[c];
+                else acc[c][1] += x[c] * x[c];
                 acc[c][2] += t;
-                acc[c][3] += t * (lse - raw[c]);
+                if constexpr (KIND == KIND_DICE_CE) acc[c][3] += t * (lse - raw[c]);
+                else if constexpr (KIND == KIND_DICE_FOCAL) acc[c][3] += focal_value(raw[c], t);
                 const float pm = (am == c) ? 1.f : 0.f;
                 acc[c][4] += pm * t;
                 acc[c][5] += pm;
@@ -163,26 +192,42 @@ __global__ __launch_bounds__(256) void dice_ce_partials_kernel(const T* __restri
     }
 }
 
-__global__ void dice_ce_finalize_kernel(const float* partial, float* loss, int N, long long S, int C, float snr,
-                                        float sdr) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// loss[0..2] = (total, first term, second term) from the N*C rows of sums at `sums` (`stride` floats apart):
+// (dice + ce, dice, ce) | (tversky, tversky, 0) | (dice + focal, dice, focal); one thread, fixed order
+template <int KIND>
+MSSEG_DEVFN void loss_triple(const float* sums, int stride, float* loss, int N, long long S, int C, float snr, float sdr,
+                             float alpha, float beta) {
     float dice = 0.f, ce = 0.f;
     for (int i = 0; i < N * C; ++i) {
-        const float I = partial[i * 4 + 0], p2 = partial[i * 4 + 1], t = partial[i * 4 + 2];
-        dice += 1.f - (2.f * I + snr) / (p2 + t + sdr);
-        ce += partial[i * 4 + 3];
+        const float I = sums[i * stride + 0], p2 = sums[i * stride + 1], t = sums[i * stride + 2];
+        if constexpr (KIND == KIND_TVERSKY) {   // p2 is sum p here
+            const float fp = alpha * (p2 - I), fn = beta * (t - I);
+            dice += 1.f - (I + snr) / (I + fp + fn + sdr);
+        } else {
+            dice += 1.f - (2.f * I + snr) / (p2 + t + sdr);
+            ce += sums[i * stride + 3];
+        }
     }
     dice /= (float)(N * C);
-    ce /= (float)((double)N * (double)S);
+    if constexpr (KIND == KIND_DICE_CE) ce /= (float)((double)N * (double)S);
+    else if constexpr (KIND == KIND_DICE_FOCAL) ce /= (float)((double)N * (double)C * (double)S);
     loss[0] = dice + ce;
     loss[1] = dice;
     loss[2] = ce;
 }
 
+template <int KIND>
+__global__ void dice_ce_finalize_kernel(const float* partial, float* loss, int N, long long S, int C, float snr,
+                                        float sdr, float alpha, float beta) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    loss_triple<KIND>(partial, 4, loss, N, S, C, snr, sdr, alpha, beta);
+}
+
 // rows [N][nblk][C*7] -> partial[N][C][4], hard[N][C][3] (optional) and the loss triple, one block, fixed order
+template <int KIND>
 __global__ __launch_bounds__(256) void dice_ce_rows_finalize_kernel(const float* rows, int nblk, float* partial, float* hard,
                                                                     float* loss, int N, long long S, int C, float snr,
-                                                                    float sdr) {
+                                                                    float sdr, float alpha, float beta) {
     __shared__ float tot[8 * 16 * 7];
     const int L = C * 7;
     // thread = (column o, row slot): 256 / L' slots per column add every slot-th row, then the slots are added in order
@@ -222,59 +267,64 @@ __global__ __launch_bounds__(256) void dice_ce_rows_finalize_kernel(const float*
         if (k < 4) partial[(n * C + c) * 4 + k] = tot[i];
         else if (hard) hard[(n * C + c) * 3 + (k - 4)] = tot[i];
     }
-    if (threadIdx.x == 0 && loss) {
-        float dice = 0.f, ce = 0.f;
-        for (int i = 0; i < N * C; ++i) {
-            const float I = tot[i * 7 + 0], p2 = tot[i * 7 + 1], t = tot[i * 7 + 2];
-            dice += 1.f - (2.f * I + snr) / (p2 + t + sdr);
-            ce += tot[i * 7 + 3];
-        }
-        dice /= (float)(N * C);
-        ce /= (float)((double)N * (double)S);
-        loss[0] = dice + ce;
-        loss[1] = dice;
-        loss[2] = ce;
-    }
+    if (threadIdx.x == 0 && loss) loss_triple<KIND>(tot, 7, loss, N, S, C, snr, sdr, alpha, beta);
 }
 
-template <typename T, int CMAX>
+template <typename T, int CMAX, int KIND>
 __global__ __launch_bounds__(256) void dice_ce_bwd_kernel(const T* __restrict__ logits, long long ld,
                                                           const void* __restrict__ labels, int label_dtype,
                                                           const float* __restrict__ partial, const float* gscale,
                                                           T* __restrict__ dlogits, long long ldd, int N, long long S,
-                                                          int C, float snr, float sdr) {
+                                                          int C, float snr, float sdr, float alpha, float beta) {
     const long long n = blockIdx.y;
-    // per (n, c) constants of d dice / d p
+    // per (n, c) constants of d dice / d p (d tversky / d p)
     float ka[CMAX], kb[CMAX];
     const float gs = gscale ? gscale[0] : 1.f;
     const float wd = gs / (float)(N * C);
-    const float wc = gs / (float)((double)N * (double)S);
+    // weight of the per-element term: cross-entropy (mean over N*S) or focal (mean over N*C*S)
+    const float wc = gs / (float)(KIND == KIND_DICE_FOCAL ? (double)N * (double)C * (double)S : (double)N * (double)S);
 #pragma unroll
     for (int c = 0; c < CMAX; ++c) {
         ka[c] = kb[c] = 0.f;
         if (c < C) {
             const float I = partial[(n * C + c) * 4 + 0], p2 = partial[(n * C + c) * 4 + 1], t = partial[(n * C + c) * 4 + 2];
-            const float den = p2 + t + sdr, num = 2.f * I + snr;
-            ka[c] = -2.f / den * wd;              // multiplies t
-            kb[c] = 2.f * num / (den * den) * wd;  // multiplies p
+            if constexpr (KIND == KIND_TVERSKY) {
+                // loss = 1 - num / D, D = I + alpha*(P - I) + beta*(T - I) + sdr: d/dp = t * (-1/D + num*(1-alpha-beta)/D^2)
+                // + num*alpha/D^2 (p2 is P here)
+                const float D = I + alpha * (p2 - I) + beta * (t - I) + sdr, num = I + snr;
+                ka[c] = (-1.f / D + num * (1.f - alpha - beta) / (D * D)) * wd;   // multiplies t
+                kb[c] = num * alpha / (D * D) * wd;                                // constant in p
+            } else {
+                const float den = p2 + t + sdr, num = 2.f * I + snr;
+                ka[c] = -2.f / den * wd;              // multiplies t
+                kb[c] = 2.f * num / (den * den) * wd;  // multiplies p
+            }
         }
     }
     const bool vec = ld > 0 && ld * (long long)sizeof(T) == 16 && ldd == ld && C <= DT<T>::EPC &&
                      ((((uintptr_t)logits) | ((uintptr_t)dlogits)) & 15) == 0;
     auto grad = [&](float* x, int lab, float* d) {   // x: logits in, probabilities out; d[c] = d loss / d logit c
+        float raw[CMAX];
+        if constexpr (KIND == KIND_DICE_FOCAL) {
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c) raw[c] = x[c];
+        }
         float lse;
         softmax_inplace<CMAX>(x, C, lse);
         float g[CMAX], dot = 0.f;
 #pragma unroll
         for (int c = 0; c < CMAX; ++c) {
             const float t = (lab == c) ? 1.f : 0.f;
-            g[c] = (c < C) ? (ka[c] * t + kb[c] * x[c]) : 0.f;
+            if constexpr (KIND == KIND_TVERSKY) g[c] = (c < C) ? (ka[c] * t + kb[c]) : 0.f;
+            else g[c] = (c < C) ? (ka[c] * t + kb[c] * x[c]) : 0.f;
             dot += g[c] * x[c];
         }
 #pragma unroll
         for (int c = 0; c < CMAX; ++c) {
             const float t = (lab == c) ? 1.f : 0.f;
-            d[c] = (c < C) ? x[c] * (g[c] - dot) + wc * (x[c] - t) : 0.f;
+            if constexpr (KIND == KIND_DICE_CE) d[c] = (c < C) ? x[c] * (g[c] - dot) + wc * (x[c] - t) : 0.f;
+            else if constexpr (KIND == KIND_TVERSKY) d[c] = (c < C) ? x[c] * (g[c] - dot) : 0.f;
+            else d[c] = (c < C) ? x[c] * (g[c] - dot) + wc * focal_grad(raw[c], t) : 0.f;
         }
     };
     const long long stride = (long long)gridDim.x * 256;
@@ -462,42 +512,57 @@ inline int grid_for(long long total, int per_thread = 4) {
     return (int)b;
 }
 
+// calls f(std::integral_constant<int, KIND>) for a run-time loss kind (checked by the entry points)
+template <typename F> void for_kind(int kind, F&& f) {
+    if (kind == KIND_TVERSKY) f(std::integral_constant<int, KIND_TVERSKY>{});
+    else if (kind == KIND_DICE_FOCAL) f(std::integral_constant<int, KIND_DICE_FOCAL>{});
+    else f(std::integral_constant<int, KIND_DICE_CE>{});
+}
+
 template <typename T, int CMAX>
 int launch_partials(const void* logits, long long ld, const void* labels, int label_dtype, float* partial, float* hard,
-                    int N, long long S, int C, hipStream_t st, float* rows = nullptr, int* nblk_out = nullptr) {
+                    int N, long long S, int C, int kind, hipStream_t st, float* rows = nullptr, int* nblk_out = nullptr) {
     long long blocks = ceil_div_ll(S, 256LL * 8);
     const long long cap = (long long)msseg_num_cus() * 8 / N + 1;
     if (blocks > cap) blocks = cap;
     const long long vpb = ceil_div_ll(S, blocks);
     blocks = ceil_div_ll(S, vpb);
     if (nblk_out) *nblk_out = (int)blocks;
-    hipLaunchKernelGGL((dice_ce_partials_kernel<T, CMAX>), dim3((unsigned)blocks, N), dim3(256), 0, st, (const T*)logits,
-                       ld, labels, label_dtype, partial, hard, S, C, vpb, rows);
+    for_kind(kind, [&](auto k) {
+        hipLaunchKernelGGL((dice_ce_partials_kernel<T, CMAX, decltype(k)::value>), dim3((unsigned)blocks, N), dim3(256), 0, st,
+                           (const T*)logits, ld, labels, label_dtype, partial, hard, S, C, vpb, rows);
+    });
     MSSEG_CHECK_LAUNCH("dice_ce_partials");
     return MSSEG_OK;
 }
 
 template <typename T, int CMAX>
 int launch_fwd(const void* logits, long long ld, const void* labels, int label_dtype, float* partial, float* hard,
-               float* loss, int N, long long S, int C, float snr, float sdr, float* rows, hipStream_t st) {
+               float* loss, int N, long long S, int C, float snr, float sdr, int kind, float alpha, float beta, float* rows,
+               hipStream_t st) {
     int nblk = 0;
-    const int rc = launch_partials<T, CMAX>(logits, ld, labels, label_dtype, partial, hard, N, S, C, st, rows, &nblk);
+    const int rc = launch_partials<T, CMAX>(logits, ld, labels, label_dtype, partial, hard, N, S, C, kind, st, rows, &nblk);
     if (rc) return rc;
-    hipLaunchKernelGGL(dice_ce_rows_finalize_kernel, dim3(1), dim3(256), 0, st, rows, nblk, partial, hard, loss, N, S, C,
-                       snr, sdr);
+    for_kind(kind, [&](auto k) {
+        hipLaunchKernelGGL(dice_ce_rows_finalize_kernel<decltype(k)::value>, dim3(1), dim3(256), 0, st, rows, nblk, partial,
+                           hard, loss, N, S, C, snr, sdr, alpha, beta);
+    });
     MSSEG_CHECK_LAUNCH("dice_ce_rows_finalize");
     return MSSEG_OK;
 }
 
 template <typename T, int CMAX>
 int launch_bwd(const void* logits, long long ld, const void* labels, int label_dtype, const float* partial,
-               const float* gscale, void* dlogits, long long ldd, int N, long long S, int C, float snr, float sdr,
-               hipStream_t st) {
+               const float* gscale, void* dlogits, long long ldd, int N, long long S, int C, float snr, float sdr, int kind,
+               float alpha, float beta, hipStream_t st) {
     long long blocks = ceil_div_ll(S, 256LL * 4);
     const long long cap = (long long)msseg_num_cus() * 16 / N + 1;
     if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL((dice_ce_bwd_kernel<T, CMAX>), dim3((unsigned)blocks, N), dim3(256), 0, st, (const T*)logits, ld,
-                       labels, label_dtype, partial, gscale, (T*)dlogits, ldd, N, S, C, snr, sdr);
+    for_kind(kind, [&](auto k) {
+        hipLaunchKernelGGL((dice_ce_bwd_kernel<T, CMAX, decltype(k)::value>), dim3((unsigned)blocks, N), dim3(256), 0, st,
+                           (const T*)logits, ld, labels, label_dtype, partial, gscale, (T*)dlogits, ldd, N, S, C, snr, sdr,
+                           alpha, beta);
+    });
     MSSEG_CHECK_LAUNCH("dice_ce_bwd");
     return MSSEG_OK;
 }
@@ -520,45 +585,74 @@ int launch_bwd(const void* logits, long long ld, const void* labels, int label_d
 
 extern "C" {
 
+int msseg_seg_loss_partials(const void* logits, long long ld, int dtype, const void* labels, int label_dtype,
+                            float* partial, float* hard, int N, long long S, int C, int kind, msseg_stream_t stream) {
+    if (!logits || !labels || (!partial && !hard) || N < 1 || S < 1 || C < 1 || C > 16 || (ld != 0 && ld < C) ||
+        label_dtype < 0 || label_dtype > 3 || kind < 0 || kind > 2)
+        MSSEG_FAIL(MSSEG_EINVAL, "seg_loss_partials: bad args (C=%d must be 1..16, kind=%d 0..2)", C, kind);
+    DISPATCH_TC(dtype, C, launch_partials, logits, ld, labels, label_dtype, partial, hard, N, S, C, kind,
+                (hipStream_t)stream);
+}
+
+int msseg_seg_loss_fwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype, float* partial,
+                       float* hard, float* loss, int N, long long S, int C, float smooth_nr, float smooth_dr, int kind,
+                       float alpha, float beta, void* scratch, size_t scratch_bytes, msseg_stream_t stream) {
+    if (!logits || !labels || !partial || !loss || N < 1 || N > 8 || S < 1 || C < 1 || C > 16 || (ld != 0 && ld < C) ||
+        label_dtype < 0 || label_dtype > 3 || kind < 0 || kind > 2)
+        MSSEG_FAIL(MSSEG_EINVAL, "seg_loss_fwd: bad args (1 <= N <= 8, 1 <= C <= 16, 0 <= kind <= 2)");
+    const size_t need = MSSEG_SCRATCH_COUNTER_BYTES + (size_t)N * ((size_t)msseg_num_cus() * 8 / N + 2) * C * 7 * 4;
+    if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < need)
+        MSSEG_FAIL(MSSEG_EWORKSPACE, "seg_loss_fwd: scratch of %zu bytes needed", need);
+    float* rows = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
+    DISPATCH_TC(dtype, C, launch_fwd, logits, ld, labels, label_dtype, partial, hard, loss, N, S, C, smooth_nr, smooth_dr,
+                kind, alpha, beta, rows, (hipStream_t)stream);
+}
+
+int msseg_seg_loss_finalize(const float* partial, float* loss, int N, long long S, int C, float smooth_nr,
+                            float smooth_dr, int kind, float alpha, float beta, msseg_stream_t stream) {
+    if (!partial || !loss || N < 1 || S < 1 || C < 1 || kind < 0 || kind > 2)
+        MSSEG_FAIL(MSSEG_EINVAL, "seg_loss_finalize: bad args");
+    for_kind(kind, [&](auto k) {
+        hipLaunchKernelGGL(dice_ce_finalize_kernel<decltype(k)::value>, dim3(1), dim3(64), 0, (hipStream_t)stream, partial,
+                           loss, N, S, C, smooth_nr, smooth_dr, alpha, beta);
+    });
+    MSSEG_CHECK_LAUNCH("seg_loss_finalize");
+    return MSSEG_OK;
+}
+
+int msseg_seg_loss_bwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype,
+                       const float* partial, const float* gscale, void* dlogits, long long ldd, int N, long long S, int C,
+                       float smooth_nr, float smooth_dr, int kind, float alpha, float beta, msseg_stream_t stream) {
+    if (!logits || !labels || !partial || !dlogits || N < 1 || S < 1 || C < 1 || C > 16 || (ld != 0 && ld < C) ||
+        (ldd != 0 && ldd < C) || label_dtype < 0 || label_dtype > 3 || kind < 0 || kind > 2)
+        MSSEG_FAIL(MSSEG_EINVAL, "seg_loss_bwd: bad args");
+    DISPATCH_TC(dtype, C, launch_bwd, logits, ld, labels, label_dtype, partial, gscale, dlogits, ldd, N, S, C, smooth_nr,
+                smooth_dr, kind, alpha, beta, (hipStream_t)stream);
+}
+
+// the Dice + cross-entropy forms of the four entry points above
 int msseg_dice_ce_partials(const void* logits, long long ld, int dtype, const void* labels, int label_dtype,
                            float* partial, float* hard, int N, long long S, int C, msseg_stream_t stream) {
-    if (!logits || !labels || (!partial && !hard) || N < 1 || S < 1 || C < 1 || C > 16 || (ld != 0 && ld < C) ||
-        label_dtype < 0 || label_dtype > 3)
-        MSSEG_FAIL(MSSEG_EINVAL, "dice_ce_partials: bad args (C=%d must be 1..16)", C);
-    DISPATCH_TC(dtype, C, launch_partials, logits, ld, labels, label_dtype, partial, hard, N, S, C, (hipStream_t)stream);
+    return msseg_seg_loss_partials(logits, ld, dtype, labels, label_dtype, partial, hard, N, S, C, MSSEG_LOSS_DICE_CE, stream);
 }
 
 int msseg_dice_ce_fwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype, float* partial,
                       float* hard, float* loss, int N, long long S, int C, float smooth_nr, float smooth_dr, void* scratch,
                       size_t scratch_bytes, msseg_stream_t stream) {
-    if (!logits || !labels || !partial || !loss || N < 1 || N > 8 || S < 1 || C < 1 || C > 16 || (ld != 0 && ld < C) ||
-        label_dtype < 0 || label_dtype > 3)
-        MSSEG_FAIL(MSSEG_EINVAL, "dice_ce_fwd: bad args (1 <= N <= 8, 1 <= C <= 16)");
-    const size_t need = MSSEG_SCRATCH_COUNTER_BYTES + (size_t)N * ((size_t)msseg_num_cus() * 8 / N + 2) * C * 7 * 4;
-    if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < need)
-        MSSEG_FAIL(MSSEG_EWORKSPACE, "dice_ce_fwd: scratch of %zu bytes needed", need);
-    float* rows = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
-    DISPATCH_TC(dtype, C, launch_fwd, logits, ld, labels, label_dtype, partial, hard, loss, N, S, C, smooth_nr, smooth_dr,
-                rows, (hipStream_t)stream);
+    return msseg_seg_loss_fwd(logits, ld, dtype, labels, label_dtype, partial, hard, loss, N, S, C, smooth_nr, smooth_dr,
+                              MSSEG_LOSS_DICE_CE, 0.f, 0.f, scratch, scratch_bytes, stream);
 }
 
 int msseg_dice_ce_finalize(const float* partial, float* loss, int N, long long S, int C, float smooth_nr,
                            float smooth_dr, msseg_stream_t stream) {
-    if (!partial || !loss || N < 1 || S < 1 || C < 1) MSSEG_FAIL(MSSEG_EINVAL, "dice_ce_finalize: bad args");
-    hipLaunchKernelGGL(dice_ce_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partial, loss, N, S, C,
-                       smooth_nr, smooth_dr);
-    MSSEG_CHECK_LAUNCH("dice_ce_finalize");
-    return MSSEG_OK;
+    return msseg_seg_loss_finalize(partial, loss, N, S, C, smooth_nr, smooth_dr, MSSEG_LOSS_DICE_CE, 0.f, 0.f, stream);
 }
 
 int msseg_dice_ce_bwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype,
                       const float* partial, const float* gscale, void* dlogits, long long ldd, int N, long long S, int C,
                       float smooth_nr, float smooth_dr, msseg_stream_t stream) {
-    if (!logits || !labels || !partial || !dlogits || N < 1 || S < 1 || C < 1 || C > 16 || (ld != 0 && ld < C) ||
-        (ldd != 0 && ldd < C) || label_dtype < 0 || label_dtype > 3)
-        MSSEG_FAIL(MSSEG_EINVAL, "dice_ce_bwd: bad args");
-    DISPATCH_TC(dtype, C, launch_bwd, logits, ld, labels, label_dtype, partial, gscale, dlogits, ldd, N, S, C, smooth_nr,
-                smooth_dr, (hipStream_t)stream);
+    return msseg_seg_loss_bwd(logits, ld, dtype, labels, label_dtype, partial, gscale, dlogits, ldd, N, S, C, smooth_nr,
+                              smooth_dr, MSSEG_LOSS_DICE_CE, 0.f, 0.f, stream);
 }
 
 int msseg_sw_normalize(float* out, const float* cnt, int C, long long V, msseg_stream_t stream) {

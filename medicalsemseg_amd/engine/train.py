@@ -76,7 +76,7 @@ class _GraphedFwdBwd:
             self.loss = criterion(self.out, self.y)
             self.loss.backward()
         # the criterion's by-products (hard-Dice counts of THIS graph's static logits): a replay does not run
-        # _DiceCEFn.forward in Python, so they are re-bound after every replay
+        # _SegLossFn.forward in Python, so they are re-bound after every replay
         self.last = dict(getattr(criterion, "last", {}))
         self.criterion = weakref.ref(criterion)
         # two-phase backward (parallel.GradSync): the tail of the backward is its own graph, so the all-reduce of the
@@ -111,7 +111,7 @@ class _GraphedFwdBwd:
 def _graph_ok(model, criterion, optimizer, loss_scaler, inputs, cfg):
     import os
     net = getattr(model, "module", model)
-    return (inputs.is_cuda and getattr(net, "graph_safe", False) and isinstance(criterion, L.DiceCELoss)
+    return (inputs.is_cuda and getattr(net, "graph_safe", False) and isinstance(criterion, (L.DiceCELoss, L.TverskyLoss, L.DiceFocalLoss))
             and hasattr(optimizer, "flat_grad") and not getattr(loss_scaler, "is_enabled", lambda: False)()
             and not bool(getattr(cfg, "anomaly_detection", False)) and not os.environ.get("MSSEG_NO_TRAIN_GRAPH"))
 

@@ -122,6 +122,10 @@ SIGNATURES = {
     "msseg_dice_ce_fwd": ([_vp, _ll, _i, _vp, _i, _vp, _vp, _vp, _i, _ll, _i, _f, _f, _vp, _sz, _vp], _i),
     "msseg_dice_ce_finalize": ([_vp, _vp, _i, _ll, _i, _f, _f, _vp], _i),
     "msseg_dice_ce_bwd": ([_vp, _ll, _i, _vp, _i, _vp, _vp, _vp, _ll, _i, _ll, _i, _f, _f, _vp], _i),
+    "msseg_seg_loss_partials": ([_vp, _ll, _i, _vp, _i, _vp, _vp, _i, _ll, _i, _i, _vp], _i),
+    "msseg_seg_loss_fwd": ([_vp, _ll, _i, _vp, _i, _vp, _vp, _vp, _i, _ll, _i, _f, _f, _i, _f, _f, _vp, _sz, _vp], _i),
+    "msseg_seg_loss_finalize": ([_vp, _vp, _i, _ll, _i, _f, _f, _i, _f, _f, _vp], _i),
+    "msseg_seg_loss_bwd": ([_vp, _ll, _i, _vp, _i, _vp, _vp, _vp, _ll, _i, _ll, _i, _f, _f, _i, _f, _f, _vp], _i),
     "msseg_adamw_step": ([_vp, _vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _f, _i, _vp, _vp, _vp], _i),
     "msseg_sumsq": ([_vp, _ll, _vp, _vp, _i, _vp], _i),
     "msseg_sw_normalize": ([_vp, _vp, _i, _ll, _vp], _i),
@@ -1194,20 +1198,29 @@ def add(a, b, y):
 # --------------------------------------------------------------------------------------------
 # loss / metric
 # --------------------------------------------------------------------------------------------
-def dice_ce_partials(logits, labels, n_cls, channels_last_ld=0, want_hard=False):
-    """logits: NCDHW (channels_last_ld == 0) or channels-last with voxel stride ld.  Returns (partial, hard)."""
+# loss kinds of the seg_loss_* passes (MSSEG_LOSS_* of include/msseg.h); msseg_dice_ce_* are kind LOSS_DICE_CE
+LOSS_DICE_CE, LOSS_TVERSKY, LOSS_DICE_FOCAL = 0, 1, 2
+
+
+def seg_loss_partials(logits, labels, n_cls, kind, channels_last_ld=0, want_hard=False):
+    """atomic partial sums (any N) for a loss kind: slot 1 / slot 3 of partial hold (sum p^2, CE sum) | (sum p, 0) | (sum p^2, focal sum)"""
     _need_gpu(logits, labels)
     N = logits.shape[0]
     S = labels.numel() // N
     partial = torch.zeros(N, n_cls, 4, dtype=torch.float32, device=logits.device)
     hard = torch.zeros(N, n_cls, 3, dtype=torch.float32, device=logits.device) if want_hard else None
-    _ck(lib().msseg_dice_ce_partials(_p(logits), channels_last_ld, dt(logits), _p(labels), _LAB[labels.dtype],
-                                     _p(partial), _p(hard), N, S, n_cls, _stream()), "dice_ce_partials")
+    _ck(lib().msseg_seg_loss_partials(_p(logits), channels_last_ld, dt(logits), _p(labels), _LAB[labels.dtype],
+                                      _p(partial), _p(hard), N, S, n_cls, kind, _stream()), "seg_loss_partials")
     return partial, hard
 
 
-def dice_ce_fwd(logits, labels, n_cls, smooth_nr, smooth_dr, channels_last_ld=0, want_hard=True):
-    """deterministic fused forward: returns (partial [N,C,4], hard [N,C,3] or None, loss3 = (total, dice, ce))"""
+def dice_ce_partials(logits, labels, n_cls, channels_last_ld=0, want_hard=False):
+    """logits: NCDHW (channels_last_ld == 0) or channels-last with voxel stride ld.  Returns (partial, hard)."""
+    return seg_loss_partials(logits, labels, n_cls, LOSS_DICE_CE, channels_last_ld, want_hard)
+
+
+def seg_loss_fwd(logits, labels, n_cls, smooth_nr, smooth_dr, kind, alpha=0.0, beta=0.0, channels_last_ld=0, want_hard=True):
+    """deterministic fused forward (N <= 8): (partial [N,C,4], hard [N,C,3] or None, loss3 = (total, first term, second term))"""
     _need_gpu(logits, labels)
     N = logits.shape[0]
     S = labels.numel() // N
@@ -1215,27 +1228,28 @@ def dice_ce_fwd(logits, labels, n_cls, smooth_nr, smooth_dr, channels_last_ld=0,
     hard = torch.empty(N, n_cls, 3, dtype=torch.float32, device=logits.device) if want_hard else None
     loss = torch.empty(3, dtype=torch.float32, device=logits.device)
     sc = scratch(logits.device)
-    _ck(lib().msseg_dice_ce_fwd(_p(logits), channels_last_ld, dt(logits), _p(labels), _LAB[labels.dtype], _p(partial),
-                                _p(hard), _p(loss), N, S, n_cls, smooth_nr, smooth_dr, _p(sc), sc.numel(), _stream()),
-        "dice_ce_fwd")
+    _ck(lib().msseg_seg_loss_fwd(_p(logits), channels_last_ld, dt(logits), _p(labels), _LAB[labels.dtype], _p(partial),
+                                 _p(hard), _p(loss), N, S, n_cls, smooth_nr, smooth_dr, kind, alpha, beta, _p(sc),
+                                 sc.numel(), _stream()), "seg_loss_fwd")
     return partial, hard, loss
 
 
-def dice_ce_finalize(partial, S, smooth_nr, smooth_dr):
+def seg_loss_finalize(partial, S, smooth_nr, smooth_dr, kind, alpha=0.0, beta=0.0):
     N, Cc = partial.shape[0], partial.shape[1]
     loss = torch.empty(3, dtype=torch.float32, device=partial.device)
-    _ck(lib().msseg_dice_ce_finalize(_p(partial), _p(loss), N, S, Cc, smooth_nr, smooth_dr, _stream()),
-        "dice_ce_finalize")
+    _ck(lib().msseg_seg_loss_finalize(_p(partial), _p(loss), N, S, Cc, smooth_nr, smooth_dr, kind, alpha, beta, _stream()),
+        "seg_loss_finalize")
     return loss
 
 
-def dice_ce_bwd(logits, labels, partial, gscale, dlogits, n_cls, smooth_nr, smooth_dr, ld_in=0, ld_out=0):
+def seg_loss_bwd(logits, labels, partial, gscale, dlogits, n_cls, smooth_nr, smooth_dr, kind, alpha=0.0, beta=0.0, ld_in=0,
+                 ld_out=0):
     _need_gpu(logits, labels, partial, dlogits)
     N = logits.shape[0]
     S = labels.numel() // N
-    _ck(lib().msseg_dice_ce_bwd(_p(logits), ld_in, dt(logits), _p(labels), _LAB[labels.dtype], _p(partial),
-                                _p(gscale), _p(dlogits), ld_out, N, S, n_cls, smooth_nr, smooth_dr, _stream()),
-        "dice_ce_bwd")
+    _ck(lib().msseg_seg_loss_bwd(_p(logits), ld_in, dt(logits), _p(labels), _LAB[labels.dtype], _p(partial), _p(gscale),
+                                 _p(dlogits), ld_out, N, S, n_cls, smooth_nr, smooth_dr, kind, alpha, beta, _stream()),
+        "seg_loss_bwd")
     return dlogits
 
 

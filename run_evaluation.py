@@ -22,7 +22,7 @@ if ROOT not in sys.path:
 
 from medicalsemseg_amd.data import SyntheticLoader
 from medicalsemseg_amd.engine.test import eval_model
-from medicalsemseg_amd.losses import DiceCELoss
+from medicalsemseg_amd.losses import build_criterion
 from medicalsemseg_amd.models.model_builder import build_model
 from medicalsemseg_amd.utils import misc
 from medicalsemseg_amd.utils.arguments import get_args
@@ -38,7 +38,9 @@ def main(cfg):
     model = build_model(cfg).to(device)
     cfg.eval = True
     misc.load_model(cfg, model)                       # weights only: load_state_dict(torch.load(cfg.resume)['model'])
-    criterion = DiceCELoss(to_onehot_y=True, softmax=True, squared_pred=True, smooth_nr=cfg.smooth_nr, smooth_dr=cfg.smooth_dr)
+    # the reference evaluates with DiceCE whatever was trained (its run_evaluation.py:53); here eval/loss is the loss
+    # --loss_fn names (default DiceCE), so it can be read against the training loss
+    criterion = build_criterion(cfg)
     if cfg.synthetic:
         vval = cfg.synthetic_val_size if isinstance(cfg.synthetic_val_size, int) else cfg.synthetic_val_size[0]
         loader = SyntheticLoader(cfg.synthetic_steps, 1, vval, cfg.in_chans, cfg.output_dim, cfg.seed + 7 + misc.get_rank(),

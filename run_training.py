@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Training driver with the reference's flow and flags (``/root/reference/run_training.py:27-190``): distributed
 init -> seeds -> data -> build_model -> AdamW(+timm-style weight-decay groups) -> cosine schedule with linear warm-up
--> resume -> DiceCE -> epochs of train_one_epoch / run_validation with best-mDice and periodic checkpoints.
+-> resume -> criterion (--loss_fn) -> epochs of train_one_epoch / run_validation with best-mDice and periodic checkpoints.
 
 Differences: runs on MI355X through ``medicalsemseg_amd`` (no CPU fallback); without ``--synthetic`` the Decathlon
 data list under ``--data_path/--task/--json_list`` is read, preprocessed on the GPU and cached in HBM
@@ -24,7 +24,7 @@ from medicalsemseg_amd import parallel
 from medicalsemseg_amd.data import SyntheticLoader
 from medicalsemseg_amd.engine.train import train_one_epoch
 from medicalsemseg_amd.engine.val import run_validation
-from medicalsemseg_amd.losses import DiceCELoss
+from medicalsemseg_amd.losses import build_criterion
 from medicalsemseg_amd.models.model_builder import build_model
 from medicalsemseg_amd.optim import FlatAdamW, LinearWarmupCosineAnnealingLR, add_weight_decay
 from medicalsemseg_amd.utils import misc
@@ -124,9 +124,7 @@ def main(cfg):
     loss_scaler = torch.amp.GradScaler("cuda", enabled=False)
     scheduler = LinearWarmupCosineAnnealingLR(optimizer, warmup_epochs=cfg.warmup_epochs, max_epochs=cfg.epochs)
     misc.load_model(cfg, model, optimizer, loss_scaler, scheduler)
-    if cfg.loss_fn != "DiceCE":
-        raise RuntimeError("Could not parse loss function argument (only DiceCE is on the hot path).")
-    criterion = DiceCELoss(to_onehot_y=True, softmax=True, squared_pred=True, smooth_nr=cfg.smooth_nr, smooth_dr=cfg.smooth_dr)
+    criterion = build_criterion(cfg)   # --loss_fn DiceCE | Tversky | DiceFocal
 
     best, best_epoch = 0.0, 0
     start = time.time()
