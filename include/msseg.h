@@ -666,6 +666,23 @@ int msseg_hd_directed_hist(const uint8_t* edges_src, const uint8_t* edges_tgt, i
                            msseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Keep the largest connected component per class (csrc/components.hip): MONAI KeepLargestConnectedComponent(
+ * applied_labels=1..n_classes-1, is_onehot=False, independent=True) on a uint8 label map [D][H][W].
+ * For each class c in 1..n_classes-1 independently: the connected components of lab == c (connectivity 6: face
+ * neighbours; 26: face, edge and corner neighbours; outside the volume counts as background); the component with the most
+ * voxels is kept -- among equal sizes the one whose first voxel in flat [D][H][W] order comes first, scipy's numbering with
+ * argmax(bincount) -- and every other voxel of class c becomes 0.  Class 0 and values >= n_classes (an ignore label such
+ * as 255) are copied unchanged and join no component.
+ * work: 2 * D*H*W int32 (labels, counters; contents undefined afterwards).  stats[c][4] = {number of components, voxels
+ * kept, flat index of the kept component's first voxel (-1: class absent), voxels removed}; row 0 is {0, 0, -1, 0}; 8-byte
+ * aligned.  out == lab (in place) is allowed.  MSSEG_EINVAL for a connectivity other than 6 / 26, n_classes outside 2..64,
+ * null pointers, D*H*W >= 2^31.  Lock-free integer atomics only: bit-identical from run to run.  No host synchronisation,
+ * no device-to-host copy: the caller reads `stats`.
+ * ------------------------------------------------------------------------------------------- */
+int msseg_keep_largest_u8(const uint8_t* lab, int D, int H, int W, int n_classes, int connectivity, int32_t* work,
+                          int32_t* stats, uint8_t* out, msseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Device-side training crop + augmentation (the step right before the path): one gather launch per
  * batch of patches from a volume cached in HBM.  Replaces RandCropByPosNegLabeld + RandFlipd x3 + RandRotate90d +
  * RandShiftIntensityd + RandScaleIntensityd (data/dataset_builder.py:108-193); the random draws arrive in `table`.

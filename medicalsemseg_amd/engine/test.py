@@ -4,7 +4,12 @@ the reference's softmax is monotonic) and resampled to the original grid with ``
 reference's ``resample_3d`` = scipy order-0 zoom, ``utils/misc.py:420-425``); only uint8 maps cross PCIe.  Outputs go
 to the reference's directory layout as NIfTI-1 files (``utils/nifti.py``: nibabel is not available) when the input names
 carry a NIfTI extension, as ``.npy`` otherwise (synthetic loaders).  The Hausdorff-95 meter (``mHdorffDist``, :20,31,48-51,64)
-comes from ``metrics.hausdorff95``: surfaces, exact distances and their histogram on the device."""
+comes from ``metrics.hausdorff95``: surfaces, exact distances and their histogram on the device.
+
+``--post_keep_largest`` (an addition of this build, off by default) runs MONAI ``KeepLargestConnectedComponent`` /
+nnU-Net's post-processing on the arg-max maps on the device (``msseg_keep_largest_u8``, ``--post_connectivity`` 6 or 26):
+``eval_model`` then reports ``ppDice`` and ``ppHdorffDist`` of the filtered maps next to the unchanged meters and saves
+the filtered map; ``test_model`` filters on the model grid, before the resample and before saving."""
 from __future__ import annotations
 
 import os
@@ -23,12 +28,19 @@ def label_map(outputs: torch.Tensor) -> torch.Tensor:
     return hip.argmax_u8(outputs[0].float().contiguous())
 
 
+def keep_largest(seg: torch.Tensor, cfg, return_stats: bool = False):
+    """uint8 [D, H, W] label map -> the map with the largest connected component of every foreground class only"""
+    return hip.keep_largest_u8(seg, cfg.output_dim, int(getattr(cfg, "post_connectivity", 26)), return_stats=return_stats)
+
+
 def eval_model(inferer, model, data_loader, criterion, device, cfg, log_writer=None):
     """`inferer(inputs=..., network=...)` -> logits (MONAI SlidingWindowInferer call convention, engine/test.py:47), or
     None for the built-in sliding window with the validation settings.  Returns {'eval/<meter>': global average}."""
     model.eval()
     metric_logger = misc.MetricLogger(delimiter="  ")
-    for name in ["loss", "mHdorffDist", "mDice"] + ["class" + str(c) + "Dice" for c in range(cfg.output_dim)]:
+    post = bool(getattr(cfg, "post_keep_largest", False))
+    for name in ["loss", "mHdorffDist", "mDice"] + ["class" + str(c) + "Dice" for c in range(cfg.output_dim)] \
+            + (["ppDice", "ppHdorffDist"] if post else []):
         metric_logger.add_meter(name, misc.SmoothedValue(window_size=1, fmt="{value:.6f}"))
     header = "Evaluation starting"
     for data_iter_step, batch in enumerate(metric_logger.log_every(data_loader, 1, header)):
@@ -51,9 +63,18 @@ def eval_model(inferer, model, data_loader, criterion, device, cfg, log_writer=N
         pred_maps = torch.stack([label_map(outputs[b:b + 1]) for b in range(outputs.shape[0])])
         hdorf, _ = metrics.hausdorff_mean(metrics.hausdorff95(pred_maps, labels, cfg.output_dim))
         metric_logger.update(loss=loss.item(), mHdorffDist=hdorf, mDice=mDice.item())
+        if post:
+            # the same two metrics after the clean-up step; the meters above stay those of the unfiltered output
+            pp_maps = torch.stack([keep_largest(m, cfg) for m in pred_maps])
+            pp_dice = torch.cat([metrics.dice_from_maps(pp_maps[b], labels[b], cfg.output_dim)[0]
+                                 for b in range(pp_maps.shape[0])]).cpu()
+            class_means = torch.stack([pp_dice[:, c].nanmean() for c in range(cfg.output_dim)])
+            pp_hdorf, _ = metrics.hausdorff_mean(metrics.hausdorff95(pp_maps, labels, cfg.output_dim))
+            metric_logger.update(ppDice=float(class_means.nanmean()), ppHdorffDist=pp_hdorf)
         if getattr(cfg, "save_eval_output", False) and cfg.output_dir:
             os.makedirs(cfg.output_dir, exist_ok=True)
-            np.save(os.path.join(cfg.output_dir, "pred_" + img_name + ".npy"), label_map(outputs).cpu().numpy())
+            saved = pp_maps[0] if post else label_map(outputs)
+            np.save(os.path.join(cfg.output_dir, "pred_" + img_name + ".npy"), saved.cpu().numpy())
     metric_logger.synchronize_between_processes()
     print("Evaluation averaged stats:", metric_logger.log_all_average())
     return {"eval/" + k: meter.global_avg for k, meter in metric_logger.meters.items()}
@@ -70,6 +91,11 @@ def test_model(model, data_loader, device, cfg, log_writer=None):
             outputs = sliding_window_inference(inputs, aff_xyz, cfg.vol_size, cfg.batch_size_val, model,
                                                overlap=cfg.val_infer_overlap, mode="gaussian", cval=air_cval)
         seg = label_map(outputs)
+        if getattr(cfg, "post_keep_largest", False):
+            seg, stats = keep_largest(seg, cfg, return_stats=True)
+            print("keep largest component, " + img_name + ": " + ", ".join(
+                f"class {c}: {n} components, {kept} kept, {removed} removed"
+                for c, (n, kept, _, removed) in enumerate(stats.cpu().tolist()) if c > 0))
         seg_rs = None
         if getattr(cfg, "t_voxel_spacings", None):
             target = None

@@ -158,6 +158,7 @@ SIGNATURES = {
     "msseg_hd_edges": ([_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "msseg_hd_directed_workspace_bytes": ([_i, _i, _i], _sz),
     "msseg_hd_directed_hist": ([_vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _i, _vp], _i),
+    "msseg_keep_largest_u8": ([_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "msseg_ktimer_enable": ([_i], _i),
     "msseg_ktimer_reset": ([], _i),
     "msseg_ktimer_count": ([], _i),
@@ -1364,6 +1365,27 @@ def hd_directed_hist(edges_src, edges_tgt, cls: int, box, hist: torch.Tensor):
     _ck(lib().msseg_hd_directed_hist(_p(edges_src), _p(edges_tgt), int(cls), D, H, W, b6, _p(ws), ws.numel(), _p(hist),
                                      hist.numel(), _stream()), "hd_directed_hist")
     return hist
+
+
+def keep_largest_u8(lab: torch.Tensor, n_classes: int, connectivity: int = 26, out: Optional[torch.Tensor] = None,
+                    return_stats: bool = False):
+    """uint8 [D, H, W] label map -> the map with only the largest connected component of every class 1..n_classes-1
+    (MONAI KeepLargestConnectedComponent, independent; connectivity 6 or 26; ties: first voxel in flat order); class 0 and
+    values >= n_classes are copied.  out may be lab (in place).  return_stats: also int32 [n_classes, 4] on the device =
+    {components, voxels kept, flat index of the kept component's first voxel (-1: absent), voxels removed}."""
+    _need_gpu(lab, out)
+    assert lab.dtype == torch.uint8 and lab.is_contiguous() and lab.dim() == 3, \
+        "keep_largest_u8: lab must be a contiguous uint8 [D, H, W] tensor"
+    if out is None:
+        out = torch.empty_like(lab)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == lab.shape, \
+        "keep_largest_u8: out must be a contiguous uint8 tensor of lab's shape"
+    D, H, W = lab.shape
+    work = torch.empty(2, lab.numel(), dtype=torch.int32, device=lab.device)
+    stats = torch.empty(max(int(n_classes), 1), 4, dtype=torch.int32, device=lab.device)
+    _ck(lib().msseg_keep_largest_u8(_p(lab), D, H, W, int(n_classes), int(connectivity), _p(work), _p(stats), _p(out),
+                                    _stream()), "keep_largest_u8")
+    return (out, stats) if return_stats else out
 
 
 def aug_crop_batch(img, lab, table, out_img, out_lab, roi):

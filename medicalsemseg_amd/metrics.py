@@ -92,3 +92,19 @@ def hausdorff_mean(hd: np.ndarray):
         per = np.where(nn > 0, f.sum(1) / np.maximum(nn, 1.0), 0.0)
     nb = float((nn > 0).sum())
     return (float(per.sum() / nb) if nb > 0 else 0.0), nb
+
+
+def dice_from_maps(pred_u8: torch.Tensor, label: torch.Tensor, n_classes: int):
+    """hard Dice of one integer label map against one label volume (any shapes with the same voxel count) from the
+    confusion matrix ``bincount(pred * C + label)`` on the tensors' device -> (scores[1, C], not_nans[1, C]) with the nan
+    convention of ``losses.dice_metric``: NaN where the label lacks the class.  Voxels whose prediction or label is not a
+    class (an ignore value) are left out.  Not a hot path: one pass over a uint8 map per evaluated volume."""
+    C = int(n_classes)
+    p = pred_u8.reshape(-1).long()
+    t = label.reshape(-1).long()
+    assert p.numel() == t.numel(), "prediction and label differ in voxel count"
+    ok = (p >= 0) & (p < C) & (t >= 0) & (t < C)
+    conf = torch.bincount(p[ok] * C + t[ok], minlength=C * C).view(C, C).float()      # [pred][label]
+    inter, np_, nt = conf.diagonal(), conf.sum(1), conf.sum(0)
+    score = torch.where(nt > 0, 2.0 * inter / (np_ + nt), torch.full_like(inter, float("nan")))[None]
+    return score, (~torch.isnan(score)).float()

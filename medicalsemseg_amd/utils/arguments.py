@@ -8,7 +8,8 @@ from __future__ import annotations
 import argparse
 
 S, I, F = str, int, float
-# (flag, kind, default, type)   kind: v = value, l = list (nargs='*'), t = store_true, f = store_false(dest)
+# (flag, kind, default, type)   kind: v = value, l = list (nargs='*'), t = store_true, f = store_false(dest),
+#                               c = value out of the choices in a fifth field
 _SPEC = {
     "model": [
         ("--model", "v", "UNETR_Official", S), ("--vol_size", "l", [96], I), ("--patch_size", "l", [16], I),
@@ -59,6 +60,8 @@ _SPEC = {
     "amd": [  # additions of this build
         ("--synthetic", "t"), ("--synthetic_steps", "v", 8, I), ("--synthetic_val_size", "l", [128], I),
         ("--compute_dtype", "v", "bf16", S), ("--flat_optimizer", "t"),
+        # post-processing of the predicted label maps (engine/test.py): keep the largest connected component per class
+        ("--post_keep_largest", "t"), ("--post_connectivity", "c", 26, I, (6, 26)),
     ],
 }
 
@@ -71,6 +74,8 @@ def build_parser() -> argparse.ArgumentParser:
             flag, kind = spec[0], spec[1]
             if kind == "v":
                 g.add_argument(flag, default=spec[2], type=spec[3])
+            elif kind == "c":
+                g.add_argument(flag, default=spec[2], type=spec[3], choices=spec[4])
             elif kind == "l":
                 g.add_argument(flag, nargs="*", default=list(spec[2]), type=spec[3])
             elif kind == "t":

@@ -7,6 +7,7 @@ gaussian blending).  Data: the validation list of the Decathlon data list (devic
 ``medicalsemseg_amd/data_device.py``), or ``--synthetic`` volumes.
 
     python run_evaluation.py --synthetic --model UNet --output_dim 3 --vol_size 96 --resume out/best_model.pth
+    python run_evaluation.py ... --post_keep_largest    # adds ppDice / ppHdorffDist of the largest-component maps
 """
 from __future__ import annotations
 
