@@ -683,6 +683,32 @@ int msseg_keep_largest_u8(const uint8_t* lab, int D, int H, int W, int n_classes
                           int32_t* stats, uint8_t* out, msseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Post-processing of a uint8 label map [D][H][W] (csrc/components.hip): up to three steps, always in this order, each
+ * optional.  Semantics pinned to scipy (tests/postproc_ref.py); parity with MONAI unpinned.
+ *  1 remove small components (MONAI RemoveSmallObjects, nnU-Net): min_size = N; 0 and 1 switch the step off.  Each class c
+ *    in 1..n_classes-1 is labelled independently with `connectivity` (6 or 26); every component with fewer than N voxels
+ *    becomes 0.
+ *  2 keep the largest component per class (keep_largest != 0): msseg_keep_largest_u8's rule on what step 1 left -- the same
+ *    labelling and sizes serve both; a class whose largest component is below N ends up empty.
+ *  3 fill holes (fill_holes != 0; MONAI FillHoles): for c = 1, 2, .., n_classes-1 in this order, each on the map the class
+ *    before left, every voxel that cannot be reached from outside the volume through voxels != c becomes c
+ *    (out[scipy.ndimage.binary_fill_holes(out == c, structure)] = c).  `hole_connectivity` (6 or 26) is the neighbourhood of
+ *    the leak path: a diagonal gap in a wall leaks at 26 and not at 6.  Enclosed voxels of other classes and of values >=
+ *    n_classes are overwritten; a region that touches one of the six volume faces is no hole.  One labelling of the
+ *    complement per foreground class.
+ * In steps 1 and 2 class 0 and values >= n_classes are copied and join nothing.  With all three steps off the call is a copy.
+ * work: 2 * D*H*W int32 (contents undefined afterwards).  stats[c][6], 8-byte aligned, row 0 all zero = {components before
+ * any step (-1 when neither step 1 nor step 2 is on: the classes are then not labelled), components removed as small, voxels
+ * removed as small, voxels removed by keep-largest, voxels turned into c by its fill step, voxels of class c in the final
+ * map}.  out == lab (in place) is allowed.  MSSEG_EINVAL for a connectivity or hole connectivity other than 6 / 26 (checked
+ * whether or not the step is on), n_classes outside 2..64, a negative min_size, null or misaligned pointers, D*H*W >= 2^31.
+ * Lock-free integer atomics only: bit-identical from run to run.  No host synchronisation: the caller reads `stats`.
+ * ------------------------------------------------------------------------------------------- */
+int msseg_postprocess_u8(const uint8_t* lab, int D, int H, int W, int n_classes, int min_size, int keep_largest,
+                         int connectivity, int fill_holes, int hole_connectivity, int32_t* work, int32_t* stats,
+                         uint8_t* out, msseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Device-side training crop + augmentation (the step right before the path): one gather launch per
  * batch of patches from a volume cached in HBM.  Replaces RandCropByPosNegLabeld + RandFlipd x3 + RandRotate90d +
  * RandShiftIntensityd + RandScaleIntensityd (data/dataset_builder.py:108-193); the random draws arrive in `table`.

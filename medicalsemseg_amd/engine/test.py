@@ -6,10 +6,14 @@ to the reference's directory layout as NIfTI-1 files (``utils/nifti.py``: nibabe
 carry a NIfTI extension, as ``.npy`` otherwise (synthetic loaders).  The Hausdorff-95 meter (``mHdorffDist``, :20,31,48-51,64)
 comes from ``metrics.hausdorff95``: surfaces, exact distances and their histogram on the device.
 
-``--post_keep_largest`` (an addition of this build, off by default) runs MONAI ``KeepLargestConnectedComponent`` /
-nnU-Net's post-processing on the arg-max maps on the device (``msseg_keep_largest_u8``, ``--post_connectivity`` 6 or 26):
-``eval_model`` then reports ``ppDice`` and ``ppHdorffDist`` of the filtered maps next to the unchanged meters and saves
-the filtered map; ``test_model`` filters on the model grid, before the resample and before saving."""
+Post-processing of the arg-max maps (an addition of this build, off by default) runs on the device in one call
+(``msseg_postprocess_u8``), in this order: ``--post_min_size N`` drops components below N voxels (MONAI
+``RemoveSmallObjects``, nnU-Net), ``--post_keep_largest`` keeps the largest component per class (MONAI
+``KeepLargestConnectedComponent``; both with ``--post_connectivity`` 6 or 26), ``--post_fill_holes`` fills the holes of
+class 1, 2, .. (MONAI ``FillHoles``, ``--post_hole_connectivity`` 6 or 26).  Any of the three switches it on:
+``eval_model`` then reports ``ppDice`` and ``ppHdorffDist`` of the processed maps next to the unchanged meters and saves
+the processed map; ``test_model`` processes on the model grid, before the resample and before saving; ``run_validation``
+(engine/val.py) adds ``ppDice``."""
 from __future__ import annotations
 
 import os
@@ -28,9 +32,45 @@ def label_map(outputs: torch.Tensor) -> torch.Tensor:
     return hip.argmax_u8(outputs[0].float().contiguous())
 
 
-def keep_largest(seg: torch.Tensor, cfg, return_stats: bool = False):
-    """uint8 [D, H, W] label map -> the map with the largest connected component of every foreground class only"""
-    return hip.keep_largest_u8(seg, cfg.output_dim, int(getattr(cfg, "post_connectivity", 26)), return_stats=return_stats)
+def post_enabled(cfg) -> bool:
+    """any post-processing flag is set"""
+    return bool(getattr(cfg, "post_keep_largest", False)) or int(getattr(cfg, "post_min_size", 0)) > 1 \
+        or bool(getattr(cfg, "post_fill_holes", False))
+
+
+def postprocess(seg: torch.Tensor, cfg, return_stats: bool = False):
+    """uint8 [D, H, W] label map -> the map after the steps the --post_* flags ask for (hip.postprocess_u8)"""
+    return hip.postprocess_u8(seg, cfg.output_dim, min_size=int(getattr(cfg, "post_min_size", 0)),
+                              keep_largest=bool(getattr(cfg, "post_keep_largest", False)),
+                              connectivity=int(getattr(cfg, "post_connectivity", 26)),
+                              fill_holes=bool(getattr(cfg, "post_fill_holes", False)),
+                              hole_connectivity=int(getattr(cfg, "post_hole_connectivity", 26)), return_stats=return_stats)
+
+
+def dice_of_maps(maps: torch.Tensor, labels: torch.Tensor, n_classes: int) -> float:
+    """hard Dice of uint8 maps [B, D, H, W] against labels [B, 1, D, H, W]: per class the mean over the volumes that hold
+    it, then the mean over the classes"""
+    dice = torch.cat([metrics.dice_from_maps(maps[b], labels[b], n_classes)[0] for b in range(maps.shape[0])]).cpu()
+    return float(torch.stack([dice[:, c].nanmean() for c in range(n_classes)]).nanmean())
+
+
+def _stats_line(stats, cfg) -> str:
+    """the per-class counts of postprocess()' stats; with --post_keep_largest alone, the line of earlier builds"""
+    min_size = int(getattr(cfg, "post_min_size", 0))
+    largest, fill = bool(getattr(cfg, "post_keep_largest", False)), bool(getattr(cfg, "post_fill_holes", False))
+    rows = []
+    for c, (n, small_n, small_vox, removed, filled, final) in enumerate(stats.cpu().tolist()):
+        if c == 0:
+            continue
+        parts = [f"{n} components"] if n >= 0 else []
+        if min_size > 1:
+            parts.append(f"{small_n} below {min_size} voxels removed ({small_vox} voxels)")
+        if largest:                                   # without the fill step the class holds what was kept
+            parts.append(f"{removed} removed" if fill else f"{final} kept, {removed} removed")
+        if fill:
+            parts.append(f"{filled} filled, {final} voxels")
+        rows.append(f"class {c}: " + ", ".join(parts))
+    return ", ".join(rows)
 
 
 def eval_model(inferer, model, data_loader, criterion, device, cfg, log_writer=None):
@@ -38,7 +78,7 @@ def eval_model(inferer, model, data_loader, criterion, device, cfg, log_writer=N
     None for the built-in sliding window with the validation settings.  Returns {'eval/<meter>': global average}."""
     model.eval()
     metric_logger = misc.MetricLogger(delimiter="  ")
-    post = bool(getattr(cfg, "post_keep_largest", False))
+    post = post_enabled(cfg)
     for name in ["loss", "mHdorffDist", "mDice"] + ["class" + str(c) + "Dice" for c in range(cfg.output_dim)] \
             + (["ppDice", "ppHdorffDist"] if post else []):
         metric_logger.add_meter(name, misc.SmoothedValue(window_size=1, fmt="{value:.6f}"))
@@ -65,12 +105,9 @@ def eval_model(inferer, model, data_loader, criterion, device, cfg, log_writer=N
         metric_logger.update(loss=loss.item(), mHdorffDist=hdorf, mDice=mDice.item())
         if post:
             # the same two metrics after the clean-up step; the meters above stay those of the unfiltered output
-            pp_maps = torch.stack([keep_largest(m, cfg) for m in pred_maps])
-            pp_dice = torch.cat([metrics.dice_from_maps(pp_maps[b], labels[b], cfg.output_dim)[0]
-                                 for b in range(pp_maps.shape[0])]).cpu()
-            class_means = torch.stack([pp_dice[:, c].nanmean() for c in range(cfg.output_dim)])
+            pp_maps = torch.stack([postprocess(m, cfg) for m in pred_maps])
             pp_hdorf, _ = metrics.hausdorff_mean(metrics.hausdorff95(pp_maps, labels, cfg.output_dim))
-            metric_logger.update(ppDice=float(class_means.nanmean()), ppHdorffDist=pp_hdorf)
+            metric_logger.update(ppDice=dice_of_maps(pp_maps, labels, cfg.output_dim), ppHdorffDist=pp_hdorf)
         if getattr(cfg, "save_eval_output", False) and cfg.output_dir:
             os.makedirs(cfg.output_dir, exist_ok=True)
             saved = pp_maps[0] if post else label_map(outputs)
@@ -91,11 +128,11 @@ def test_model(model, data_loader, device, cfg, log_writer=None):
             outputs = sliding_window_inference(inputs, aff_xyz, cfg.vol_size, cfg.batch_size_val, model,
                                                overlap=cfg.val_infer_overlap, mode="gaussian", cval=air_cval)
         seg = label_map(outputs)
-        if getattr(cfg, "post_keep_largest", False):
-            seg, stats = keep_largest(seg, cfg, return_stats=True)
-            print("keep largest component, " + img_name + ": " + ", ".join(
-                f"class {c}: {n} components, {kept} kept, {removed} removed"
-                for c, (n, kept, _, removed) in enumerate(stats.cpu().tolist()) if c > 0))
+        if post_enabled(cfg):
+            only_largest = not (int(getattr(cfg, "post_min_size", 0)) > 1 or getattr(cfg, "post_fill_holes", False))
+            seg, stats = postprocess(seg, cfg, return_stats=True)
+            print(("keep largest component, " if only_largest else "post-processing, ") + img_name + ": "
+                  + _stats_line(stats, cfg))
         seg_rs = None
         if getattr(cfg, "t_voxel_spacings", None):
             target = None

@@ -1,4 +1,5 @@
-"""Validation with sliding-window inference: mirror of ``/root/reference/engine/val.py:15-110``."""
+"""Validation with sliding-window inference: mirror of ``/root/reference/engine/val.py:15-110``.  With a ``--post_*`` flag
+(engine/test.py) it also reports ``ppDice``: the hard Dice of the post-processed arg-max map, as ``eval_model`` does."""
 from __future__ import annotations
 
 import math
@@ -7,6 +8,7 @@ import sys
 import torch
 
 from ..utils import misc
+from .test import dice_of_maps, label_map, post_enabled, postprocess
 from .train import _metric_update
 from .utils import sliding_window_inference
 
@@ -14,7 +16,8 @@ from .utils import sliding_window_inference
 def run_validation(model, data_loader, criterion, device, epoch, cfg, log_writer=None, inferer=sliding_window_inference):
     model.eval()
     metric_logger = misc.MetricLogger(delimiter="  ")
-    for name in ["loss", "mDice"] + ["class" + str(c) + "Dice" for c in range(cfg.output_dim)]:
+    post = post_enabled(cfg)
+    for name in ["loss", "mDice"] + ["class" + str(c) + "Dice" for c in range(cfg.output_dim)] + (["ppDice"] if post else []):
         metric_logger.add_meter(name, misc.SmoothedValue(window_size=100, fmt="{value:.6f}"))
     header = "Validation for epoch: [{}]".format(epoch)
     air_cval = (0.0 - cfg.t_norm_mean) / cfg.t_norm_std if cfg.t_normalize else 0.0
@@ -35,6 +38,9 @@ def run_validation(model, data_loader, criterion, device, epoch, cfg, log_writer
         mDice = _metric_update(metric_logger, criterion, outputs, labels, cfg.output_dim)
         metric_logger.update(loss=loss_value)
         metric_logger.update(mDice=mDice.item())
+        if post:
+            pp_maps = torch.stack([postprocess(label_map(outputs[b:b + 1]), cfg) for b in range(outputs.shape[0])])
+            metric_logger.update(ppDice=dice_of_maps(pp_maps, labels, cfg.output_dim))
         loss_value_reduce = misc.all_reduce_mean(loss_value)
         if log_writer is not None:
             epoch_1000x = int((data_iter_step / len(data_loader) + epoch) * 1000)

@@ -159,6 +159,7 @@ SIGNATURES = {
     "msseg_hd_directed_workspace_bytes": ([_i, _i, _i], _sz),
     "msseg_hd_directed_hist": ([_vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _i, _vp], _i),
     "msseg_keep_largest_u8": ([_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "msseg_postprocess_u8": ([_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "msseg_ktimer_enable": ([_i], _i),
     "msseg_ktimer_reset": ([], _i),
     "msseg_ktimer_count": ([], _i),
@@ -1385,6 +1386,32 @@ def keep_largest_u8(lab: torch.Tensor, n_classes: int, connectivity: int = 26, o
     stats = torch.empty(max(int(n_classes), 1), 4, dtype=torch.int32, device=lab.device)
     _ck(lib().msseg_keep_largest_u8(_p(lab), D, H, W, int(n_classes), int(connectivity), _p(work), _p(stats), _p(out),
                                     _stream()), "keep_largest_u8")
+    return (out, stats) if return_stats else out
+
+
+def postprocess_u8(lab: torch.Tensor, n_classes: int, min_size: int = 0, keep_largest: bool = False, connectivity: int = 26,
+                   fill_holes: bool = False, hole_connectivity: int = 26, out: Optional[torch.Tensor] = None,
+                   return_stats: bool = False):
+    """uint8 [D, H, W] label map -> the map after up to three steps, in this order: components of a class 1..n_classes-1
+    with fewer than min_size voxels become 0 (0, 1: off); only the largest component of every class stays (keep_largest,
+    keep_largest_u8's rule; both steps label with `connectivity`); holes of class 1, 2, .. are filled in that order
+    (fill_holes: scipy binary_fill_holes per class, `hole_connectivity` is that of the leak path).  With all steps off: a
+    copy.  out may be lab (in place).  return_stats: also int32 [n_classes, 6] on the device = {components before any step
+    (-1 when neither of the first two steps is on), components removed as small, voxels removed as small, voxels removed
+    by keep-largest, voxels filled, voxels of the class in the result}."""
+    _need_gpu(lab, out)
+    assert lab.dtype == torch.uint8 and lab.is_contiguous() and lab.dim() == 3, \
+        "postprocess_u8: lab must be a contiguous uint8 [D, H, W] tensor"
+    if out is None:
+        out = torch.empty_like(lab)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == lab.shape, \
+        "postprocess_u8: out must be a contiguous uint8 tensor of lab's shape"
+    D, H, W = lab.shape
+    work = torch.empty(2, lab.numel(), dtype=torch.int32, device=lab.device)
+    stats = torch.empty(max(int(n_classes), 1), 6, dtype=torch.int32, device=lab.device)
+    _ck(lib().msseg_postprocess_u8(_p(lab), D, H, W, int(n_classes), int(min_size), int(bool(keep_largest)), int(connectivity),
+                                   int(bool(fill_holes)), int(hole_connectivity), _p(work), _p(stats), _p(out), _stream()),
+        "postprocess_u8")
     return (out, stats) if return_stats else out
 
 

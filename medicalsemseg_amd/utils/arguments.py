@@ -60,8 +60,10 @@ _SPEC = {
     "amd": [  # additions of this build
         ("--synthetic", "t"), ("--synthetic_steps", "v", 8, I), ("--synthetic_val_size", "l", [128], I),
         ("--compute_dtype", "v", "bf16", S), ("--flat_optimizer", "t"),
-        # post-processing of the predicted label maps (engine/test.py): keep the largest connected component per class
+        # post-processing of the predicted label maps (engine/test.py), in this order: drop components below N voxels, keep
+        # the largest connected component per class, fill the holes of every class; any of them switches it on
         ("--post_keep_largest", "t"), ("--post_connectivity", "c", 26, I, (6, 26)),
+        ("--post_min_size", "v", 0, I), ("--post_fill_holes", "t"), ("--post_hole_connectivity", "c", 26, I, (6, 26)),
     ],
 }
 

@@ -8,6 +8,7 @@ gaussian blending).  Data: the validation list of the Decathlon data list (devic
 
     python run_evaluation.py --synthetic --model UNet --output_dim 3 --vol_size 96 --resume out/best_model.pth
     python run_evaluation.py ... --post_keep_largest    # adds ppDice / ppHdorffDist of the largest-component maps
+    python run_evaluation.py ... --post_min_size 64 --post_fill_holes    # the same two meters after those steps
 """
 from __future__ import annotations
 
