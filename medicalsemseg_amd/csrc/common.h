@@ -88,6 +88,33 @@ template <> MSSEG_DEVFN void mma_chunk<float>(f32x4_t& acc, const u32x4_t& a, co
     for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], bf[j], acc, 0, 0, 0);
 }
 
+// ---- operand fetches shared by the MFMA kernels ------------------------------------------------------
+MSSEG_DEVFN u32x4_t ldg16(const void* p) { return *(const u32x4_t*)p; }
+
+// byte offset, in a bf16 msseg_pack_weights image (T = 1) with nkb k-blocks and cout block width cb, of the 16-byte piece that
+// lane quarter q holds of image row `row` of cout block blk in k-block kb: a lane's A fragment for mma_chunk<bf16_t>
+MSSEG_DEVFN long long wimg_frag_off(int blk, int nkb, int kb, int q, int cb, int row) {
+    return ((((long long)blk * nkb + kb) * 4 + q) * cb + row) * 16;
+}
+MSSEG_DEVFN long long wimg_kblock_bytes(int cb) { return (long long)4 * cb * 16; }   // from a fragment to the next k-block's
+
+// transposing LDS reads (memory holds rows of the contraction index, 16-bit elements): two of them make the fragment of a
+// 32-deep k-step for one 16-channel tile; r0 / r1 are the byte offsets of the lane's two rows from base
+MSSEG_DEVFN bf16x4_t lds_tr_read(const unsigned char* p) {
+    return __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+        (__attribute__((address_space(3))) bf16x4_t*)(uintptr_t)(uint32_t)(uintptr_t)p);
+}
+MSSEG_DEVFN u32x4_t tr_frag(const unsigned char* base, int r0, int r1) {
+    const bf16x4_t lo = lds_tr_read(base + r0), hi = lds_tr_read(base + r1);
+    const bf16x8_t f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(u32x4_t, f);
+}
+
+// bf16 operands a [.., lda >= ca] and b [.., ldb >= cb] that 16-byte vector accesses can walk row by row
+static inline bool msseg_aligned_bf16(int dtype, const void* a, long long lda, int ca, const void* b, long long ldb, int cb) {
+    return dtype == MSSEG_BF16 && !((lda % 8) || (ldb % 8) || ((uintptr_t)a & 15) || ((uintptr_t)b & 15) || lda < ca || ldb < cb);
+}
+
 // store 4 consecutive channel values
 template <typename T> MSSEG_DEVFN void store4(T* p, const f32x4_t& v);
 template <> MSSEG_DEVFN void store4<float>(float* p, const f32x4_t& v) { *(f32x4_t*)p = v; }

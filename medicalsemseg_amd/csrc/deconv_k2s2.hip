@@ -36,7 +36,6 @@ struct Dc2Params {
     float* bias_ws;                    // partial rows [gx * N][Cout]
 };
 
-MSSEG_DEVFN u32x4_t ldg16(const void* p) { return *(const u32x4_t*)p; }
 
 // ---------------------------------------------------------------------------------------------------------
 // forward
@@ -64,7 +63,7 @@ __global__ __launch_bounds__(DC_THREADS, 2) void deconv2_fwd_kernel(const Dc2Par
             for (int k = 0; k < KS; ++k) {
                 const int m0 = abc * COUT + j * 16;
                 const int cb = m0 >> 5, row = (m0 & 31) + r;
-                af[abc][j][k] = ldg16((const unsigned char*)p.wp + ((((long long)cb * KS + k) * 4 + q) * 32 + row) * 16);
+                af[abc][j][k] = ldg16((const unsigned char*)p.wp + wimg_frag_off(cb, KS, k, q, 32, row));
             }
     f32x4_t bv[NH];
 #pragma unroll
@@ -137,7 +136,7 @@ __global__ __launch_bounds__(DC_THREADS, 2) void deconv2_bwd_kernel(const Dc2Par
         for (int kb = 0; kb < NKB; ++kb) {
             const int m0 = jt * 16;
             const int cb = m0 >> 5, row = (m0 & 31) + r;
-            af[jt][kb] = ldg16((const unsigned char*)p.wp + ((((long long)cb * NKB + kb) * 4 + q) * 32 + row) * 16);
+            af[jt][kb] = ldg16((const unsigned char*)p.wp + wimg_frag_off(cb, NKB, kb, q, 32, row));
         }
     float s1[NH][4], s2[NH][4], bs[KC][8];
 #pragma unroll
@@ -266,9 +265,8 @@ int grid_x(long long groups) {
 // ---- host interface (igemm_fwd.hip dispatches here when eligible) ----------------------------------------
 bool msseg_deconv2_fast_eligible(int dtype, int Cin, int Cout, const void* coarse, long long ldc, const void* fine,
                                  long long ldf, const float* bias) {
-    if (dtype != MSSEG_BF16) return false;
     if (!((Cin == 32 || Cin == 64) && Cout == 32)) return false;   // weight fragments must fit the register file
-    if ((ldc % 8) || (ldf % 8) || ((uintptr_t)coarse & 15) || ((uintptr_t)fine & 15)) return false;
+    if (!msseg_aligned_bf16(dtype, coarse, ldc, Cin, fine, ldf, Cout)) return false;
     if (bias && ((uintptr_t)bias & 15)) return false;
     return true;
 }

@@ -8,123 +8,27 @@
 // Same scheme as deconv_k2s2.hip / linear_regw.hip -- a wave takes 16 coarse voxels, its B operand comes straight from
 // global memory (a channels-last row IS the operand layout), the weights it needs live in registers -- with the output
 // sliced over grid.y so that any channel count fits the register file:
-//   forward   slice = (fine row pair ab, cout slice): the two children (ab, c = 0 / 1) of 16 coarse voxels form ONE fine row
-//             segment of 32 voxels, transposed through a wave-private LDS tile into coalesced 16-byte stores.
+//   forward   deconv_sliced_fwd_kernel<S = 2> (deconv_sliced.h, shared with k4 s4): slice = (fine row pair ab, cout slice): the
+//             two children (ab, c = 0 / 1) of 16 coarse voxels form ONE fine row segment of 32 voxels, transposed through a
+//             wave-private LDS tile into coalesced 16-byte stores.
 //   backward  dx[v][ci] = sum over the 8 children and Cout: K = 8 * Cout is split over the FOUR WAVES of a workgroup (every
 //             wave gathers its k-steps from the child rows -- a 16-byte chunk never straddles two children), the partial
 //             tiles meet in LDS in a fixed order (deterministic); slice = Cin tiles.  Output: bf16 dx, or the fp32 block
 //             layout of the small-grid finish kernels (conv3d_k3_small.hip: [Cin / 4][voxel][4]), whose k3s_bwd_unit_kernel
 //             then runs the receiving conv + InstanceNorm + LeakyReLU unit's whole backward in one launch.
 // Bound: HBM on the 96^3 / 48^3 outputs (8x the input voxels written / read once), launch latency below.
+#include "deconv_sliced.h"
 #include "k3pp.h"
 
 namespace {
 
 constexpr int DG_THREADS = 256;
 
-struct DcgParams {
-    const void* x; long long ldx;      // coarse [N, D, H, W, Cin]   (forward input / backward output dx)
-    const void* wp;                    // packed image (forward: M = 8*Cout, K = Cin; backward: M = Cin, K = 8*Cout)
-    const float* bias;
-    void* y; long long ldy;            // fine [N, 2D, 2H, 2W, Cout] (forward output / backward input dy)
-    int N, D, H, W, Cin, Cout;
-    int cb;                            // cout block width of the image
-    float* part;                       // backward: fp32 [Cin / 4][N*D*H*W][4] instead of bf16 dx
-};
-
-MSSEG_DEVFN u32x4_t ldg16(const void* p) { return *(const u32x4_t*)p; }
-
-// ---------------------------------------------------------------------------------------------------------
-// forward
-// ---------------------------------------------------------------------------------------------------------
-template <int KS, int NH, int CH>   // KS = ceil(Cin / 32) k-steps, NH cout tiles per slice, CH children per slice (2 or 1)
-__global__ __launch_bounds__(DG_THREADS, 2) void dcg_fwd_kernel(const DcgParams p) {
-    constexpr int CS = NH * 16;                         // channels of a slice
-    constexpr int RSB = CS * 2 + 16;                    // LDS bytes per fine voxel (16-byte pad: fewer write conflicts)
-    constexpr int FV = 16 * CH;                         // fine voxels of a segment that this slice writes
-    constexpr int TILE_B = FV * RSB;
-    constexpr int CPV = CS * 2 / 16;                    // 16-byte chunks per fine voxel
-    __shared__ __attribute__((aligned(16))) unsigned char lds[4 * TILE_B];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 15, q = lane >> 4;
-    unsigned char* tile = lds + wave * TILE_B;
-    const bf16_t* __restrict__ xg = (const bf16_t*)p.x;
-    const int nsl = p.Cout / CS;
-    const int cg = blockIdx.y / nsl, js = blockIdx.y - cg * nsl;
-    const int abc0 = cg * CH;                           // first child of the slice; CH == 2: (abc0, abc0 + 1) share a fine row
-    const int cbase = js * CS;
-    bf16_t* __restrict__ yg = (bf16_t*)p.y + cbase;
-
-    u32x4_t af[CH][NH][KS];
-#pragma unroll
-    for (int c = 0; c < CH; ++c)
-#pragma unroll
-        for (int j = 0; j < NH; ++j)
-#pragma unroll
-            for (int k = 0; k < KS; ++k) {
-                const int m0 = (abc0 + c) * p.Cout + cbase + j * 16;
-                const int blk = m0 / p.cb, row = m0 - blk * p.cb + r;
-                af[c][j][k] = ldg16((const unsigned char*)p.wp + ((((long long)blk * KS + k) * 4 + q) * p.cb + row) * 16);
-            }
-    f32x4_t bv[NH];
-#pragma unroll
-    for (int j = 0; j < NH; ++j) {
-        bv[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        if (p.bias) bv[j] = *(const f32x4_t*)(p.bias + cbase + j * 16 + q * 4);
-    }
-    bool kok[KS];                                       // this lane's chunk of k-step k lies inside the row
-#pragma unroll
-    for (int k = 0; k < KS; ++k) kok[k] = k * 32 + q * 8 < p.Cin;
-
-    const int GW = (p.W + 15) >> 4;
-    const long long groups = (long long)p.N * p.D * p.H * GW;
-    const long long wstride = (long long)gridDim.x * 4;
-    for (long long g = (long long)blockIdx.x * 4 + wave; g < groups; g += wstride) {
-        const int gw = (int)(g % GW);
-        long long t = g / GW;
-        const int h = (int)(t % p.H); t /= p.H;
-        const int d = (int)(t % p.D);
-        const int n = (int)(t / p.D);
-        const int w0 = gw * 16, w = w0 + r;
-        const bool valid = w < p.W;
-        const long long cvox = (((long long)n * p.D + d) * p.H + h) * p.W + w;
-        u32x4_t bx[KS];
-#pragma unroll
-        for (int k = 0; k < KS; ++k)
-            bx[k] = (valid && kok[k]) ? ldg16(xg + cvox * p.ldx + k * 32 + q * 8) : u32x4_t{0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-#pragma unroll
-            for (int j = 0; j < NH; ++j) {
-                f32x4_t acc = bv[j];
-#pragma unroll
-                for (int k = 0; k < KS; ++k) mma_chunk<bf16_t>(acc, af[c][j][k], bx[k]);
-                const bf16x4_t o = {(bf16_t)acc[0], (bf16_t)acc[1], (bf16_t)acc[2], (bf16_t)acc[3]};
-                *(bf16x4_t*)(tile + (CH * r + c) * RSB + (j * 16 + q * 4) * 2) = o;
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // wave-private tile: LDS ops of one wave execute in order
-        const int ncv = (p.W - w0) < 16 ? (p.W - w0) : 16;   // valid coarse voxels of this segment
-        const long long frow = (((long long)n * 2 * p.D + 2 * d + (abc0 >> 2)) * 2 * p.H + 2 * h + ((abc0 >> 1) & 1)) * 2 * p.W + 2 * w0;
-#pragma unroll
-        for (int it = 0; it < (FV * CPV + 63) / 64; ++it) {
-            const int ch = it * 64 + lane;
-            const int fv = ch / CPV, part = ch - fv * CPV;
-            if (ch < FV * CPV && fv < CH * ncv) {
-                const u32x4_t v = *(const u32x4_t*)(tile + fv * RSB + part * 16);
-                const long long fw = CH == 2 ? fv : 2 * fv + (abc0 & 1);
-                *(u32x4_t*)(yg + (frow + fw) * p.ldy + part * 8) = v;
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the reads are done before the next group's writes
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // backward-data: the four waves split K = 8 * Cout
 // ---------------------------------------------------------------------------------------------------------
 template <int KSW, int NH, bool PART>   // KSW = Cout / 16 k-steps per wave, NH Cin tiles per slice
-__global__ __launch_bounds__(DG_THREADS, 2) void dcg_bwd_kernel(const DcgParams p) {
+__global__ __launch_bounds__(DG_THREADS, 2) void dcg_bwd_kernel(const DeconvParams p) {
     __shared__ __attribute__((aligned(16))) float xch[3][NH][64][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 15, q = lane >> 4;
@@ -141,7 +45,7 @@ __global__ __launch_bounds__(DG_THREADS, 2) void dcg_bwd_kernel(const DcgParams 
         for (int k = 0; k < KSW; ++k) {
             const int m0 = mbase + j * 16;
             const int blk = m0 / p.cb, row = m0 - blk * p.cb + r;
-            af[j][k] = ldg16((const unsigned char*)p.wp + ((((long long)blk * kstot + k0 + k) * 4 + q) * p.cb + row) * 16);
+            af[j][k] = ldg16((const unsigned char*)p.wp + wimg_frag_off(blk, kstot, k0 + k, q, p.cb, row));
         }
     int off[KSW];                                       // this lane's chunk of k-step k0 + k, relative to fine voxel (2d, 2h, 2w)
 #pragma unroll
@@ -213,18 +117,12 @@ bool bwd_cfg(int Cin, int Cout, BwdCfg* c) {
     return false;
 }
 
-bool common_ok(int dtype, const void* coarse, long long ldc, const void* fine, long long ldf, int Cin, int Cout) {
-    if (dtype != MSSEG_BF16) return false;
-    if ((ldc % 8) || (ldf % 8) || ((uintptr_t)coarse & 15) || ((uintptr_t)fine & 15) || ldc < Cin || ldf < Cout) return false;
-    return true;
-}
-
 }  // namespace
 
 bool msseg_deconv2g_fwd_eligible(int dtype, int Cin, int Cout, const void* coarse, long long ldc, const void* fine,
                                  long long ldf, const float* bias) {
     FwdCfg c;
-    if (!common_ok(dtype, coarse, ldc, fine, ldf, Cin, Cout) || Cin % 8 || Cout % 16) return false;
+    if (!msseg_aligned_bf16(dtype, coarse, ldc, Cin, fine, ldf, Cout) || Cin % 8 || Cout % 16) return false;
     if (bias && ((uintptr_t)bias & 15)) return false;
     return fwd_cfg(Cin, Cout, &c);
 }
@@ -233,7 +131,7 @@ int msseg_deconv2g_fwd_launch(const void* x, long long ldx, const void* wp, cons
                               int D, int H, int W, int Cin, int Cout, hipStream_t stream) {
     FwdCfg c;
     if (!fwd_cfg(Cin, Cout, &c)) MSSEG_FAIL(MSSEG_EINVAL, "deconv2g_fwd: shape %d -> %d has no instantiation", Cin, Cout);
-    DcgParams p{};
+    DeconvParams p{};
     p.x = x; p.ldx = ldx; p.wp = wp; p.bias = bias; p.y = y; p.ldy = ldy;
     p.N = N; p.D = D; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
     p.cb = msseg_cout_block(8 * Cout);
@@ -247,7 +145,7 @@ int msseg_deconv2g_fwd_launch(const void* x, long long ldx, const void* wp, cons
 #define DCG_FWD(KS_, NH_, CH_)                                                                                         \
     if (c.ks == KS_ && c.nh == NH_ && c.ch == CH_) {                                                                   \
         MSSEG_KTIMED("dcg_fwd_kernel", stream,                                                                          \
-                     hipLaunchKernelGGL((dcg_fwd_kernel<KS_, NH_, CH_>), grid, dim3(DG_THREADS), 0, stream, p));        \
+                     hipLaunchKernelGGL((deconv_sliced_fwd_kernel<2, KS_, NH_, CH_>), grid, dim3(DG_THREADS), 0, stream, p)); \
     } else
     DCG_FWD(2, 3, 2) DCG_FWD(3, 3, 2) DCG_FWD(4, 2, 2) DCG_FWD(6, 2, 2) DCG_FWD(8, 1, 2) DCG_FWD(12, 1, 2) DCG_FWD(24, 1, 1) {}
 #undef DCG_FWD
@@ -260,7 +158,7 @@ bool msseg_deconv2g_bwd_eligible(int dtype, int Cin, int Cout, const void* coars
     BwdCfg c;
     if (coarse == nullptr) {   // partial-sum form: no coarse tensor
         if (dtype != MSSEG_BF16 || (ldf % 8) || ((uintptr_t)fine & 15) || ldf < Cout) return false;
-    } else if (!common_ok(dtype, coarse, ldc, fine, ldf, Cin, Cout) || (ldc % 4)) {
+    } else if (!msseg_aligned_bf16(dtype, coarse, ldc, Cin, fine, ldf, Cout) || (ldc % 4)) {
         return false;
     }
     return bwd_cfg(Cin, Cout, &c);
@@ -272,7 +170,7 @@ int msseg_deconv2g_bwd_launch(const void* dy, long long lddy, const void* wp, vo
     BwdCfg c;
     if (!bwd_cfg(Cin, Cout, &c)) MSSEG_FAIL(MSSEG_EINVAL, "deconv2g_bwd: shape %d -> %d has no instantiation", Cin, Cout);
     if ((long long)(2 * H) * (2 * W) * 2 * lddy > 0x7fffffffLL) MSSEG_FAIL(MSSEG_EINVAL, "deconv2g_bwd: fine plane too large");
-    DcgParams p{};
+    DeconvParams p{};
     p.x = dx; p.ldx = lddx; p.wp = wp; p.y = (void*)dy; p.ldy = lddy; p.part = part;
     p.N = N; p.D = D; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
     p.cb = msseg_cout_block(Cin);

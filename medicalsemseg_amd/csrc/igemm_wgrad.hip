@@ -56,11 +56,6 @@ template <typename T, int NTAPS, int TD, int TH, int TW> struct WgCfg {
     static_assert(TV % KSTEP == 0, "tile voxels must be a multiple of the k-step");
 };
 
-MSSEG_DEVFN bf16x4_t lds_tr_read(const unsigned char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-        (__attribute__((address_space(3))) bf16x4_t*)(uintptr_t)(uint32_t)(uintptr_t)p);
-}
-
 template <typename T, int NTAPS, int QSRC, int TD, int TH, int TW>
 __global__ __launch_bounds__(256) void igemm_wgrad_kernel(const WgradParams p) {
     using C = WgCfg<T, NTAPS, TD, TH, TW>;
@@ -273,12 +268,6 @@ __global__ __launch_bounds__(256) void igemm_wgrad_kernel(const WgradParams p) {
                     prow[i] = tv * RS + pc * 8;
                     qrow[i] = ((td * PH + th) * PW + tw) * RS + pc * 8;
                 }
-                auto tr_frag = [&](const unsigned char* base, int r0, int r1) -> u32x4_t {
-                    bf16x4_t lo = lds_tr_read(base + r0);
-                    bf16x4_t hi = lds_tr_read(base + r1);
-                    bf16x8_t f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    return __builtin_bit_cast(u32x4_t, f);
-                };
                 auto tap_off = [&](int tap) -> int {
                     if constexpr (NTAPS == 27) {
                         const int kd = tap / 9, kh = (tap / 3) % 3, kw = tap % 3;

@@ -45,7 +45,6 @@ MSSEG_DEVFN float bf16_lo(unsigned u) { return __builtin_bit_cast(float, u << 16
 MSSEG_DEVFN float bf16_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
 MSSEG_DEVFN float gelu_cdf(float v) { return 0.5f * (1.f + erff(v * 0.70710678118654752f)); }
 
-MSSEG_DEVFN u32x4_t ldg16(const void* p) { return *(const u32x4_t*)p; }
 
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 MSSEG_DEVFN unsigned pack_bf16x2(float a, float b) {
@@ -74,7 +73,7 @@ __global__ __launch_bounds__(LR_THREADS, 2) void linear_regw_kernel(const LinPar
         for (int k = 0; k < KS; ++k) {
             const int m0 = mbase + j * 16;
             const int blk = m0 / p.cb, row = m0 - blk * p.cb + r;
-            af[j][k] = ldg16((const unsigned char*)p.wp + ((((long long)blk * KS + k) * 4 + q) * p.cb + row) * 16);
+            af[j][k] = ldg16((const unsigned char*)p.wp + wimg_frag_off(blk, KS, k, q, p.cb, row));
         }
     f32x4_t bv[NH];
 #pragma unroll
@@ -182,7 +181,7 @@ __global__ __launch_bounds__(LR_THREADS, 2) void linear_ksplit_kernel(const LinP
         u32x4_t af[KSW];
 #pragma unroll
         for (int k = 0; k < KSW; ++k)
-            af[k] = ldg16((const unsigned char*)p.wp + ((((long long)blk * kstot + k0 + k) * 4 + q) * p.cb + row) * 16);
+            af[k] = ldg16((const unsigned char*)p.wp + wimg_frag_off(blk, kstot, k0, q, p.cb, row) + k * wimg_kblock_bytes(p.cb));
         acc[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         if (wave == 0 && p.bias) acc[j] = *(const f32x4_t*)(p.bias + m0 + q * 4);
 #pragma unroll
@@ -256,7 +255,7 @@ bool msseg_linear_regw_eligible(int dtype, long long NV, int Cin, int Cout, cons
     if (dtype != MSSEG_BF16 || NV < 1 || Cout % 16 || Cin % 8) return false;
     const int ks = (Cin + 31) / 32;
     if ((!lr_ks_ok(ks) || pick_nh(ks, Cout) == 0) && !ksplit_ok(Cin, Cout, NV)) return false;
-    if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || (ldx % 8) || (ldy % 8) || ldx < Cin || ldy < Cout) return false;
+    if (!msseg_aligned_bf16(dtype, x, ldx, Cin, y, ldy, Cout)) return false;
     if (bias && ((uintptr_t)bias & 15)) return false;
     return true;
 }

@@ -12,182 +12,17 @@
 // its token chunks, gets db from one more MFMA per row tile against a fragment of ones, and writes ONE partial block;
 // a second small kernel adds the workgroups' blocks in a fixed order (deterministic) into the torch-layout gradients.
 //
-// Per 128-token chunk: 256 threads load the rows (16-byte pieces, consecutive lanes on consecutive pieces of a row) into
-// registers while the previous chunk is computed, then store them as [32-channel block][token][96 B] images (64 B of data,
-// 32 B pad: the pitch that makes the transposing reads conflict-free, as in igemm_wgrad.hip); wave w takes tokens
-// 32 w .. 32 w + 31 as its MFMA k-step: both operands are read with ds_read_b64_tr_b16 (contraction index = token,
-// memory holds token rows), NTP + NTQ fragments for NTP x NTQ (+ NTP) MFMAs.
-#include "common.h"
+// The kernel itself (wgrad_onepass.h) takes the dy row of a token from a row source: plain rows for nn.Linear, the gathered child
+// rows of a transposed convolution for msseg_lwg_deconv_wgrad below (k2 s2) and for deconv_k4s4.hip (k4 s4).
+#include "wgrad_onepass.h"
 
 namespace {
-
-constexpr int TT = 128;            // tokens per chunk
-constexpr int RS = 96;             // LDS row pitch of a 32-channel block image
-constexpr int BLK_BYTES = TT * RS;
-constexpr int LW_THREADS = 256;
-
-struct LwgParams {
-    const void* x; long long ldx;      // [NV][K]
-    const void* dy; long long lddy;    // [NV][M]
-    float* part;                       // [slice][workgroup][ [k: NTQ*16][m: NTP*16] + bias [NTP*16] ] fp32
-    long long NV;
-    int M, K, mslices, kslices, nchunks;
-    // DCV (weight gradient of ConvTranspose3d k2 s2): dy is the FINE tensor [N, 2D, 2H, 2W, cout]; the row of coarse token t is
-    // the 8 child rows (m = abc * cout + co), gathered while staging
-    int D, H, W, cout;
-};
-
-MSSEG_DEVFN bf16x4_t lds_tr_read(const unsigned char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-        (__attribute__((address_space(3))) bf16x4_t*)(uintptr_t)(uint32_t)(uintptr_t)p);
-}
-MSSEG_DEVFN u32x4_t tr_frag(const unsigned char* base, int r0, int r1) {
-    const bf16x4_t lo = lds_tr_read(base + r0), hi = lds_tr_read(base + r1);
-    const bf16x8_t f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(u32x4_t, f);
-}
-
-template <int NTP, int NTQ, bool DCV = false>
-__global__ __launch_bounds__(LW_THREADS, 1) void lwg_kernel(const LwgParams p) {
-    constexpr int NBP = (NTP + 1) / 2, NBQ = (NTQ + 1) / 2;       // 32-channel block images
-    constexpr int CHP = NTP * 2, CHQ = NTQ * 2;                   // 16-byte pieces per row of the slice
-    constexpr int NLP = (TT * CHP + LW_THREADS - 1) / LW_THREADS; // staged pieces per thread
-    constexpr int NLQ = (TT * CHQ + LW_THREADS - 1) / LW_THREADS;
-    constexpr int PART = NTP * 16 * NTQ * 16 + NTP * 16;
-    extern __shared__ __attribute__((aligned(256))) unsigned char smem[];
-    unsigned char* ldsP = smem;
-    unsigned char* ldsQ = smem + NBP * BLK_BYTES;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ms = blockIdx.y / p.kslices, ks = blockIdx.y - ms * p.kslices;
-    const bool with_bias = ks == 0;
-    const unsigned char* pg = (const unsigned char*)p.dy + (long long)ms * NTP * 32;
-    const unsigned char* qg = (const unsigned char*)p.x + (long long)ks * NTQ * 32;
-
-    // ---- staging: piece i of the chunk = (row i / CH, 16-byte piece i % CH of the slice's part of the row); the offsets are
-    // recomputed per chunk (constant divisions) instead of held in 3 registers per piece: the accumulators need the room
-    u32x4_t sp[NLP], sq[NLQ];
-    __shared__ unsigned fbase[2][DCV ? TT : 1];   // DCV: fine voxel (2d, 2h, 2w) of the chunk's tokens (fine voxel count < 2^31)
-    auto fill_table = [&](int chunk, int sel) {
-        if constexpr (DCV) {
-            if (tid < TT) {
-                unsigned t = (unsigned)chunk * (unsigned)TT + (unsigned)tid;
-                if ((long long)t >= p.NV) t = 0;
-                const unsigned w = t % (unsigned)p.W; t /= (unsigned)p.W;
-                const unsigned h = t % (unsigned)p.H; t /= (unsigned)p.H;
-                const unsigned d = t % (unsigned)p.D, n = t / (unsigned)p.D;
-                fbase[sel][tid] = ((n * 2u * p.D + 2u * d) * 2u * p.H + 2u * h) * 2u * p.W + 2u * w;
-            }
-        }
-    };
-    auto fetch = [&](int chunk, int tsel) {
-        const long long t0 = (long long)chunk * TT;
-        const int rows = (p.NV - t0) < TT ? (int)(p.NV - t0) : TT;
-        const unsigned char* pb = pg + t0 * p.lddy * 2;
-        const unsigned char* qb = qg + t0 * p.ldx * 2;
-#pragma unroll
-        for (int it = 0; it < NLP; ++it) {
-            const int i = tid + it * LW_THREADS, row = i / CHP, c = i - row * CHP;
-            if constexpr (DCV) {
-                // piece c of the slice = channels (ms * NTP * 2 + c) * 8 .. of the gathered row: child abc, channel co; the
-                // row's fine base voxel comes from the table the first 128 threads filled for this chunk
-                const unsigned ch = (unsigned)(ms * NTP * 2 + c) * 8u;
-                const unsigned abc = ch / (unsigned)p.cout, co = ch - abc * (unsigned)p.cout;
-                const unsigned fv = fbase[tsel][row < TT ? row : 0] + ((abc >> 2) * 2u * p.H + ((abc >> 1) & 1u)) * 2u * p.W + (abc & 1u);
-                sp[it] = row < rows ? *(const u32x4_t*)((const unsigned char*)p.dy + ((unsigned long long)fv * (unsigned)p.lddy + co) * 2)
-                                    : u32x4_t{0u, 0u, 0u, 0u};
-            } else {
-                sp[it] = row < rows ? *(const u32x4_t*)(pb + (unsigned)(row * (int)p.lddy * 2 + c * 16)) : u32x4_t{0u, 0u, 0u, 0u};
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < NLQ; ++it) {
-            const int i = tid + it * LW_THREADS, row = i / CHQ, c = i - row * CHQ;
-            sq[it] = row < rows ? *(const u32x4_t*)(qb + (unsigned)(row * (int)p.ldx * 2 + c * 16)) : u32x4_t{0u, 0u, 0u, 0u};
-        }
-    };
-    auto commit = [&]() {
-#pragma unroll
-        for (int it = 0; it < NLP; ++it) {
-            const int i = tid + it * LW_THREADS, row = i / CHP, c = i - row * CHP;
-            if (row < TT) *(u32x4_t*)(ldsP + (c >> 2) * BLK_BYTES + row * RS + (c & 3) * 16) = sp[it];
-        }
-#pragma unroll
-        for (int it = 0; it < NLQ; ++it) {
-            const int i = tid + it * LW_THREADS, row = i / CHQ, c = i - row * CHQ;
-            if (row < TT) *(u32x4_t*)(ldsQ + (c >> 2) * BLK_BYTES + row * RS + (c & 3) * 16) = sq[it];
-        }
-    };
-
-    // ---- transposing fragment reads: lane = 16 g + 4 qr + pc supplies row 8 g + 4 i + qr of the wave's 32 tokens, channels
-    // 4 pc .. of a 16-channel tile (cdna_hip_programming.md T10)
-    const int g = lane >> 4, qr = (lane >> 2) & 3, pc = lane & 3;
-    int trow[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) trow[i] = (wave * 32 + 8 * g + 4 * i + qr) * RS + pc * 8;
-
-    f32x4_t acc[NTP][NTQ], accb[NTP];
-#pragma unroll
-    for (int a = 0; a < NTP; ++a) {
-        accb[a] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int b = 0; b < NTQ; ++b) acc[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    }
-    const u32x4_t ones = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};   // bf16 1.0 x 8
-
-    if constexpr (DCV) {
-        fill_table(blockIdx.x, 0);
-        __syncthreads();
-    }
-    if ((int)blockIdx.x < p.nchunks) fetch(blockIdx.x, 0);
-    int tsel = 0;
-    for (int chunk = blockIdx.x; chunk < p.nchunks; chunk += gridDim.x) {
-        __syncthreads();                 // the previous chunk's fragment reads are done
-        commit();
-        tsel ^= 1;
-        fill_table(chunk + gridDim.x, tsel);   // read by the fetch behind the next barrier; the other half is still the table of
-                                               // the pieces in flight ... which were fetched before this point
-        __syncthreads();
-        if (chunk + (int)gridDim.x < p.nchunks) fetch(chunk + gridDim.x, tsel);
-        u32x4_t pf[NTP], qf[NTQ];
-#pragma unroll
-        for (int a = 0; a < NTP; ++a) pf[a] = tr_frag(ldsP + (a >> 1) * BLK_BYTES, trow[0] + (a & 1) * 32, trow[1] + (a & 1) * 32);
-#pragma unroll
-        for (int b = 0; b < NTQ; ++b) qf[b] = tr_frag(ldsQ + (b >> 1) * BLK_BYTES, trow[0] + (b & 1) * 32, trow[1] + (b & 1) * 32);
-#pragma unroll
-        for (int a = 0; a < NTP; ++a) {
-#pragma unroll
-            for (int b = 0; b < NTQ; ++b) mma_chunk<bf16_t>(acc[a][b], pf[a], qf[b]);
-            if (with_bias) mma_chunk<bf16_t>(accb[a], pf[a], ones);
-        }
-    }
-
-    // ---- the four waves' partial sums (different tokens) meet in LDS, [wave][k][m] so that a lane's four consecutive m are one
-    // 16-byte store, and are added in a fixed order: ONE block [k][m] (+ the bias sums) per workgroup goes to memory
-    __syncthreads();                     // the images are dead
-    float* xch = (float*)smem;
-    const int r = lane & 15, q = lane >> 4;
-#pragma unroll
-    for (int a = 0; a < NTP; ++a) {
-#pragma unroll
-        for (int b = 0; b < NTQ; ++b)
-            *(f32x4_t*)(xch + wave * PART + (b * 16 + r) * (NTP * 16) + a * 16 + q * 4) = acc[a][b];
-        if (r == 0) *(f32x4_t*)(xch + wave * PART + NTQ * 16 * NTP * 16 + a * 16 + q * 4) = accb[a];
-    }
-    __syncthreads();
-    float* out = p.part + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * PART;
-    for (int i = tid * 4; i < PART; i += LW_THREADS * 4) {
-        const f32x4_t v0 = *(const f32x4_t*)(xch + i), v1 = *(const f32x4_t*)(xch + PART + i),
-                      v2 = *(const f32x4_t*)(xch + 2 * PART + i), v3 = *(const f32x4_t*)(xch + 3 * PART + i);
-        *(f32x4_t*)(out + i) = (v0 + v1) + (v2 + v3);
-    }
-}
 
 struct LwgRedParams {
     const float* part;
     float* dw; float* db;
     int M, K, ntp16, ntq16, mslices, kslices, nwg, acc_w, acc_b;
+    int stride;     // floats between the partial blocks of two workgroups (lwg_part_floats)
     int dcv_cout;   // > 0: m = abc * cout + co of a transposed conv: dw in the torch layout [K = Cin][cout][8]
 };
 
@@ -196,7 +31,7 @@ struct LwgRedParams {
 __global__ __launch_bounds__(256) void lwg_reduce_kernel(const LwgRedParams p) {
     __shared__ float gs[8][33];
     const int total = p.M * p.K + (p.db ? p.M : 0);
-    const int part = p.ntp16 * p.ntq16 + p.ntp16;
+    const int part = p.stride;
     const int ol = threadIdx.x & 31, sg = threadIdx.x >> 5;
     for (int base = blockIdx.x * 32; base < total; base += gridDim.x * 32) {
         const int i = base + ol;
@@ -248,33 +83,37 @@ constexpr Shape kShapes[] = {{12, 3}, {3, 12}, {6, 6}, {9, 3}, {3, 9}, {6, 3}, {
 // partial blocks and their reduction cost more than the flat kernel's re-reads.  Only the 48-multiples on large grids come here.
 constexpr Shape kShapesDcv[] = {{12, 3}};
 
-bool pick_shape_dcv(int M, int K, Shape* out) {
+bool pick_shape(const Shape* shapes, int n, int M, int K, Shape* out) {
     if (M % 16 || K % 16) return false;
     const int tm = M / 16, tk = K / 16;
-    for (const Shape& s : kShapesDcv)
-        if (tm % s.ntp == 0 && tk % s.ntq == 0) { *out = s; return true; }
+    for (int i = 0; i < n; ++i)
+        if (tm % shapes[i].ntp == 0 && tk % shapes[i].ntq == 0) { *out = shapes[i]; return true; }
     return false;
 }
+bool pick_shape_dcv(int M, int K, Shape* out) { return pick_shape(kShapesDcv, sizeof(kShapesDcv) / sizeof(Shape), M, K, out); }
+bool pick_shape(int M, int K, Shape* out) { return pick_shape(kShapes, sizeof(kShapes) / sizeof(Shape), M, K, out); }
 
-bool pick_shape(int M, int K, Shape* out) {
-    if (M % 16 || K % 16) return false;
-    const int tm = M / 16, tk = K / 16;
-    for (const Shape& s : kShapes)
-        if (tm % s.ntp == 0 && tk % s.ntq == 0) { *out = s; return true; }
-    return false;
-}
-
-template <int NTP, int NTQ, bool DCV = false> int launch_lwg(const LwgParams& p, int gx, hipStream_t stream) {
-    constexpr int NBP = (NTP + 1) / 2, NBQ = (NTQ + 1) / 2;
-    constexpr int PART = NTP * 16 * NTQ * 16 + NTP * 16;
-    constexpr int lds = (NBP + NBQ) * BLK_BYTES > 4 * PART * 4 ? (NBP + NBQ) * BLK_BYTES : 4 * PART * 4;
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = lwg_kernel<NTP, NTQ, DCV>;
-    static msseg_lds_attr_once attr;
-    if (!attr.ensure((const void*)kern, lds)) MSSEG_FAIL(MSSEG_ELAUNCH, "linear_wgrad: cannot set dynamic LDS size %d", lds);
-    MSSEG_KTIMED(DCV ? "lwg_kernel<deconv>" : "lwg_kernel", stream,
-                 hipLaunchKernelGGL(kern, dim3(gx, p.mslices * p.kslices), dim3(LW_THREADS), lds, stream, p));
-    MSSEG_CHECK_LAUNCH("linear_wgrad");
+// the kernel (through `launch(gx, slices)`) on M x K outputs in slices of shape s, then the fixed-order sum of the partial blocks
+// into dw (and db: the row source accumulates bias sums)
+template <class Launch>
+int run_lwg(LwgParams& p, Shape s, int M, int K, bool bias_sums, float* dw, float* db, int acc_w, int acc_b, int dcv_cout,
+            void* workspace, size_t workspace_bytes, const char* who, hipStream_t stream, Launch launch) {
+    const int mslices = M / (s.ntp * 16), slices = mslices * (K / (s.ntq * 16));
+    const int part = s.ntp * 16 * s.ntq * 16 + (bias_sums ? s.ntp * 16 : 0);   // lwg_part_floats
+    p.kslices = K / (s.ntq * 16);
+    p.nchunks = (int)((p.NV + LWG_TT - 1) / LWG_TT);
+    p.part = (float*)workspace;
+    const size_t slice_bytes = (size_t)part * 4 * slices;
+    if (workspace_bytes < slice_bytes) MSSEG_FAIL(MSSEG_EWORKSPACE, "%s: workspace %zu B too small (need >= %zu)", who, workspace_bytes, slice_bytes);
+    const int gx = lwg_grid_x(slices, p.nchunks, workspace_bytes / slice_bytes);
+    if (int rc = launch(gx, slices)) return rc;
+    LwgRedParams r{};
+    r.part = p.part; r.dw = dw; r.db = db; r.M = M; r.K = K; r.ntp16 = s.ntp * 16; r.ntq16 = s.ntq * 16;
+    r.mslices = mslices; r.kslices = p.kslices; r.nwg = gx; r.acc_w = acc_w; r.acc_b = acc_b; r.stride = part; r.dcv_cout = dcv_cout;
+    int rb = (M * K + (db ? M : 0) + 31) / 32;
+    if (rb > 4096) rb = 4096;
+    hipLaunchKernelGGL(lwg_reduce_kernel, dim3(rb), dim3(256), 0, stream, r);
+    MSSEG_CHECK_LAUNCH(who);
     return MSSEG_OK;
 }
 
@@ -286,8 +125,7 @@ template <int NTP, int NTQ, bool DCV = false> int launch_lwg(const LwgParams& p,
 // layer, 64 us per Swin-UNETR layer); here a workgroup reads whole rows -- the coarse row and the 8 child rows it gathers.
 bool msseg_lwg_deconv_ok(int dtype, long long NV, int Cin, int Cout, const void* x, long long ldx, const void* dy, long long lddy) {
     Shape s;
-    if (dtype != MSSEG_BF16 || NV < 100000 || NV > 0x7fffffffLL / 8 || Cout % 8) return false;
-    if ((((uintptr_t)x | (uintptr_t)dy) & 15) || (ldx % 8) || (lddy % 8) || ldx < Cin || lddy < Cout) return false;
+    if (NV < 100000 || NV > 0x7fffffffLL / 8 || Cout % 8 || !msseg_aligned_bf16(dtype, x, ldx, Cin, dy, lddy, Cout)) return false;
     return pick_shape_dcv(8 * Cout, Cin, &s);
 }
 
@@ -297,33 +135,13 @@ int msseg_lwg_deconv_wgrad(const void* x, long long ldx, const void* dy, long lo
     if (!pick_shape_dcv(8 * Cout, Cin, &s)) MSSEG_FAIL(MSSEG_EINVAL, "deconv wgrad: shape %d -> %d has no instantiation", Cin, Cout);
     if ((uintptr_t)workspace & 15) MSSEG_FAIL(MSSEG_EINVAL, "deconv wgrad: workspace alignment");
     LwgParams p{};
-    p.x = x; p.ldx = ldx; p.dy = dy; p.lddy = lddy; p.NV = (long long)N * D * H * W; p.M = 8 * Cout; p.K = Cin;
+    p.x = x; p.ldx = ldx; p.dy = dy; p.lddy = lddy; p.NV = (long long)N * D * H * W;
     p.D = D; p.H = H; p.W = W; p.cout = Cout;
-    p.mslices = p.M / (s.ntp * 16); p.kslices = Cin / (s.ntq * 16);
-    p.nchunks = (int)((p.NV + TT - 1) / TT);
-    const int slices = p.mslices * p.kslices;
-    const size_t part_bytes = (size_t)(s.ntp * 16 * s.ntq * 16 + s.ntp * 16) * 4;
-    int gx = msseg_num_cus() / slices;
-    if (gx < 1) gx = 1;
-    if (gx > (p.nchunks + 1) / 2) gx = (p.nchunks + 1) / 2;
-    if (gx < 1) gx = 1;
-    const size_t fit = workspace_bytes / (part_bytes * slices);
-    if (fit < 1) MSSEG_FAIL(MSSEG_EWORKSPACE, "deconv wgrad: workspace %zu B too small (need >= %zu)", workspace_bytes, part_bytes * slices);
-    if ((size_t)gx > fit) gx = (int)fit;
-    p.part = (float*)workspace;
-    int rc = MSSEG_EINVAL;
-    switch (s.ntp * 100 + s.ntq) {
-        case 1203: rc = launch_lwg<12, 3, true>(p, gx, stream); break;
-    }
-    if (rc) return rc;
-    LwgRedParams r{};
-    r.part = p.part; r.dw = dw; r.db = nullptr; r.M = p.M; r.K = Cin; r.ntp16 = s.ntp * 16; r.ntq16 = s.ntq * 16;
-    r.mslices = p.mslices; r.kslices = p.kslices; r.nwg = gx; r.acc_w = accumulate; r.acc_b = 0; r.dcv_cout = Cout;
-    int rb = (p.M * Cin + 31) / 32;
-    if (rb > 4096) rb = 4096;
-    hipLaunchKernelGGL(lwg_reduce_kernel, dim3(rb), dim3(256), 0, stream, r);
-    MSSEG_CHECK_LAUNCH("deconv_wgrad_reduce");
-    return MSSEG_OK;
+    const char* who = "deconv wgrad";
+    return run_lwg(p, s, 8 * Cout, Cin, false, dw, nullptr, accumulate, 0, Cout, workspace, workspace_bytes, who, stream,
+                   [&](int gx, int slices) {   // kShapesDcv
+                       return lwg_launch<12, 3, RowsDeconvK2<12, 3>>(p, gx, slices, who, stream);
+                   });
 }
 
 extern "C" {
@@ -342,48 +160,28 @@ int msseg_linear_wgrad(const void* x, long long ldx, const void* dy, long long l
                        int dtype, msseg_stream_t stream) {
     if (!x || !dy || !dw || !workspace) MSSEG_FAIL(MSSEG_EINVAL, "linear_wgrad: null pointer");
     if (!msseg_linear_wgrad_ok(NV, Cin, Cout, dtype)) MSSEG_FAIL(MSSEG_EINVAL, "linear_wgrad: shape %d -> %d not supported (msseg_linear_wgrad_ok)", Cin, Cout);
-    if ((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)workspace) & 15) || (ldx % 8) || (lddy % 8) || ldx < Cin || lddy < Cout)
+    if (!msseg_aligned_bf16(dtype, x, ldx, Cin, dy, lddy, Cout) || ((uintptr_t)workspace & 15))
         MSSEG_FAIL(MSSEG_EINVAL, "linear_wgrad: operands must be 16-byte aligned with 16-byte row strides");
-    if ((long long)TT * (ldx > lddy ? ldx : lddy) * 2 >= 0x7fffffffLL) MSSEG_FAIL(MSSEG_EINVAL, "linear_wgrad: row stride too large");
     Shape s;
     pick_shape(Cout, Cin, &s);
     LwgParams p{};
-    p.x = x; p.ldx = ldx; p.dy = dy; p.lddy = lddy; p.NV = NV; p.M = Cout; p.K = Cin;
-    p.mslices = Cout / (s.ntp * 16); p.kslices = Cin / (s.ntq * 16);
-    p.nchunks = (int)((NV + TT - 1) / TT);
-    const int slices = p.mslices * p.kslices;
-    const size_t part_bytes = (size_t)(s.ntp * 16 * s.ntq * 16 + s.ntp * 16) * 4;
-    // workgroups per slice: the chip divided by the slices, at least two chunks each when there are that many tokens (every
-    // workgroup writes a partial block whatever it summed), bounded by the workspace
-    int gx = msseg_num_cus() / slices;
-    if (gx < 1) gx = 1;
-    if (gx > (p.nchunks + 1) / 2) gx = (p.nchunks + 1) / 2;
-    if (gx < 1) gx = 1;
-    const size_t fit = workspace_bytes / (part_bytes * slices);
-    if (fit < 1) MSSEG_FAIL(MSSEG_EWORKSPACE, "linear_wgrad: workspace %zu B too small (need >= %zu)", workspace_bytes, part_bytes * slices);
-    if ((size_t)gx > fit) gx = (int)fit;
-    p.part = (float*)workspace;
-    int rc = MSSEG_EINVAL;
-    switch (s.ntp * 100 + s.ntq) {
-        case 1203: rc = launch_lwg<12, 3>(p, gx, (hipStream_t)stream); break;
-        case 312: rc = launch_lwg<3, 12>(p, gx, (hipStream_t)stream); break;
-        case 606: rc = launch_lwg<6, 6>(p, gx, (hipStream_t)stream); break;
-        case 903: rc = launch_lwg<9, 3>(p, gx, (hipStream_t)stream); break;
-        case 309: rc = launch_lwg<3, 9>(p, gx, (hipStream_t)stream); break;
-        case 603: rc = launch_lwg<6, 3>(p, gx, (hipStream_t)stream); break;
-        case 306: rc = launch_lwg<3, 6>(p, gx, (hipStream_t)stream); break;
-        case 303: rc = launch_lwg<3, 3>(p, gx, (hipStream_t)stream); break;
-    }
-    if (rc) return rc;
-    LwgRedParams r{};
-    r.part = p.part; r.dw = dw; r.db = dbias; r.M = Cout; r.K = Cin; r.ntp16 = s.ntp * 16; r.ntq16 = s.ntq * 16;
-    r.mslices = p.mslices; r.kslices = p.kslices; r.nwg = gx; r.acc_w = accumulate_w; r.acc_b = accumulate_b;
-    const int total = Cout * Cin + (dbias ? Cout : 0);
-    int rb = (total + 31) / 32;
-    if (rb > 4096) rb = 4096;
-    hipLaunchKernelGGL(lwg_reduce_kernel, dim3(rb), dim3(256), 0, (hipStream_t)stream, r);
-    MSSEG_CHECK_LAUNCH("linear_wgrad_reduce");
-    return MSSEG_OK;
+    p.x = x; p.ldx = ldx; p.dy = dy; p.lddy = lddy; p.NV = NV;
+    const char* who = "linear_wgrad";
+    hipStream_t st = (hipStream_t)stream;
+    return run_lwg(p, s, Cout, Cin, true, dw, dbias, accumulate_w, accumulate_b, 0, workspace, workspace_bytes, who, st,
+                   [&](int gx, int slices) {   // kShapes
+                       switch (s.ntp * 100 + s.ntq) {
+                           case 1203: return lwg_launch<12, 3, RowsPlain<12, 3>>(p, gx, slices, who, st);
+                           case 312: return lwg_launch<3, 12, RowsPlain<3, 12>>(p, gx, slices, who, st);
+                           case 606: return lwg_launch<6, 6, RowsPlain<6, 6>>(p, gx, slices, who, st);
+                           case 903: return lwg_launch<9, 3, RowsPlain<9, 3>>(p, gx, slices, who, st);
+                           case 309: return lwg_launch<3, 9, RowsPlain<3, 9>>(p, gx, slices, who, st);
+                           case 603: return lwg_launch<6, 3, RowsPlain<6, 3>>(p, gx, slices, who, st);
+                           case 306: return lwg_launch<3, 6, RowsPlain<3, 6>>(p, gx, slices, who, st);
+                           case 303: return lwg_launch<3, 3, RowsPlain<3, 3>>(p, gx, slices, who, st);
+                       }
+                       return (int)MSSEG_EINVAL;
+                   });
 }
 
 }  // extern "C"

@@ -405,7 +405,11 @@ def _deconv_ref(cin, cout, sp, N, k):
     return dict(x=x.detach(), w=w.detach(), b=b, dy=dy, y=y.detach(), dx=x.grad, dw=w.grad, db=dy.sum((0, 2, 3, 4)))
 
 
-DC2_CASES = [(32, 32, (8, 8, 8), 2), (256, 128, (3, 3, 3), 2), (48, 48, (4, 6, 10), 2), (128, 64, (4, 5, 7), 3)]
+# second row: the one-child forward slice <24, 1, 1> (fine-voxel index of a lone child) with input gradient <24, 1>; forward
+# <3, 3, 2> on a ragged W (a second 16-voxel group holding one voxel); the remaining forward instantiations <6, 2, 2> and <12, 1, 2>.
+# Maximum |reference| of the last two (y, dx, dw): 67, 124, 56 and 92, 121, 21
+DC2_CASES = [(32, 32, (8, 8, 8), 2), (256, 128, (3, 3, 3), 2), (48, 48, (4, 6, 10), 2), (128, 64, (4, 5, 7), 3),
+             (768, 384, (2, 3, 3), 2), (96, 48, (2, 3, 17), 2), (192, 96, (2, 3, 17), 2), (384, 192, (2, 3, 3), 2)]
 
 
 @pytest.mark.parametrize("cin,cout,sp,N,dtype", [(*c, d) for c in DC2_CASES for d in (F32, BF16)])
@@ -424,7 +428,7 @@ def test_deconv_k2s2_exact(cin, cout, sp, N, dtype):
         hip.deconv_k2s2_wgrad(xg, dyg, dw, cin, cout)
     part_ok = hip.deconv_k2s2_small_unit_ok((N, *sp, cin), cin, cout, dtype)
     print(f"deconv_k2s2 {cin}->{cout} @ {sp} N={N} {dtype}: launched {sorted(k.names)}; partial-block input gradient: {part_ok}")
-    assert part_ok == (dtype == BF16 and (cin, cout) in ((256, 128), (128, 64)))
+    assert part_ok == (dtype == BF16 and (cin, cout) in ((256, 128), (128, 64), (768, 384), (96, 48), (192, 96), (384, 192)))
     assert "lwg_kernel<deconv>" not in k.names and "igemm_wgrad_kernel<flat>" in k.names   # below 100 k coarse voxels: flat kernel
     assert_exact(vol(y), r["y"], "deconv_k2s2 fwd")
     assert_exact(vol(dx), r["dx"], "deconv_k2s2 bwd data")
@@ -441,7 +445,7 @@ def test_deconv_k2s2_exact(cin, cout, sp, N, dtype):
 
 def test_deconv_k2s2_wgrad_one_pass_exact():
     """48 -> 48 on more than 100 k coarse voxels: the weight gradient takes the one-pass kernel with the child-row gather
-    (csrc/linear_wgrad.hip, msseg_lwg_deconv_ok); test_deconv_k2s2_exact holds the shapes it rejects"""
+    (csrc/wgrad_onepass.h, msseg_lwg_deconv_ok); test_deconv_k2s2_exact holds the shapes it rejects"""
     from medicalsemseg_amd import hip
     dev = _dev()
     _threads()
@@ -461,10 +465,18 @@ def test_deconv_k2s2_wgrad_one_pass_exact():
     assert_exact(dw, 2 * ref, "deconv_k2s2 one-pass wgrad accumulate")
 
 
-# 48 -> 48: MFMA kernels in bf16 (dc4_*); 24 -> 40: no MFMA instantiation, the vector kernels in both dtypes
-@pytest.mark.parametrize("cin,cout,sp,dtype,mfma", [(48, 48, (3, 4, 5), BF16, True), (48, 48, (3, 4, 5), F32, False),
-                                                     (24, 40, (3, 4, 5), BF16, False), (24, 40, (3, 4, 5), F32, False)])
-def test_deconv_k4s4_exact(cin, cout, sp, dtype, mfma):
+# the dc4_* kernels a case must launch (everything else runs on the vector kernels).  48 -> 48 and the square cases on 2 x 3 x 17
+# (W = 17: a second W group holding one voxel; 204 coarse voxels: a second 128-voxel chunk with a tail of 76) cover forward
+# <1, 2> <2, 2> <2, 3> <3, 2> and weight gradient <8, 2, 4> <12, 3, 4> <8, 4, 2> <6, 6, 1>; 32 -> 48 is forward <1, 3>, whose
+# gradients have no MFMA instantiation; 24 -> 40 has none at all
+DC4_ALL = "fwd+bwd+wgrad"          # dc4_fwd_kernel, dc4_bwd_kernel, dc4_wgrad_kernel
+
+
+@pytest.mark.parametrize("cin,cout,sp,dtype,dc4", [(48, 48, (3, 4, 5), BF16, DC4_ALL), (48, 48, (3, 4, 5), F32, "none"),
+                                                    (24, 40, (3, 4, 5), BF16, "none"), (24, 40, (3, 4, 5), F32, "none"),
+                                                    (32, 32, (2, 3, 17), BF16, DC4_ALL), (64, 64, (2, 3, 17), BF16, DC4_ALL),
+                                                    (96, 96, (2, 3, 17), BF16, DC4_ALL), (32, 48, (2, 3, 17), BF16, "fwd")])
+def test_deconv_k4s4_exact(cin, cout, sp, dtype, dc4):
     from medicalsemseg_amd import hip
     dev = _dev()
     N = 2
@@ -478,7 +490,7 @@ def test_deconv_k4s4_exact(cin, cout, sp, dtype, mfma):
         dx = hip.deconv_k4s4_bwd_data(dyg, hip.pack_deconv(w, dtype, bwd=True), torch.empty(N, *sp, cin, dtype=dtype, device=dev), cin, cout)
         hip.deconv_k4s4_wgrad(xg, dyg, dw, cin, cout)
     print(f"deconv_k4s4 {cin}->{cout} @ {sp} {dtype}: launched {sorted(k.names)}")
-    assert ({"dc4_fwd_kernel", "dc4_bwd_kernel", "dc4_wgrad_kernel"} <= k.names) == mfma
+    assert {n for n in k.names if n.startswith("dc4_")} == {f"dc4_{v}_kernel" for v in dc4.split("+") if v != "none"}
     assert_exact(vol(y), r["y"], "deconv_k4s4 fwd")
     assert_exact(vol(dx), r["dx"], "deconv_k4s4 bwd data")
     assert_exact(dw, r["dw"], "deconv_k4s4 wgrad")

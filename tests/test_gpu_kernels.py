@@ -992,7 +992,7 @@ def test_deconv_bwd_fused_sums_and_bias(dtype, cin, cout, sp, N):
 
 def test_deconv_wgrad_large_grid_one_pass():
     """Swin-UNETR's 48 -> 48 transposed conv on a grid of > 100 k coarse voxels: the weight gradient takes the one-pass kernel
-    with the child-row gather (csrc/linear_wgrad.hip, DCV) -- against the fp32 contraction of the same bf16 operands"""
+    with the child-row gather (csrc/wgrad_onepass.h, RowsDeconvK2) -- against the fp32 contraction of the same bf16 operands"""
     from medicalsemseg_amd import hip
     dev = _dev()
     cin = cout = 48
