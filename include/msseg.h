@@ -744,6 +744,15 @@ int msseg_aug_crop_batch(const float* img, const uint8_t* lab, int C, int VD, in
  *            entry point cannot check it; DeviceDatasetLoader does on the host): every rows[i].vol is in [0, nvol), that
  *            volume has C channels and is at least R long on every axis.  A row that breaks it reads nothing and yields
  *            an all-zero patch; the call still returns MSSEG_OK.
+ * aug_crop_affine: aug_crop_multi that samples the cached VOLUME under a row-major 3x3 matrix M per patch (mats: npatch x 9
+ *            doubles on the device) instead of copying the crop: free rotation and zoom about the patch's geometric centre,
+ *            still one launch per batch.  Output voxel -> patch index p (rotk and flips undone as in aug_crop_multi, crop
+ *            start clamped the same way); source coordinate per axis a, in double with one rounding per operation:
+ *            c[a] = (start[a] + h) + ((M[a][0] d[0] + M[a][1] d[1]) + M[a][2] d[2]), h = (R - 1) / 2.0, d = p - h.  Image:
+ *            trilinear over the 8 taps at floor(c), fp32 lerps a + f * (b - a) along x, then y, then z with f = (float)(c -
+ *            floor(c)); a tap with any index outside the volume reads pad_value (scipy mode="grid-constant"); then
+ *            (v + shift) * scale.  Label: the voxel floor(c + 0.5), 0 outside the volume or without a label pointer.  With
+ *            M = I the output is bit for bit that of aug_crop_multi.  Invalid rows as in aug_crop_multi.
  * ------------------------------------------------------------------------------------------- */
 typedef struct msseg_volume_desc { const float* img; const uint8_t* lab; int32_t C, D, H, W; } msseg_volume_desc;
 typedef struct msseg_pick_row { int32_t vol, mode, z, rank, flips, rotk; float shift, scale; } msseg_pick_row;
@@ -759,6 +768,8 @@ int msseg_pick_voxels(const void* volumes, int nvol, const void* rows, int nrows
                       msseg_stream_t stream);
 int msseg_aug_crop_multi(const void* volumes, int nvol, const void* rows, const int* picks, int npatch, int C, void* out_img,
                          int out_dtype, float* out_lab, int R, msseg_stream_t stream);
+int msseg_aug_crop_affine(const void* volumes, int nvol, const void* rows, const int* picks, const double* mats, int npatch,
+                          int C, void* out_img, int out_dtype, float* out_lab, int R, float pad_value, msseg_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,7 @@
 //   slab_counts       per z-slice numbers of the crop-centre candidates RandCropByPosNegLabeld draws from (:108-120)
 //   pick_voxels       the k-th candidate of a slice -> crop centre (correct_crop_centers clamp) and crop start
 //   aug_crop_multi    msseg_aug_crop_batch over many cached volumes: one launch per batch
+//   aug_crop_affine   aug_crop_multi sampling the volume under a 3x3 matrix per patch (rotation + zoom about the patch centre)
 //
 // MONAI is absent: the semantics are those of the numpy / scipy restatement in tests/dataprep_ref.py (MONAI parity
 // unpinned).  All kernels are HBM-bound; geometry (z, y) comes from the launch grid, threads run along x.
@@ -295,6 +296,82 @@ __global__ __launch_bounds__(256) void aug_crop_multi_kernel(const VolDesc* __re
     }
 }
 
+// floor(c) (image, lo = -2) or floor(c + 0.5) (label, lo = -1) as an index that is safe to test against [0, n) and to add
+// 1 to, whatever the matrix table holds: values beyond the volume collapse onto lo / n, a NaN onto lo
+MSSEG_DEVFN int affine_index(double fl, double lo, int n) { return (int)fmin(fmax(fl, lo), (double)n); }
+
+// grid: (y tiles, R, npatch), block (32 along x, 8 rows).  The patch row, its matrix and the crop start are uniform per
+// block.  Source coordinate of patch index p, about the patch's geometric centre: c = (start + h) + M (p - h), h = (R - 1) / 2,
+// in double; image = trilinear over 8 taps (a tap outside the volume reads `pad`: scipy's mode="grid-constant"), fp32 lerps
+// a + f * (b - a) along x, y, z as resample_spacing_kernel; label = the nearest voxel floor(c + 0.5), 0 outside.
+// No LDS staging: the 32 x 8 voxels of a block map onto a slanted slab of a few KiB of the source, which the taps of
+// neighbouring lanes and rows re-read from the CU's vector cache; coordinates and fractions are shared by the C channels.
+template <typename TO>
+__global__ __launch_bounds__(256) void aug_crop_affine_kernel(const VolDesc* __restrict__ vols, int nvol,
+                                                              const PickRow* __restrict__ rows, const int* __restrict__ picks,
+                                                              const double* __restrict__ mats, TO* __restrict__ out_img,
+                                                              float* __restrict__ out_lab, int C, int R, float pad) {
+#pragma clang fp contract(off)   // every product and sum of the coordinate and of the lerps rounds once, in the stated order
+    const int b = blockIdx.z, z = blockIdx.y, y = blockIdx.x * blockDim.y + threadIdx.y;
+    if (y >= R) return;
+    const PickRow row = rows[b];
+    const bool known = row.vol >= 0 && row.vol < nvol;
+    const VolDesc vd = vols[known ? row.vol : 0];
+    const long long R3 = (long long)R * R * R, orow = ((long long)z * R + y) * R;
+    if (!known || vd.C != C || R > vd.D || R > vd.H || R > vd.W) {
+        for (int x = threadIdx.x; x < R; x += blockDim.x) {
+            for (int c = 0; c < C; ++c) DT<TO>::st(out_img + ((long long)b * C + c) * R3 + orow + x, 0.0f);
+            out_lab[(long long)b * R3 + orow + x] = 0.0f;
+        }
+        return;
+    }
+    int z0 = picks[8 * b + 3], y0 = picks[8 * b + 4], x0 = picks[8 * b + 5];
+    z0 = z0 < 0 ? 0 : (z0 > vd.D - R ? vd.D - R : z0);
+    y0 = y0 < 0 ? 0 : (y0 > vd.H - R ? vd.H - R : y0);
+    x0 = x0 < 0 ? 0 : (x0 > vd.W - R ? vd.W - R : x0);
+    // patch index of this output row: rot90^k and the flips undone as in aug_crop_multi_kernel
+    int sz = z, sy = y;
+    if (row.rotk == 1) { sz = y; sy = R - 1 - z; }
+    else if (row.rotk == 2) { sz = R - 1 - z; sy = R - 1 - y; }
+    else if (row.rotk == 3) { sz = R - 1 - y; sy = z; }
+    if (row.flips & 1) sz = R - 1 - sz;
+    if (row.flips & 2) sy = R - 1 - sy;
+    const bool flipx = (row.flips & 4) != 0;
+    const double* M = mats + 9 * (long long)b;
+    const double h = (double)(R - 1) / 2.0;
+    const double dz = (double)sz - h, dy = (double)sy - h;
+    const double bz = (double)z0 + h, by = (double)y0 + h, bx = (double)x0 + h;
+    const double pz = M[0] * dz + M[1] * dy, py = M[3] * dz + M[4] * dy, px = M[6] * dz + M[7] * dy;
+    const long long HW = (long long)vd.H * vd.W, V = (long long)vd.D * HW;
+    for (int x = threadIdx.x; x < R; x += blockDim.x) {
+        const double dx = (double)(flipx ? R - 1 - x : x) - h;
+        const double cz = bz + (pz + M[2] * dx), cy = by + (py + M[5] * dx), cx = bx + (px + M[8] * dx);
+        const double lz = floor(cz), ly = floor(cy), lx = floor(cx);
+        const float wz = (float)(cz - lz), wy = (float)(cy - ly), wx = (float)(cx - lx);
+        const int iz = affine_index(lz, -2.0, vd.D), iy = affine_index(ly, -2.0, vd.H), ix = affine_index(lx, -2.0, vd.W);
+        const bool z0in = iz >= 0 && iz < vd.D, z1in = iz + 1 >= 0 && iz + 1 < vd.D;
+        const bool y0in = iy >= 0 && iy < vd.H, y1in = iy + 1 >= 0 && iy + 1 < vd.H;
+        const bool x0in = ix >= 0 && ix < vd.W, x1in = ix + 1 >= 0 && ix + 1 < vd.W;
+        const long long o = (long long)iz * HW + (long long)iy * vd.W + ix;            // read only where the tap is inside
+        for (int c = 0; c < C; ++c) {
+            const float* s = vd.img + (long long)c * V + o;
+            const float t000 = z0in && y0in && x0in ? s[0] : pad, t001 = z0in && y0in && x1in ? s[1] : pad;
+            const float t010 = z0in && y1in && x0in ? s[vd.W] : pad, t011 = z0in && y1in && x1in ? s[vd.W + 1] : pad;
+            const float t100 = z1in && y0in && x0in ? s[HW] : pad, t101 = z1in && y0in && x1in ? s[HW + 1] : pad;
+            const float t110 = z1in && y1in && x0in ? s[HW + vd.W] : pad, t111 = z1in && y1in && x1in ? s[HW + vd.W + 1] : pad;
+            const float v00 = t000 + wx * (t001 - t000), v01 = t010 + wx * (t011 - t010);
+            const float v10 = t100 + wx * (t101 - t100), v11 = t110 + wx * (t111 - t110);
+            const float v0 = v00 + wy * (v01 - v00), v1 = v10 + wy * (v11 - v10);
+            const float v = v0 + wz * (v1 - v0);
+            DT<TO>::st(out_img + ((long long)b * C + c) * R3 + orow + x, (v + row.shift) * row.scale);
+        }
+        const int nz = affine_index(floor(cz + 0.5), -1.0, vd.D), ny = affine_index(floor(cy + 0.5), -1.0, vd.H);
+        const int nx = affine_index(floor(cx + 0.5), -1.0, vd.W);
+        const bool in = vd.lab && nz >= 0 && nz < vd.D && ny >= 0 && ny < vd.H && nx >= 0 && nx < vd.W;
+        out_lab[(long long)b * R3 + orow + x] = in ? (float)vd.lab[(long long)nz * HW + (long long)ny * vd.W + nx] : 0.0f;
+    }
+}
+
 inline bool dims_ok(int C, int D, int H, int W) { return C >= 1 && D >= 1 && H >= 1 && W >= 1 && D <= 65535 && H <= 65535; }
 inline dim3 row_grid(int D, int H, int W) { return dim3((unsigned)ceil_div(W, 256), (unsigned)H, (unsigned)D); }
 
@@ -389,6 +466,23 @@ int msseg_aug_crop_multi(const void* volumes, int nvol, const void* rows, const 
                            (const PickRow*)rows, picks, (bf16_t*)out_img, out_lab, C, R);
     else MSSEG_FAIL(MSSEG_EINVAL, "aug_crop_multi: bad dtype");
     MSSEG_CHECK_LAUNCH("aug_crop_multi");
+    return MSSEG_OK;
+}
+
+int msseg_aug_crop_affine(const void* volumes, int nvol, const void* rows, const int* picks, const double* mats, int npatch,
+                          int C, void* out_img, int out_dtype, float* out_lab, int R, float pad_value, msseg_stream_t stream) {
+    if (!volumes || !rows || !picks || !mats || !out_img || !out_lab || nvol < 1 || C < 1 || npatch < 1 || npatch > 65535 ||
+        R < 1 || R > 65535)
+        MSSEG_FAIL(MSSEG_EINVAL, "aug_crop_affine: bad args");
+    dim3 block(32, 8), grid((unsigned)ceil_div(R, 8), (unsigned)R, (unsigned)npatch);
+    if (out_dtype == MSSEG_F32)
+        hipLaunchKernelGGL(aug_crop_affine_kernel<float>, grid, block, 0, (hipStream_t)stream, (const VolDesc*)volumes, nvol,
+                           (const PickRow*)rows, picks, mats, (float*)out_img, out_lab, C, R, pad_value);
+    else if (out_dtype == MSSEG_BF16)
+        hipLaunchKernelGGL(aug_crop_affine_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (const VolDesc*)volumes, nvol,
+                           (const PickRow*)rows, picks, mats, (bf16_t*)out_img, out_lab, C, R, pad_value);
+    else MSSEG_FAIL(MSSEG_EINVAL, "aug_crop_affine: bad dtype");
+    MSSEG_CHECK_LAUNCH("aug_crop_affine");
     return MSSEG_OK;
 }
 

@@ -6,7 +6,8 @@ second per GPU that chain is the bottleneck directly in front of the hot path.  
 label map stay on the device (288 GB of HBM hold hundreds of CT volumes), the random draws of one batch -- crop centre
 per patch (foreground / background voxel picked with the reference's pos : neg odds), three flip coins, a quarter-turn
 count, intensity shift and scale -- are made on the host with a seeded ``numpy`` generator, and ONE gather kernel
-(``msseg_aug_crop_batch``) writes the batch.  ``iter(DevicePatchLoader)`` yields the batch dict the engine consumes,
+(``msseg_aug_crop_batch``) writes the batch; with ``affine_prob > 0`` a rotation + zoom matrix per patch is drawn as well and
+the gather samples the volume under it (``msseg_aug_crop_affine``, still one launch).  ``iter(DevicePatchLoader)`` yields the batch dict the engine consumes,
 including the crop centre record the reference's transform fork adds (``data/transforms.py:411``).
 """
 from __future__ import annotations
@@ -56,14 +57,59 @@ def draw_rows(rng: np.random.Generator, n, fg_count, bg_count, cfg_like):
     return rows
 
 
+def affine_matrix(angles_rad, zoom):
+    """R0(a0) . R1(a1) . R2(a2) / zoom in float64: Rk is the right-handed rotation about tensor axis k of (D, H, W), zoom > 1
+    magnifies.  The gather reads the volume at patch centre + M (patch index - (roi - 1) / 2)."""
+    a0, a1, a2 = (float(a) for a in angles_rad)
+    c0, s0, c1, s1, c2, s2 = np.cos(a0), np.sin(a0), np.cos(a1), np.sin(a1), np.cos(a2), np.sin(a2)
+    r0 = np.array([[1.0, 0.0, 0.0], [0.0, c0, -s0], [0.0, s0, c0]], dtype=np.float64)
+    r1 = np.array([[c1, 0.0, s1], [0.0, 1.0, 0.0], [-s1, 0.0, c1]], dtype=np.float64)
+    r2 = np.array([[c2, -s2, 0.0], [s2, c2, 0.0], [0.0, 0.0, 1.0]], dtype=np.float64)
+    return (r0 @ r1 @ r2) / float(zoom) + 0.0                  # + 0.0: no negative zeros (zero angles, zoom 1 give eye(3))
+
+
+def affine_config(prob, rotate, zoom):
+    """--t_affine_prob / --t_affine_rotate / --t_affine_zoom as (probability, three angle bounds in degrees, (lo, hi));
+    a ValueError names the flag"""
+    prob = float(prob)
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError(f"--t_affine_prob takes a probability in [0, 1], got {prob!r}")
+    rot = tuple(rotate) if isinstance(rotate, (tuple, list)) else (rotate,)
+    if len(rot) == 1:
+        rot = rot * 3
+    if len(rot) != 3 or any(not float(a) >= 0.0 for a in rot):
+        raise ValueError(f"--t_affine_rotate takes one or three angles >= 0 in degrees, got {rotate!r}")
+    zm = tuple(zoom) if isinstance(zoom, (tuple, list)) else (zoom,)
+    if len(zm) != 2 or not 0.0 < float(zm[0]) <= float(zm[1]):
+        raise ValueError(f"--t_affine_zoom takes LO HI with 0 < LO <= HI, got {zoom!r}")
+    return prob, tuple(float(a) for a in rot), (float(zm[0]), float(zm[1]))
+
+
+def draw_affine(rng: np.random.Generator, n, affine):
+    """the matrices of n patches, float64 [n, 3, 3]; affine = affine_config(...).  Per patch one uniform number and, only if
+    the patch is chosen, three angles and the zoom; a patch not chosen gets the identity.  Probability 0 draws nothing."""
+    prob, rot, (lo, hi) = affine
+    mats = np.tile(np.eye(3, dtype=np.float64), (n, 1, 1))
+    if prob <= 0.0:
+        return mats
+    for j in range(n):
+        if rng.random() < prob:
+            ang = [np.deg2rad(float(rng.uniform(-a, a))) for a in rot]
+            mats[j] = affine_matrix(ang, float(rng.uniform(lo, hi)))
+    return mats
+
+
 class DevicePatchLoader:
-    """len() batches of `batch` patches of roi^3 from ONE cached volume; deterministic per seed."""
+    """len() batches of `batch` patches of roi^3 from ONE cached volume; deterministic per seed.  affine_prob > 0 sends the
+    batch through msseg_aug_crop_affine (see DeviceDatasetLoader); the matrices follow the batch's other draws."""
 
     def __init__(self, image: torch.Tensor, label: torch.Tensor, roi: int, batch: int, n_batches: int, device, seed=13,
                  pos=1.0, neg=1.0, flip_prob=0.0, rot_prob=0.0, shift_os=0.1, shift_prob=0.0, scale_f=0.1, scale_prob=0.0,
-                 image_threshold=0.0, out_dtype=torch.float32):
+                 image_threshold=0.0, out_dtype=torch.float32, affine_prob=0.0, affine_rotate=30.0, affine_zoom=(0.7, 1.4),
+                 affine_pad=0.0):
         if image.dim() != 4 or label.dim() != 3:
             raise ValueError("image [C, D, H, W] and label [D, H, W] expected")
+        self.affine, self.affine_pad = affine_config(affine_prob, affine_rotate, affine_zoom), float(affine_pad)
         self.img = image.to(device=device, dtype=torch.float32).contiguous()
         self.lab = label.to(device=device, dtype=torch.uint8).contiguous()
         self.roi, self.batch, self.n, self.dev, self.out_dtype = int(roi), int(batch), int(n_batches), device, out_dtype
@@ -74,7 +120,11 @@ class DevicePatchLoader:
         flat_lab = self.lab.reshape(-1)
         self.fg = torch.nonzero(flat_lab > 0).reshape(-1)
         self.bg = torch.nonzero((flat_lab == 0) & (self.img[0].reshape(-1) > image_threshold)).reshape(-1)
-        self.last_rows = None
+        self.last_rows = self.last_picks = self.last_mats = None
+        self.launches = 0
+        # the affine gather addresses volumes through a descriptor table: this loader's has one entry
+        self.desc = _upload([VolumeDesc(self.img.data_ptr(), self.lab.data_ptr(), *self.img.shape)], device) \
+            if self.affine[0] > 0.0 else None
 
     def __len__(self):
         return self.n
@@ -99,11 +149,22 @@ class DevicePatchLoader:
             draws = draw_rows(self.rng, self.batch, int(self.fg.numel()), int(self.bg.numel()), self.cfg)
             rows, centers = self.rows_for(draws)
             self.last_rows = rows
-            host = torch.frombuffer(bytearray(bytes((AugRow * len(rows))(*rows))), dtype=torch.uint8)
-            table = host.to(self.dev, non_blocking=True)
             img = torch.empty(self.batch, Cc, self.roi, self.roi, self.roi, dtype=self.out_dtype, device=self.dev)
             lab = torch.empty(self.batch, 1, self.roi, self.roi, self.roi, dtype=torch.float32, device=self.dev)
-            hip.aug_crop_batch(self.img, self.lab, table, img, lab, self.roi)
+            if self.affine[0] > 0.0:
+                # the matrices are drawn after the batch's other draws; the rows and starts go to the multi-volume gather's
+                # tables (one volume, explicit crop starts)
+                mats = draw_affine(self.rng, self.batch, self.affine)
+                picks = torch.tensor([[c[0], c[1], c[2], r.z0, r.y0, r.x0, 0, 0] for r, c in zip(rows, centers)], dtype=torch.int32)
+                table = _upload([PickRow(0, PICK_VOXEL, 0, 0, r.flips, r.rotk, r.shift, r.scale) for r in rows], self.dev)
+                hip.aug_crop_affine(self.desc, 1, table, picks.to(self.dev), torch.from_numpy(mats).to(self.dev), img, lab,
+                                    self.roi, self.affine_pad)
+                self.last_picks, self.last_mats = picks, mats
+            else:
+                host = torch.frombuffer(bytearray(bytes((AugRow * len(rows))(*rows))), dtype=torch.uint8)
+                table = host.to(self.dev, non_blocking=True)
+                hip.aug_crop_batch(self.img, self.lab, table, img, lab, self.roi)
+            self.launches += 1
             aff = torch.eye(4)[None].repeat(self.batch, 1, 1)
             cen = torch.tensor(centers, dtype=torch.float32)
             yield {"image": img, "label": lab,
@@ -250,11 +311,17 @@ class DeviceDatasetLoader:
     """len() batches of `batch` patches of roi^3 drawn across the cached `volumes` (records of preprocess_volume): a seeded
     permutation of the volumes per epoch, `patches_per_image` consecutive patches from each, the per-patch draws of
     draw_rows; msseg_pick_voxels resolves the crop centres from the per-slice candidate counts and msseg_aug_crop_multi
-    writes the batch in ONE launch.  crop = "fgbg" (RandCropByPosNegLabeld) or "spatial" (RandSpatialCropd)."""
+    writes the batch in ONE launch.  crop = "fgbg" (RandCropByPosNegLabeld) or "spatial" (RandSpatialCropd).
+    affine_prob > 0: each patch is, with that probability, rotated (angles from U(-affine_rotate, affine_rotate) degrees per
+    tensor axis) and zoomed (factor from U(*affine_zoom)) about its centre by sampling the cached volume under
+    affine_matrix(...) in msseg_aug_crop_affine, still one launch; taps outside the volume read affine_pad.  The matrices
+    of the last batch are in last_mats.  With affine_prob == 0 nothing changes: same kernels, same generator stream."""
 
     def __init__(self, volumes, roi, batch, n_batches, patches_per_image=1, device=None, seed=13, crop="fgbg", pos=1.0,
                  neg=1.0, flip_prob=0.0, rot_prob=0.0, shift_os=0.1, shift_prob=0.0, scale_f=0.1, scale_prob=0.0,
-                 image_threshold=0.0, out_dtype=torch.float32):
+                 image_threshold=0.0, out_dtype=torch.float32, affine_prob=0.0, affine_rotate=30.0, affine_zoom=(0.7, 1.4),
+                 affine_pad=0.0):
+        self.affine, self.affine_pad = affine_config(affine_prob, affine_rotate, affine_zoom), float(affine_pad)
         if not volumes:
             raise ValueError("DeviceDatasetLoader needs at least one cached volume")
         if crop not in ("fgbg", "spatial"):
@@ -285,7 +352,7 @@ class DeviceDatasetLoader:
                 self.cum.append((np.cumsum(c[:, 0]), np.cumsum(c[:, 1])))
         self.order, self.taken = [], 0
         self.launches = 0
-        self.last_rows = self.last_picks = None
+        self.last_rows = self.last_picks = self.last_mats = None
 
     def __len__(self):
         return self.n
@@ -322,7 +389,13 @@ class DeviceDatasetLoader:
         R = self.roi
         for _ in range(self.n):
             vis = [self._next_volume() for _ in range(self.batch)]
-            made = [self._row(vi) for vi in vis]
+            if self.affine[0] > 0.0:                             # a patch's matrix is drawn right after its other draws
+                made, mats = [], np.empty((self.batch, 3, 3), dtype=np.float64)
+                for j, vi in enumerate(vis):
+                    made.append(self._row(vi))
+                    mats[j] = draw_affine(self.rng, 1, self.affine)[0]
+            else:
+                made, mats = [self._row(vi) for vi in vis], None
             rows = [m[0] for m in made]
             table = _upload(rows, self.dev)
             if self.crop == "spatial":
@@ -334,11 +407,15 @@ class DeviceDatasetLoader:
                 hip.pick_voxels(self.desc, len(self.vols), table, self.batch, R, self.thr, picks)
             img = torch.empty(self.batch, self.C, R, R, R, dtype=self.out_dtype, device=self.dev)
             lab = torch.empty(self.batch, 1, R, R, R, dtype=torch.float32, device=self.dev)
-            hip.aug_crop_multi(self.desc, len(self.vols), table, picks, img, lab, R)
+            if mats is None:
+                hip.aug_crop_multi(self.desc, len(self.vols), table, picks, img, lab, R)
+            else:
+                hip.aug_crop_affine(self.desc, len(self.vols), table, picks, torch.from_numpy(mats).to(self.dev), img, lab, R,
+                                    self.affine_pad)
             self.launches += 1
             if self.crop != "spatial":
                 host = picks.cpu()                               # the one small device-to-host copy of the batch
-            self.last_rows, self.last_picks = rows, host
+            self.last_rows, self.last_picks, self.last_mats = rows, host, mats
             cen = host[:, :3].float()
             recs = [self.vols[vi] for vi in vis]
             sizes = [[float(r["lab"].shape[a]) for r in recs] for a in range(3)]

@@ -142,6 +142,7 @@ SIGNATURES = {
     "msseg_slab_counts": ([_vp, _vp, _i, _i, _i, _f, _vp, _vp], _i),
     "msseg_pick_voxels": ([_vp, _i, _vp, _i, _i, _f, _vp, _vp], _i),
     "msseg_aug_crop_multi": ([_vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp], _i),
+    "msseg_aug_crop_affine": ([_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _f, _vp], _i),
     "msseg_sw_gather_batch": ([_vp, _ll, _vp, _ll, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp], _i),
     "msseg_sw_blend_batch": ([_vp, _ll, _i, _vp, _vp, _ll, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "msseg_deconv_k2s2_bwd_partials_ok": ([_i, _i, _i], _i),
@@ -1512,6 +1513,22 @@ def aug_crop_multi(volumes, nvol, rows, picks, out_img, out_lab, roi):
     assert out_lab.dtype == torch.float32 and out_lab.numel() == npatch * roi ** 3 and tuple(out_img.shape[2:]) == (roi,) * 3
     _ck(lib().msseg_aug_crop_multi(_p(volumes), nvol, _p(rows), _p(picks), npatch, out_img.shape[1], _p(out_img), dt(out_img),
                                    _p(out_lab), int(roi), _stream()), "aug_crop_multi")
+    return out_img, out_lab
+
+
+def aug_crop_affine(volumes, nvol, rows, picks, mats, out_img, out_lab, roi, pad_value=0.0):
+    """aug_crop_multi sampling the cached volume under a matrix per patch, in one launch: mats float64 [n, 3, 3] on the
+    device (row-major M; source = patch centre + M (patch index - (roi - 1) / 2)), image trilinear with taps outside the
+    volume reading pad_value, label nearest with 0 outside.  Identity matrices give aug_crop_multi's output bit for bit.
+    Tables and preconditions as aug_crop_multi."""
+    _need_gpu(volumes, rows, picks, mats, out_img, out_lab)
+    npatch = out_img.shape[0]
+    assert volumes.numel() >= nvol * 32 and rows.numel() >= npatch * 32 and picks.numel() >= npatch * 8
+    assert picks.dtype == torch.int32 and picks.is_contiguous() and out_img.is_contiguous() and out_lab.is_contiguous()
+    assert mats.dtype == torch.float64 and mats.is_contiguous() and mats.numel() == npatch * 9
+    assert out_lab.dtype == torch.float32 and out_lab.numel() == npatch * roi ** 3 and tuple(out_img.shape[2:]) == (roi,) * 3
+    _ck(lib().msseg_aug_crop_affine(_p(volumes), nvol, _p(rows), _p(picks), _p(mats), npatch, out_img.shape[1], _p(out_img),
+                                    dt(out_img), _p(out_lab), int(roi), float(pad_value), _stream()), "aug_crop_affine")
     return out_img, out_lab
 
 

@@ -62,7 +62,10 @@ def file_loaders(cfg, device, seed, vol):
                                        shift_os=cfg.t_intensity_shift_os, shift_prob=cfg.t_intensity_shift_prob,
                                        scale_f=cfg.t_intensity_scale_factors, scale_prob=cfg.t_intensity_scale_prob,
                                        # image_threshold=0 of the reference, on the scale of the cached volume
-                                       image_threshold=normalised_zero(cfg))
+                                       image_threshold=normalised_zero(cfg),
+                                       # rotation + zoom inside the gather; outside the volume lies what the cache pads with
+                                       affine_prob=cfg.t_affine_prob, affine_rotate=cfg.t_affine_rotate,
+                                       affine_zoom=cfg.t_affine_zoom, affine_pad=normalised_zero(cfg))
     return loader_train, DeviceVolumeLoader(rec_val)
 
 
@@ -81,7 +84,8 @@ def synthetic_loaders(cfg, device, seed, vol):
                                          flip_prob=cfg.t_flip_prob, rot_prob=cfg.t_rot_prob,
                                          shift_os=cfg.t_intensity_shift_os, shift_prob=cfg.t_intensity_shift_prob,
                                          scale_f=cfg.t_intensity_scale_factors, scale_prob=cfg.t_intensity_scale_prob,
-                                         image_threshold=-1e9)
+                                         image_threshold=-1e9, affine_prob=cfg.t_affine_prob,
+                                         affine_rotate=cfg.t_affine_rotate, affine_zoom=cfg.t_affine_zoom, affine_pad=0.0)
     else:
         loader_train = SyntheticLoader(cfg.synthetic_steps, cfg.n_images_per_batch, vol, cfg.in_chans, cfg.output_dim, seed)
     loader_val = SyntheticLoader(1, 1, vval, cfg.in_chans, cfg.output_dim, seed + 7, with_crop_info=False)
