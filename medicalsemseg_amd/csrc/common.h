@@ -182,5 +182,13 @@ MSSEG_DEVFN void block_rows_sum(const float* rows, int R, int L, float* lds, lon
 #define MSSEG_SCRATCH_COUNTER_BYTES 256
 #define MSSEG_STATS_NMAX 8
 
+// the reduce scratch that the deterministic grid-wide reductions work in: counter block + partial rows
+static inline int scratch_ok(const void* scratch, size_t bytes, const char* who) {
+    if (!scratch || ((uintptr_t)scratch & 255) || bytes < msseg_reduce_scratch_bytes())
+        MSSEG_FAIL(MSSEG_EWORKSPACE, "%s: needs a zero-initialised, 256-byte aligned scratch of %zu bytes", who,
+                   msseg_reduce_scratch_bytes());
+    return MSSEG_OK;
+}
+
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline long long ceil_div_ll(long long a, long long b) { return (a + b - 1) / b; }

@@ -25,6 +25,7 @@
 // Weight image = four msseg_pack_weights images back to back (hip.pack_conv_k3_c48): main [blk][27 taps][q][16][16 B],
 // rest1 [blk][kd * 3 + kh][..] (kw pair), rest2 [blk][kh][..] (kd pair at kw = 2), rest3 [blk][kh][..] (kd 2, kw 2).
 #include "k3pp.h"
+#include "pingpong.h"
 
 #include <stdlib.h>
 
@@ -46,31 +47,12 @@ constexpr int NGRP_LDS = 10;                            // groups whose weight f
 constexpr int NRES = (NGRP - NGRP_LDS) * 3;             // register-resident fragments
 constexpr int W_BYTES = NGRP_LDS * 3 * 1024;
 constexpr int NMAX = 4;                                 // samples with fused statistics
-constexpr int STAT_FLOATS = 8 * NMAX * 16 * 2;
+using Stats = StatAcc<1, NMAX, true>;
 constexpr int NTHREADS = 512;
 constexpr int LDS_BYTES = W_BYTES + 2 * HALO_BYTES;
-static_assert(LDS_BYTES + STAT_FLOATS * 4 <= 160 * 1024, "LDS budget");
+static_assert(LDS_BYTES + Stats::LDS_FLOATS * 4 <= 160 * 1024, "LDS budget");
 
-__device__ u32x4_t g_c48_zero_chunk;                    // source of padding voxels
 __device__ unsigned long long g_c48_cycles[8];          // MSSEG_K3C48_TIMING build: role cycle counters of workgroup 0
-
-MSSEG_DEVFN void glds16(const void* g, void* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-
-struct TileCo { int n, d0, h0, w0; };
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-MSSEG_DEVFN unsigned pack_bf16x2(float a, float b) {
-    const bf16x2_t v = {(bf16_t)a, (bf16_t)b};
-    return __builtin_bit_cast(unsigned, v);
-}
-MSSEG_DEVFN float bf16_of_pair(unsigned u, int hi) {
-    return __builtin_bit_cast(float, hi ? (u & 0xffff0000u) : (u << 16));
-}
-MSSEG_DEVFN void acc_add(float& s, float v) { asm("v_add_f32 %0, %0, %1" : "+v"(s) : "v"(v)); }
-MSSEG_DEVFN void acc_fma(float& s, float a, float b) { asm("v_fmac_f32 %0, %1, %2" : "+v"(s) : "v"(a), "v"(b)); }
 
 // 8-byte global load that the compiler's s_waitcnt insertion does not see: a tracked load would be completed with vmcnt(0) at
 // its first use, i.e. together with the LDS-DMA pieces issued after it (the pass does not count across the two kinds).
@@ -107,29 +89,10 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3c48_kernel(const K3ppParams p) 
     const bf16_t* __restrict__ xg = (const bf16_t*)p.x;
     bf16_t* __restrict__ yg = (bf16_t*)p.y;
 
-    // ---- tile schedule (as conv3d_k3_pp.hip): each XCD walks one contiguous eighth of the tile list; the cout blocks of
-    // one grid column share the XCD, so that the halo a tile's three (or more) workgroups fetch comes out of one L2
-    const int tiles_w = (p.W + TW - 1) / TW, tiles_h = (p.H + TH - 1) / TH, tiles_d = (p.D + TD - 1) / TD;
-    const int ntiles = p.N * tiles_d * tiles_h * tiles_w;
-    int t_first, t_step, t_end;
-    if ((gridDim.x & 7) == 0) {
-        const int chunk = (ntiles + 7) >> 3, xcd = blockIdx.x & 7;
-        t_first = xcd * chunk + (blockIdx.x >> 3);
-        t_step = gridDim.x >> 3;
-        t_end = min(ntiles, (xcd + 1) * chunk);
-    } else {
-        t_first = blockIdx.x; t_step = gridDim.x; t_end = ntiles;
-    }
-    const int n_my = t_first < t_end ? (t_end - t_first + t_step - 1) / t_step : 0;
-    auto tile_of = [&](int k) {
-        int t = t_first + k * t_step;
-        TileCo tc;
-        tc.w0 = (t % tiles_w) * TW; t /= tiles_w;
-        tc.h0 = (t % tiles_h) * TH; t /= tiles_h;
-        tc.d0 = (t % tiles_d) * TD; t /= tiles_d;
-        tc.n = t;
-        return tc;
-    };
+    Sched<TD, TH, TW> sc;
+    sc.init(p.N, p.D, p.H, p.W);
+    Stats sacc;
+    sacc.init(ldsS, wave, lane);
 
     // ---- halo fill.  The LDS image is voxel-major -- [halo voxel][96 B], the voxel's 48 channels as they lie in memory --
     // so that the 64 lanes of one LDS-DMA instruction (1 KB of consecutive LDS) read consecutive 16-byte chunks of a halo
@@ -152,7 +115,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3c48_kernel(const K3ppParams p) 
     }
     // address of the zero chunk in a VGPR pair the compiler cannot rematerialise (it would re-load it from the GOT, with an
     // lgkmcnt wait, before every piece of a boundary tile)
-    unsigned long long zaddr = (unsigned long long)(uintptr_t)&g_c48_zero_chunk;
+    unsigned long long zaddr = (unsigned long long)(uintptr_t)&g_zero_chunk;
     asm volatile("" : "+v"(zaddr));
     auto load_halo = [&](const TileCo& tc) {
         unsigned char* dst = ldsH + grp * HALO_BYTES;
@@ -188,10 +151,8 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3c48_kernel(const K3ppParams p) 
 #pragma unroll
         for (int i = 0; i < NRES; ++i)
             wres[i] = *(const u32x4_t*)(wsrc + wfrag_off(NGRP_LDS + i / 3, i % 3, coutblk, ncb) + lane * 16);
-        if (STATS != 0) {
-            for (int i = tid; i < STAT_FLOATS; i += NTHREADS) ldsS[i] = 0.f;
-        }
-        if (grp == 0 && n_my > 0) load_halo(tile_of(0));
+        if (STATS != 0) sacc.zero_slots();
+        if (grp == 0 && sc.n_my > 0) load_halo(sc.tile(0));
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -262,32 +223,9 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3c48_kernel(const K3ppParams p) 
     for (int m = 0; m < TH; ++m) {
         const long long rel = ((long long)wq * p.H + m) * p.W + r;
         o_off[m] = (unsigned)(rel * p.ldy * 2 + q * 8);
-        ny_off[m] = (unsigned)(rel * p.nb_ldy * 2 + q * 8);
-        na_off[m] = (unsigned)(rel * p.nb_lda * 2 + q * 8);
+        ny_off[m] = (unsigned)(rel * p.fused.nb_ldy * 2 + q * 8);
+        na_off[m] = (unsigned)(rel * p.fused.nb_lda * 2 + q * 8);
     }
-    float s1[4], s2[4];
-    int s_n = -1;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s1[e] = s2[e] = 0.f;
-    auto flush_stats = [&]() {
-        if (s_n < 0) return;
-        float* slot = ldsS + ((wave * NMAX + s_n) * 16) * 2;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float a = s1[e], b = s2[e];
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) {
-                a += __shfl_xor(a, o);
-                b += __shfl_xor(b, o);
-            }
-            if (r == 0) {
-                float* sp = slot + (q * 4 + e) * 2;
-                sp[0] += a;
-                sp[1] += b;
-            }
-            s1[e] = s2[e] = 0.f;
-        }
-    };
     // One memory-role phase.  Order: the 8-byte loads the fused epilogues need for the finished tile `tc` (in-backward sums:
     // yraw and the activation of the receiving layer; accumulate mode: the stored partial sums), THEN the LDS-DMA of the
     // next tile `tn` (the slow part: 150-200 cycles per instruction while the other group's MFMAs and fragment reads run),
@@ -299,9 +237,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3c48_kernel(const K3ppParams p) 
             if (has_next) load_halo(tn);
             return;
         }
-        if constexpr (STATS != 0) {
-            if (tc.n != s_n) { flush_stats(); s_n = tc.n; }
-        }
+        if constexpr (STATS != 0) sacc.sample(tc.n);
         const long long vox = (((long long)tc.n * p.D + tc.d0) * p.H + tc.h0) * p.W + tc.w0;
         unsigned char* ybase = (unsigned char*)yg + (vox * p.ldy + coutblk * 16) * 2;
         const bool full = tc.d0 + TD <= p.D && tc.h0 + TH <= p.H && tc.w0 + TW <= p.W;
@@ -310,16 +246,16 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3c48_kernel(const K3ppParams p) 
             const bool okdw = FULL || (tc.d0 + wq < p.D && tc.w0 + r < p.W);
             u32x2_t pre_y[TH], pre_a[TH];
             if constexpr (STATS == 2 || STATS == 3) {
-                const unsigned char* nyb = (STATS == 2) ? (const unsigned char*)p.nb_y + (vox * p.nb_ldy + coutblk * 16) * 2 : ybase;
-                const unsigned char* nab = (const unsigned char*)p.nb_a + (vox * p.nb_lda + coutblk * 16) * 2;
+                const unsigned char* nyb = (STATS == 2) ? (const unsigned char*)p.fused.nb_y + (vox * p.fused.nb_ldy + coutblk * 16) * 2 : ybase;
+                const unsigned char* nab = (const unsigned char*)p.fused.nb_a + (vox * p.fused.nb_lda + coutblk * 16) * 2;
 #pragma unroll
                 for (int m = 0; m < TH; ++m) {
                     // voxels outside the volume read the tensor's first element instead: unconditional loads, no select on
                     // a value that has not landed; the sums and stores below mask those voxels
                     const bool ok = FULL || (okdw && tc.h0 + m < p.H);
                     gload8_untracked(pre_y[m], ok ? nyb + (STATS == 2 ? ny_off[m] : o_off[m])
-                                                  : (STATS == 2 ? (const unsigned char*)p.nb_y : (const unsigned char*)yg));
-                    if constexpr (STATS == 2) gload8_untracked(pre_a[m], ok ? nab + na_off[m] : (const unsigned char*)p.nb_a);
+                                                  : (STATS == 2 ? (const unsigned char*)p.fused.nb_y : (const unsigned char*)yg));
+                    if constexpr (STATS == 2) gload8_untracked(pre_a[m], ok ? nab + na_off[m] : (const unsigned char*)p.fused.nb_a);
                 }
             }
             load_halo(tn);   // the caller passes tn = tc when there is no next tile
@@ -347,16 +283,9 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3c48_kernel(const K3ppParams p) 
                     for (int e = 0; e < 4; ++e) {
                         float v = bf16_of_pair(ob[m][e >> 1], e & 1);   // the value as stored
                         if (!FULL) v = ok ? v : 0.f;
-                        if constexpr (STATS == 1 || STATS == 3) {
-                            acc_add(s1[e], v);
-                            acc_fma(s2[e], v, v);
-                        } else {
-                            // dz = da * lrelu'(a); accumulate (sum dz, sum dz * yraw); xhat is formed by the finalising block
-                            const float av = bf16_of_pair(pre_a[m][e >> 1], e & 1);
-                            const float dz = v * (av > 0.f ? 1.0f : p.nb_slope);
-                            acc_add(s1[e], dz);
-                            acc_fma(s2[e], dz, bf16_of_pair(pre_y[m][e >> 1], e & 1));
-                        }
+                        if constexpr (STATS == 1 || STATS == 3) sacc.add(0, e, v);
+                        else sacc.add_inbwd(0, e, v, bf16_of_pair(pre_a[m][e >> 1], e & 1), p.fused.nb_slope,
+                                          bf16_of_pair(pre_y[m][e >> 1], e & 1));
                     }
                 }
             }
@@ -367,14 +296,14 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3c48_kernel(const K3ppParams p) 
 
     // ---- phases ----------------------------------------------------------------------------------------
     unsigned long long tcyc[6] = {0, 0, 0, 0, 0, 0};
-    for (int ph = 0; ph <= n_my; ++ph) {
+    for (int ph = 0; ph <= sc.n_my; ++ph) {
         unsigned long long t0 = 0;
         if constexpr (TIMING) t0 = __builtin_readcyclecounter();
         if ((ph & 1) == grp) {
-            if (ph < n_my) compute();
+            if (ph < sc.n_my) compute();
             if constexpr (TIMING) tcyc[0] += __builtin_readcyclecounter() - t0;
         } else {
-            memory_phase(ph >= 1, tile_of(ph >= 1 ? ph - 1 : 0), ph + 1 < n_my, tile_of(ph + 1 < n_my ? ph + 1 : (ph >= 1 ? ph - 1 : 0)));
+            memory_phase(ph >= 1, sc.tile(ph >= 1 ? ph - 1 : 0), ph + 1 < sc.n_my, sc.tile(ph + 1 < sc.n_my ? ph + 1 : (ph >= 1 ? ph - 1 : 0)));
             if constexpr (TIMING) tcyc[2] += __builtin_readcyclecounter() - t0;
         }
         if constexpr (TIMING) t0 = __builtin_readcyclecounter();
@@ -387,58 +316,30 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3c48_kernel(const K3ppParams p) 
         if (blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && wave == 0) {
 #pragma unroll
             for (int k = 0; k < 5; ++k) g_c48_cycles[k] = tcyc[k];
-            g_c48_cycles[5] = (unsigned long long)n_my;
+            g_c48_cycles[5] = (unsigned long long)sc.n_my;
         }
     }
 
-    // ---- fused reductions: waves -> workgroup partial row; rows are added by msseg_k3_stats_finalize (fixed order) ----
-    if constexpr (STATS != 0) {
-        flush_stats();
-        __syncthreads();
-        const int PN = p.N * 16 * 2;
-        float* wsp = p.stats_ws + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * PN;
-        for (int i = tid; i < PN; i += NTHREADS) {
-            float s = 0.f;
-#pragma unroll
-            for (int wv = 0; wv < 8; ++wv) s += ldsS[wv * NMAX * 32 + i];
-            wsp[i] = s;
-        }
-    }
-}
-
-int grid_x(const K3ppParams& p) {
-    const int ncb = p.M / 16;
-    const int tiles = p.N * ceil_div(p.D, TD) * ceil_div(p.H, TH) * ceil_div(p.W, TW);
-    int gx = msseg_num_cus() / ncb;
-    gx &= ~7;
-    if (gx < 8) gx = 8;
-    if (gx > tiles) gx = tiles;
-    return gx;
+    // ---- fused reductions: waves -> workgroup partial row; rows are added by msseg_k3_fused_finalize (fixed order) ----
+    if constexpr (STATS != 0) sacc.finish(p.fused.stats_ws, p.N);
 }
 
 template <int STATS, int TIMING = 0> int launch(const K3ppParams& p, hipStream_t stream) {
-    const int lds = LDS_BYTES + (STATS ? STAT_FLOATS * 4 : 0);
+    const int lds = LDS_BYTES + (STATS ? Stats::LDS_FLOATS * 4 : 0);
     auto kern = k3c48_kernel<STATS, TIMING>;
     static msseg_lds_attr_once attr;
     if (!attr.ensure((const void*)kern, lds)) MSSEG_FAIL(MSSEG_ELAUNCH, "conv3d_k3_c48: cannot set dynamic LDS size %d", lds);
-    const int ncb = p.M / 16, gx = grid_x(p);
+    const int ncb = p.M / 16, gx = msseg_k3_grid_x(1, ncb, msseg_k3_tiles(p.N, p.D, p.H, p.W));
     MSSEG_KTIMED("k3c48_kernel", stream, hipLaunchKernelGGL(kern, dim3(gx, ncb, 1), dim3(NTHREADS), lds, stream, p));
     MSSEG_CHECK_LAUNCH("conv3d_k3_c48");
-    if (STATS != 0) {
-        K3FinParams f{};
-        f.ws = p.stats_ws; f.R = gx; f.N = p.N; f.coutb = 16; f.M = p.M; f.stats = p.stats;
-        f.nb_stats = (STATS == 2) ? p.nb_stats : nullptr; f.nb_eps = p.nb_eps; f.nb_S = p.nb_S;
-        f.nb_dgamma = p.nb_dgamma; f.nb_dbeta = p.nb_dbeta; f.nb_acc = p.nb_acc;
-        return msseg_k3_stats_finalize(f, ncb, stream);
-    }
-    return MSSEG_OK;
+    return STATS != 0 ? msseg_k3_fused_finalize(p.fused, gx, p.N, 16, p.M, STATS == 2, ncb, stream) : MSSEG_OK;
 }
 
 }  // namespace
 
 bool msseg_k3c48_shape_ok(int N, int D, int H, int W, int M) {
     if (M % 16 || M < 16 || M > 256 || N < 1 || N > NMAX) return false;
-    const long long tiles = (long long)N * ceil_div(D, TD) * ceil_div(H, TH) * ceil_div(W, TW);
+    const long long tiles = msseg_k3_tiles(N, D, H, W);
     if (tiles > 0x7fffffffLL) return false;
     if ((long long)(PD + 1) * H * W * 256 * 2 >= 0x7fffffffLL) return false;   // 32-bit halo-relative offsets (ldx <= 256)
     // two tiles per workgroup are the minimum for the two groups to overlap at all
@@ -449,18 +350,18 @@ bool msseg_k3c48_eligible(const K3ppParams& p) {
     if (p.K != 48 || !msseg_k3c48_shape_ok(p.N, p.D, p.H, p.W, p.M)) return false;
     if ((p.ldx % 8) || p.ldx > 256 || (p.ldy % 4) || ((uintptr_t)p.x & 15) || ((uintptr_t)p.y & 7)) return false;
     if (p.bias && ((uintptr_t)p.bias & 15)) return false;
-    if (p.nb_y && ((p.nb_ldy % 4) || (p.nb_lda % 4) || ((uintptr_t)p.nb_y & 7) || ((uintptr_t)p.nb_a & 7))) return false;
+    if (p.fused.nb_y && ((p.fused.nb_ldy % 4) || (p.fused.nb_lda % 4) || ((uintptr_t)p.fused.nb_y & 7) || ((uintptr_t)p.fused.nb_a & 7))) return false;
     return true;
 }
 
 int msseg_k3c48_launch(const K3ppParams& p, hipStream_t stream) {
     if (p.accumulate) {
-        if (p.stats == nullptr || p.nb_y != nullptr) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_c48: accumulate mode comes with forward statistics");
+        if (p.fused.stats == nullptr || p.fused.nb_y != nullptr) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_c48: accumulate mode comes with forward statistics");
         return launch<3>(p, stream);
     }
     static const bool timing = getenv("MSSEG_K3C48_TIMING") != nullptr;   // tools/bench_c48.py
-    if (p.stats == nullptr) return timing ? launch<0, 1>(p, stream) : launch<0>(p, stream);
-    if (p.nb_y == nullptr) return launch<1>(p, stream);
+    if (p.fused.stats == nullptr) return timing ? launch<0, 1>(p, stream) : launch<0>(p, stream);
+    if (p.fused.nb_y == nullptr) return launch<1>(p, stream);
     return timing ? launch<2, 1>(p, stream) : launch<2>(p, stream);
 }
 

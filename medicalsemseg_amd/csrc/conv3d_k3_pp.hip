@@ -33,6 +33,7 @@
 // adjacent q) then cover the 16 slots of a 256-byte bank window exactly once for every b.  bit2(v) of a read at
 // lane voxel + constant offset depends on (offset mod 8): eight per-lane base addresses, the offset stays an immediate.
 #include "k3pp.h"
+#include "pingpong.h"
 
 #include <type_traits>
 
@@ -44,29 +45,11 @@ constexpr int HV = PD * PH * PW;                        // 648 halo voxels
 constexpr int PLANE = ((HV * 16 + 255) / 256) * 256;    // one 16-byte channel chunk of every halo voxel
 constexpr int HALO_BYTES = 4 * PLANE;
 constexpr int W_BYTES = 27 * 4 * 32 * 16;
-constexpr int STAT_FLOATS = 8 * MSSEG_STATS_NMAX * 32 * 2;
 constexpr int NTHREADS = 512;
 
-__device__ u32x4_t g_zero_chunk;                        // source of padding voxels
 __device__ unsigned long long g_k3pp_cycles[8];
 
-MSSEG_DEVFN void glds16(const void* g, void* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-
-struct TileCo { int n, d0, h0, w0; };
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-MSSEG_DEVFN unsigned pack_bf16x2(float a, float b) {            // one v_cvt_pk_bf16_f32 (round to nearest even)
-    const bf16x2_t v = {(bf16_t)a, (bf16_t)b};
-    return __builtin_bit_cast(unsigned, v);
-}
-MSSEG_DEVFN float bf16_of_pair(unsigned u, int hi) {            // element `hi` of a packed pair as f32: one shift / mask
-    return __builtin_bit_cast(float, hi ? (u & 0xffff0000u) : (u << 16));
-}
-MSSEG_DEVFN void acc_add(float& s, float v) { asm("v_add_f32 %0, %0, %1" : "+v"(s) : "v"(v)); }
-MSSEG_DEVFN void acc_fma(float& s, float a, float b) { asm("v_fmac_f32 %0, %1, %2" : "+v"(s) : "v"(a), "v"(b)); }
+using Stats = StatAcc<2, MSSEG_STATS_NMAX, true>;
 
 template <int STATS, int TIMING>
 __global__ __launch_bounds__(NTHREADS, 1) void k3pp_kernel(const K3ppParams p) {
@@ -83,29 +66,10 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3pp_kernel(const K3ppParams p) {
     const bf16_t* __restrict__ xg = (const bf16_t*)p.x;
     bf16_t* __restrict__ yg = (bf16_t*)p.y;
 
-    // ---- tile schedule: each XCD (workgroup id mod 8) walks one contiguous eighth of the tile list, so that
-    // neighbouring tiles, which share halo voxels, are fetched through the same L2 at about the same time
-    const int tiles_w = (p.W + TW - 1) / TW, tiles_h = (p.H + TH - 1) / TH, tiles_d = (p.D + TD - 1) / TD;
-    const int ntiles = p.N * tiles_d * tiles_h * tiles_w;
-    int t_first, t_step, t_end;
-    if ((gridDim.x & 7) == 0) {
-        const int chunk = (ntiles + 7) >> 3, xcd = blockIdx.x & 7;
-        t_first = xcd * chunk + (blockIdx.x >> 3);
-        t_step = gridDim.x >> 3;
-        t_end = min(ntiles, (xcd + 1) * chunk);
-    } else {
-        t_first = blockIdx.x; t_step = gridDim.x; t_end = ntiles;
-    }
-    const int n_my = t_first < t_end ? (t_end - t_first + t_step - 1) / t_step : 0;
-    auto tile_of = [&](int k) {
-        int t = t_first + k * t_step;
-        TileCo tc;
-        tc.w0 = (t % tiles_w) * TW; t /= tiles_w;
-        tc.h0 = (t % tiles_h) * TH; t /= tiles_h;
-        tc.d0 = (t % tiles_d) * TD; t /= tiles_d;
-        tc.n = t;
-        return tc;
-    };
+    Sched<TD, TH, TW> sc;
+    sc.init(p.N, p.D, p.H, p.W);
+    Stats sacc;
+    sacc.init(ldsS, wave, lane);
 
     // ---- halo fill: wave wq of a group issues DMA pieces wq, wq + 4, ... (1 KB each = 16 halo voxels x 4 slots).
     // The memory role shares its SIMD with a wave that issues MFMAs back to back, so its VALU instructions get an
@@ -153,10 +117,8 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3pp_kernel(const K3ppParams p) {
     {
         const unsigned char* wsrc = (const unsigned char*)p.wp + (long long)coutblk * W_BYTES;
         for (int it = wave; it < W_BYTES / 1024; it += 8) glds16(wsrc + (it * 64 + lane) * 16, ldsW + it * 1024);
-        if (STATS != 0) {
-            for (int i = tid; i < STAT_FLOATS; i += NTHREADS) ldsS[i] = 0.f;
-        }
-        if (grp == 0 && n_my > 0) load_halo(tile_of(0));
+        if (STATS != 0) sacc.zero_slots();
+        if (grp == 0 && sc.n_my > 0) load_halo(sc.tile(0));
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -231,46 +193,15 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3pp_kernel(const K3ppParams p) {
     for (int m = 0; m < TH; ++m) {
         const long long rel = ((long long)wq * p.H + m) * p.W + r;
         o_off[m] = (unsigned)(rel * p.ldy * 2 + q * 8);
-        ny_off[m] = (unsigned)(rel * p.nb_ldy * 2 + q * 8);
-        na_off[m] = (unsigned)(rel * p.nb_lda * 2 + q * 8);
+        ny_off[m] = (unsigned)(rel * p.fused.nb_ldy * 2 + q * 8);
+        na_off[m] = (unsigned)(rel * p.fused.nb_lda * 2 + q * 8);
     }
-    // running (sum, sum2) of sample s_n: per lane across tiles, reduced over the 16 voxel lanes (fixed butterfly
-    // order) into this wave's private LDS slot when the sample changes and at the end: deterministic, no atomics
-    float s1[2][4], s2[2][4];
-    int s_n = -1;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s1[j][e] = s2[j][e] = 0.f;
-    auto flush_stats = [&]() {
-        if (s_n < 0) return;
-        float* slot = ldsS + ((wave * MSSEG_STATS_NMAX + s_n) * 32) * 2;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float a = s1[j][e], b = s2[j][e];
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1) {
-                    a += __shfl_xor(a, o);
-                    b += __shfl_xor(b, o);
-                }
-                if (r == 0) {
-                    float* sp = slot + (j * 16 + q * 4 + e) * 2;
-                    sp[0] += a;
-                    sp[1] += b;
-                }
-                s1[j][e] = s2[j][e] = 0.f;
-            }
-    };
     auto epilogue = [&](const TileCo& tc) {
-        if constexpr (STATS != 0) {
-            if (tc.n != s_n) { flush_stats(); s_n = tc.n; }
-        }
+        if constexpr (STATS != 0) sacc.sample(tc.n);
         const long long vox = (((long long)tc.n * p.D + tc.d0) * p.H + tc.h0) * p.W + tc.w0;
         unsigned char* ybase = (unsigned char*)yg + (vox * p.ldy + coutblk * 32) * 2;
-        const unsigned char* nyb = (const unsigned char*)p.nb_y + (vox * p.nb_ldy + coutblk * 32) * 2;
-        const unsigned char* nab = (const unsigned char*)p.nb_a + (vox * p.nb_lda + coutblk * 32) * 2;
+        const unsigned char* nyb = (const unsigned char*)p.fused.nb_y + (vox * p.fused.nb_ldy + coutblk * 32) * 2;
+        const unsigned char* nab = (const unsigned char*)p.fused.nb_a + (vox * p.fused.nb_lda + coutblk * 32) * 2;
         const bool full = tc.d0 + TD <= p.D && tc.h0 + TH <= p.H && tc.w0 + TW <= p.W;
         auto body = [&](auto fullc) {
             constexpr bool FULL = decltype(fullc)::value;
@@ -333,16 +264,9 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3pp_kernel(const K3ppParams p) {
                         for (int e = 0; e < 4; ++e) {
                             float v = bf16_of_pair(ob[m][j][e >> 1], e & 1);   // the value as stored
                             if (!FULL) v = ok ? v : 0.f;
-                            if constexpr (STATS == 1 || STATS == 3) {
-                                acc_add(s1[j][e], v);
-                                acc_fma(s2[j][e], v, v);
-                            } else {
-                                // dz = da * lrelu'(a); accumulate (sum dz, sum dz * yraw); xhat is formed by the finalising block
-                                const float av = bf16_of_pair(a4[m][j][e >> 1], e & 1);
-                                const float dz = v * (av > 0.f ? 1.0f : p.nb_slope);
-                                acc_add(s1[j][e], dz);
-                                acc_fma(s2[j][e], dz, bf16_of_pair(y4[m][j][e >> 1], e & 1));
-                            }
+                            if constexpr (STATS == 1 || STATS == 3) sacc.add(j, e, v);
+                            else sacc.add_inbwd(j, e, v, bf16_of_pair(a4[m][j][e >> 1], e & 1), p.fused.nb_slope,
+                                              bf16_of_pair(y4[m][j][e >> 1], e & 1));
                         }
                     }
             }
@@ -352,20 +276,20 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3pp_kernel(const K3ppParams p) {
     };
 
     // ---- phases ----------------------------------------------------------------------------------------
-    for (int ph = 0; ph <= n_my; ++ph) {
+    for (int ph = 0; ph <= sc.n_my; ++ph) {
         unsigned long long t0 = 0;
         if constexpr (TIMING) t0 = __builtin_readcyclecounter();
         if ((ph & 1) == grp) {
-            if (ph < n_my) compute();
+            if (ph < sc.n_my) compute();
             if constexpr (TIMING) tcyc[0] += __builtin_readcyclecounter() - t0;
         } else {
-            if (ph + 1 < n_my) load_halo(tile_of(ph + 1));
+            if (ph + 1 < sc.n_my) load_halo(sc.tile(ph + 1));
             if constexpr (TIMING) {
                 tcyc[4] += __builtin_readcyclecounter() - t0; t0 = __builtin_readcyclecounter();
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 tcyc[5] += __builtin_readcyclecounter() - t0; t0 = __builtin_readcyclecounter();
             }
-            if (ph >= 1) epilogue(tile_of(ph - 1));
+            if (ph >= 1) epilogue(sc.tile(ph - 1));
             if constexpr (TIMING) tcyc[1] += __builtin_readcyclecounter() - t0;
         }
         if constexpr (TIMING) t0 = __builtin_readcyclecounter();
@@ -381,42 +305,19 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3pp_kernel(const K3ppParams p) {
         }
     }
 
-    // ---- fused reductions: waves -> workgroup partial row; rows are added by msseg_k3_stats_finalize (fixed order) ----
-    if constexpr (STATS != 0) {
-        flush_stats();
-        __syncthreads();
-        const int PN = p.N * 32 * 2;
-        float* wsp = p.stats_ws + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * PN;
-        for (int i = tid; i < PN; i += NTHREADS) {
-            float s = 0.f;
-#pragma unroll
-            for (int wv = 0; wv < 8; ++wv) s += ldsS[wv * MSSEG_STATS_NMAX * 64 + i];
-            wsp[i] = s;
-        }
-    }
+    // ---- fused reductions: waves -> workgroup partial row; rows are added by msseg_k3_fused_finalize (fixed order) ----
+    if constexpr (STATS != 0) sacc.finish(p.fused.stats_ws, p.N);
 }
 
 template <int STATS, int TIMING> int launch(const K3ppParams& p, hipStream_t stream) {
-    const int lds = W_BYTES + 2 * HALO_BYTES + (STATS ? STAT_FLOATS * 4 : 0);
+    const int lds = W_BYTES + 2 * HALO_BYTES + (STATS ? Stats::LDS_FLOATS * 4 : 0);
     auto kern = k3pp_kernel<STATS, TIMING>;
     static msseg_lds_attr_once attr;
     if (!attr.ensure((const void*)kern, lds)) MSSEG_FAIL(MSSEG_ELAUNCH, "conv3d_k3_pp: cannot set dynamic LDS size %d", lds);
-    const int ncb = p.M / 32;
-    const int tiles = p.N * ceil_div(p.D, TD) * ceil_div(p.H, TH) * ceil_div(p.W, TW);
-    int gx = msseg_num_cus() / ncb;
-    gx &= ~7;
-    if (gx < 8) gx = 8;
-    if (gx > tiles) gx = tiles;
+    const int ncb = p.M / 32, gx = msseg_k3_grid_x(1, ncb, msseg_k3_tiles(p.N, p.D, p.H, p.W));
     MSSEG_KTIMED("k3pp_kernel", stream, hipLaunchKernelGGL(kern, dim3(gx, ncb, 1), dim3(NTHREADS), lds, stream, p));
     MSSEG_CHECK_LAUNCH("conv3d_k3_pp");
-    if (STATS != 0) {
-        K3FinParams f{};
-        f.ws = p.stats_ws; f.R = gx; f.N = p.N; f.coutb = 32; f.M = p.M; f.stats = p.stats;
-        f.nb_stats = (STATS == 2) ? p.nb_stats : nullptr; f.nb_eps = p.nb_eps; f.nb_S = p.nb_S;
-        f.nb_dgamma = p.nb_dgamma; f.nb_dbeta = p.nb_dbeta; f.nb_acc = p.nb_acc;
-        return msseg_k3_stats_finalize(f, ncb, stream);
-    }
-    return MSSEG_OK;
+    return STATS != 0 ? msseg_k3_fused_finalize(p.fused, gx, p.N, 32, p.M, STATS == 2, ncb, stream) : MSSEG_OK;
 }
 
 }  // namespace
@@ -425,9 +326,9 @@ bool msseg_k3pp_eligible(const K3ppParams& p) {
     if (p.K != 32 || p.M % 32 || p.M > 256) return false;
     if ((p.ldx % 8) || (p.ldy % 4) || ((uintptr_t)p.x & 15) || ((uintptr_t)p.y & 7)) return false;
     if (p.bias && ((uintptr_t)p.bias & 15)) return false;
-    if (p.stats && p.N > MSSEG_STATS_NMAX) return false;
-    if (p.nb_y && ((p.nb_ldy % 4) || (p.nb_lda % 4) || ((uintptr_t)p.nb_y & 7) || ((uintptr_t)p.nb_a & 7))) return false;
-    const long long tiles = (long long)p.N * ceil_div(p.D, TD) * ceil_div(p.H, TH) * ceil_div(p.W, TW);
+    if (p.fused.stats && p.N > MSSEG_STATS_NMAX) return false;
+    if (p.fused.nb_y && ((p.fused.nb_ldy % 4) || (p.fused.nb_lda % 4) || ((uintptr_t)p.fused.nb_y & 7) || ((uintptr_t)p.fused.nb_a & 7))) return false;
+    const long long tiles = msseg_k3_tiles(p.N, p.D, p.H, p.W);
     if (tiles > 0x7fffffffLL) return false;
     // two tiles per workgroup are the minimum for the two groups to overlap at all
     return tiles * (p.M / 32) >= 2LL * msseg_num_cus();
@@ -436,11 +337,11 @@ bool msseg_k3pp_eligible(const K3ppParams& p) {
 int msseg_k3pp_launch(const K3ppParams& p, hipStream_t stream) {
     static const bool timing = getenv("MSSEG_K3PP_TIMING") != nullptr;
     if (p.accumulate) {
-        if (p.stats == nullptr || p.nb_y != nullptr) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_pp: accumulate mode comes with forward statistics");
+        if (p.fused.stats == nullptr || p.fused.nb_y != nullptr) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_pp: accumulate mode comes with forward statistics");
         return launch<3, 0>(p, stream);
     }
-    if (p.stats == nullptr) return timing ? launch<0, 1>(p, stream) : launch<0, 0>(p, stream);
-    if (p.nb_y == nullptr) return timing ? launch<1, 1>(p, stream) : launch<1, 0>(p, stream);
+    if (p.fused.stats == nullptr) return timing ? launch<0, 1>(p, stream) : launch<0, 0>(p, stream);
+    if (p.fused.nb_y == nullptr) return timing ? launch<1, 1>(p, stream) : launch<1, 0>(p, stream);
     return launch<2, 0>(p, stream);
 }
 

@@ -21,6 +21,7 @@
 // all tiles of the workgroup; at the end the two groups are added through LDS and ONE fp32 slab per workgroup is
 // written for the deterministic slab reduction in igemm_wgrad.hip.
 #include "k3pp.h"
+#include "pingpong.h"
 
 #include <stdlib.h>
 
@@ -44,30 +45,9 @@ constexpr int TAPW = 7;
 constexpr int NTHREADS = 512;
 constexpr int SLAB_FLOATS = 27 * 32 * 32;
 
-__device__ u32x4_t g_wg_zero_chunk;
 __device__ unsigned long long g_k3wg_cycles[8];
 
-MSSEG_DEVFN void glds16(const void* g, void* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-
-typedef __attribute__((address_space(3))) unsigned char lds_u8;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-
-// the pointer stays an LDS-address-space pointer up to the builtin so that constant offsets fold into the
-// instruction's 16-bit offset field (one address VGPR per lane-dependent base instead of one per read)
-MSSEG_DEVFN bf16x4_t lds_tr(lds_u8* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)p);
-}
-
-MSSEG_DEVFN u32x4_t tr_frag(lds_u8* r0, lds_u8* r1) {
-    const bf16x4_t lo = lds_tr(r0), hi = lds_tr(r1);
-    const bf16x8_t f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(u32x4_t, f);
-}
-
-struct TileCo { int n, d0, h0, w0; };
 
 // LDS halo row of the first voxel of tile row ks (td = ks / TH, th = ks % TH)
 constexpr int ks_row(int ks) { return ((ks / TH) * PH + ks % TH) * PWP; }
@@ -85,28 +65,8 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3wg_pp_kernel(const K3WgParams p
     const unsigned char* pg = (const unsigned char*)p.pten + mblk * 64;   // dy, this cout block
     const unsigned char* qg = (const unsigned char*)p.qten + kblk * 64;   // x, this cin block
 
-    // ---- tile schedule (XCD-contiguous, as in conv3d_k3_pp.hip)
-    const int tiles_w = (p.W + TW - 1) / TW, tiles_h = (p.H + TH - 1) / TH, tiles_d = (p.D + TD - 1) / TD;
-    const int ntiles = p.N * tiles_d * tiles_h * tiles_w;
-    int t_first, t_step, t_end;
-    if ((gridDim.x & 7) == 0) {
-        const int chunk = (ntiles + 7) >> 3, xcd = blockIdx.x & 7;
-        t_first = xcd * chunk + (blockIdx.x >> 3);
-        t_step = gridDim.x >> 3;
-        t_end = min(ntiles, (xcd + 1) * chunk);
-    } else {
-        t_first = blockIdx.x; t_step = gridDim.x; t_end = ntiles;
-    }
-    const int n_my = t_first < t_end ? (t_end - t_first + t_step - 1) / t_step : 0;
-    auto tile_of = [&](int k) {
-        int t = t_first + k * t_step;
-        TileCo tc;
-        tc.w0 = (t % tiles_w) * TW; t /= tiles_w;
-        tc.h0 = (t % tiles_h) * TH; t /= tiles_h;
-        tc.d0 = (t % tiles_d) * TD; t /= tiles_d;
-        tc.n = t;
-        return tc;
-    };
+    Sched<TD, TH, TW> sc;
+    sc.init(p.N, p.D, p.H, p.W);
 
     // ---- memory role: per-lane byte offsets of the DMA sources, relative to the tile's halo / tile origin.
     // Lane l of wave-instruction `it` fills row it*16 + (l >> 2), physical 16-byte slot l & 3, with the logical chunk
@@ -145,7 +105,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3wg_pp_kernel(const K3WgParams p
 #pragma unroll
             for (int j = 0; j < NIP_W; ++j) glds16(pb + p_off[j], ldsP + (wq + 4 * j) * 1024);
         } else {
-            const unsigned char* zsrc = (const unsigned char*)&g_wg_zero_chunk;
+            const unsigned char* zsrc = (const unsigned char*)&g_zero_chunk;
 #pragma unroll
             for (int j = 0; j < NIQ_W; ++j) {
                 const int it = wq + 4 * j;
@@ -224,19 +184,19 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3wg_pp_kernel(const K3WgParams p
     };
 
     // ---- prologue
-    if (grp == 0 && n_my > 0) load_tile(tile_of(0));
+    if (grp == 0 && sc.n_my > 0) load_tile(sc.tile(0));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
     unsigned long long tcyc[4] = {0, 0, 0, 0};
-    for (int ph = 0; ph < n_my; ++ph) {
+    for (int ph = 0; ph < sc.n_my; ++ph) {
         unsigned long long t0 = 0;
         if constexpr (TIMING) t0 = __builtin_readcyclecounter();
         if ((ph & 1) == grp) {
             compute();
             if constexpr (TIMING) tcyc[0] += __builtin_readcyclecounter() - t0;
         } else {
-            if (ph + 1 < n_my) load_tile(tile_of(ph + 1));
+            if (ph + 1 < sc.n_my) load_tile(sc.tile(ph + 1));
             if constexpr (TIMING) tcyc[1] += __builtin_readcyclecounter() - t0;
         }
         if constexpr (TIMING) t0 = __builtin_readcyclecounter();
@@ -290,19 +250,13 @@ bool msseg_k3wg_pp_eligible(const K3WgParams& p) {
     if ((p.ldp % 8) || (p.ldq % 8) || ((uintptr_t)p.pten & 15) || ((uintptr_t)p.qten & 15)) return false;
     const long long ldm = p.ldp > p.ldq ? p.ldp : p.ldq;
     if ((long long)(PD + 1) * p.H * p.W * ldm * 2 >= 0x7fffffffLL) return false;   // 32-bit tile-relative offsets
-    const long long tiles = (long long)p.N * ceil_div(p.D, TD) * ceil_div(p.H, TH) * ceil_div(p.W, TW);
+    const long long tiles = msseg_k3_tiles(p.N, p.D, p.H, p.W);
     if (tiles > 0x7fffffffLL) return false;
     return tiles * ceil_div(p.M, 32) * ceil_div(p.K, 32) >= 2LL * msseg_num_cus();
 }
 
 int msseg_k3wg_pp_grid(const K3WgParams& p) {
-    const int pairs = ceil_div(p.M, 32) * ceil_div(p.K, 32);
-    const int tiles = p.N * ceil_div(p.D, TD) * ceil_div(p.H, TH) * ceil_div(p.W, TW);
-    int gx = msseg_num_cus() / pairs;
-    gx &= ~7;
-    if (gx < 8) gx = 8;
-    if (gx > tiles) gx = tiles;
-    return gx;
+    return msseg_k3_grid_x(1, ceil_div(p.M, 32) * ceil_div(p.K, 32), msseg_k3_tiles(p.N, p.D, p.H, p.W));
 }
 
 int msseg_k3wg_pp_launch(const K3WgParams& p, int gx, hipStream_t stream) {

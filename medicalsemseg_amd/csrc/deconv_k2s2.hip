@@ -32,7 +32,7 @@ struct Dc2Params {
     const void* nb_y; long long nb_ldy;    // raw conv output of the layer whose activation is the coarse tensor
     const void* nb_a; long long nb_lda;    // its stored activation (sign of the pre-activation)
     float nb_slope;
-    float* stats_ws;                   // partial rows for msseg_k3_stats_finalize: [cin block][gx * N][N * 32 * 2]
+    float* stats_ws;                   // partial rows for msseg_k3_fused_finalize: [cin block][gx * N][N * 32 * 2]
     float* bias_ws;                    // partial rows [gx * N][Cout]
 };
 
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(DC_THREADS, 2) void deconv2_bwd_kernel(const Dc2Par
     __syncthreads();
     const int R = gridDim.x * p.N, row = n * gridDim.x + blockIdx.x;
     if constexpr (INBWD) {
-        // rows in the layout msseg_k3_stats_finalize sums: [cin block][R][N][32][2]; only this sample's slice is non-zero
+        // rows in the layout msseg_k3_fused_finalize sums: [cin block][R][N][32][2]; only this sample's slice is non-zero
         const int L = p.N * 64;
         for (int i = threadIdx.x; i < (CIN / 32) * L; i += DC_THREADS) {
             const int b = i / L, rem = i % L, nn = rem / 64, cl2 = rem % 64;
@@ -323,11 +323,11 @@ int msseg_deconv2_bwd_launch(const void* dy, long long lddy, const void* wp, voi
         MSSEG_CHECK_LAUNCH("deconv2_bias_finalize");
     }
     if (inbwd) {
-        K3FinParams f{};
-        f.ws = p.stats_ws; f.R = R; f.N = N; f.coutb = 32; f.M = Cin; f.stats = red;
+        K3Fused f{};
+        f.stats = red; f.stats_ws = p.stats_ws;
         f.nb_stats = fwd_stats; f.nb_eps = eps; f.nb_S = (long long)D * H * W;
         f.nb_dgamma = dgamma; f.nb_dbeta = dbeta; f.nb_acc = accumulate;
-        return msseg_k3_stats_finalize(f, ncb, stream);
+        return msseg_k3_fused_finalize(f, R, N, 32, Cin, true, ncb, stream);
     }
     return MSSEG_OK;
 }

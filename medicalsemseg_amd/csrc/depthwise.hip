@@ -266,8 +266,7 @@ int msseg_dwconv3d_k3_wgrad(const void* x, long long ldx, const void* dy, long l
     int rc = check(x, ldx, dy, lddy, N, D, H, W, C, dtype, "dwconv3d_k3_wgrad");
     if (rc) return rc;
     if (!dw && !dbias) MSSEG_FAIL(MSSEG_EINVAL, "dwconv3d_k3_wgrad: nothing to compute");
-    if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < msseg_reduce_scratch_bytes())
-        MSSEG_FAIL(MSSEG_EWORKSPACE, "dwconv3d_k3_wgrad: needs the reduce scratch of %zu bytes", msseg_reduce_scratch_bytes());
+    if (int rc = scratch_ok(scratch, scratch_bytes, "dwconv3d_k3_wgrad")) return rc;
     float* ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
     const long long NV = (long long)N * D * H * W;
     const size_t row_bytes = (size_t)28 * C * sizeof(float);

@@ -1391,13 +1391,6 @@ int msseg_pack_weights_batch(const msseg_pack_job* jobs_dev, int njobs, long lon
 
 size_t msseg_reduce_scratch_bytes(void) { return ((size_t)16 << 20) + MSSEG_SCRATCH_COUNTER_BYTES; }
 
-static int scratch_ok(const void* scratch, size_t bytes, const char* who) {
-    if (!scratch || ((uintptr_t)scratch & 255) || bytes < msseg_reduce_scratch_bytes())
-        MSSEG_FAIL(MSSEG_EWORKSPACE, "%s: needs a zero-initialised, 256-byte aligned scratch of %zu bytes", who,
-                   msseg_reduce_scratch_bytes());
-    return MSSEG_OK;
-}
-
 int msseg_layernorm_param_grad(const void* x, long long ldx, const float* mean, const float* rstd, const void* dy,
                                long long lddy, float* dgamma, float* dbeta, int accumulate, long long rows, int C,
                                void* scratch, size_t scratch_bytes, int dtype, msseg_stream_t stream) {

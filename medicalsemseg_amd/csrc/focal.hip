@@ -230,8 +230,7 @@ int msseg_focal_spatial_sum(const void* x, long long ldx, const void* g, long lo
     if (!al16(x) || !out0 || N < 1 || S < 1 || ldx < C || ldx % epc || C / epc > 256 || (mode != 0 && mode != 1) ||
         (mode == 1 && !m_in) || (g && ldg < 1))
         MSSEG_FAIL(MSSEG_EINVAL, "focal_spatial_sum: bad args");
-    if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < msseg_reduce_scratch_bytes())
-        MSSEG_FAIL(MSSEG_EWORKSPACE, "focal_spatial_sum: needs the reduce scratch of %zu bytes", msseg_reduce_scratch_bytes());
+    if (int rc = scratch_ok(scratch, scratch_bytes, "focal_spatial_sum")) return rc;
     float* part = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
     const int vslots = 256 / (C / epc);
     long long blocks = ceil_div_ll(S, (long long)vslots * 8);

@@ -44,17 +44,7 @@ struct IgemmParams {
     int vec_store;       // y / ldy allow 4-element vector stores
     int rel32_ok;        // halo-relative element offsets fit 32 bits (precomputed-offset staging path)
     int cout_block;      // 0 = msseg_cout_block(M)
-    float* stats;        // optional fused per-(n, cout) (sum, sum of squares) of the stored output
-    float* stats_ws;     // scratch partials
-    unsigned int* counter;
-    // optional fused InstanceNorm-BACKWARD reductions: this launch produces da (gradient w.r.t. the activation
-    // a = lrelu(IN(yraw))); the epilogue then accumulates red[n][c] = (sum dz, sum dz*xhat), dz = da*lrelu'(a), into
-    // `stats`, and the finalising block also emits dbeta / dgamma.
-    const void* nb_y; long long nb_ldy;
-    const void* nb_a; long long nb_lda;
-    const float* nb_stats;   // [N][M][2] forward statistics (sum, sum of squares) of yraw
-    float nb_slope, nb_eps; long long nb_S;
-    float* nb_dgamma; float* nb_dbeta; int nb_acc;
+    K3Fused fused;       // optional fused reductions of the stored output (k3pp.h)
 };
 
 template <typename T, int NTAPS, int SRC, int EPI, int TD, int TH, int TW, int WAVES, int NT, int STRIDE = 1>
@@ -109,7 +99,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void igemm_fwd_kernel(const IgemmPar
     }
     const int bbase = (q * COUTB + r) * 16;
     float* spart = (float*)(smem + C::A_BYTES + C::B_BYTES);
-    const bool do_stats = (EPI == EPI_STORE) && p.stats != nullptr;
+    const bool do_stats = (EPI == EPI_STORE) && p.fused.stats != nullptr;
     float* wpart = spart + C::STAT_FLOATS;  // [WAVES][COUTB][2] staging for the per-sample flush
     if (do_stats) {
         for (int i = tid; i < C::STAT_FLOATS; i += NTHREADS) spart[i] = 0.f;
@@ -530,7 +520,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void igemm_fwd_kernel(const IgemmPar
                     }
                     if constexpr (EPI == EPI_STORE) {
                         if (do_stats) {
-                            if (p.nb_y == nullptr) {
+                            if (p.fused.nb_y == nullptr) {
     #pragma unroll
                                 for (int e = 0; e < 4; ++e) {
                                     const float rv = (float)(T)o[e];  // statistics of the tensor as stored
@@ -542,18 +532,18 @@ __global__ __launch_bounds__(WAVES * 64, 1) void igemm_fwd_kernel(const IgemmPar
                                 // sum dz*xhat = rstd * (sum dz*yraw - mean * sum dz)
                                 f32x4_t yv, av;
                                 if constexpr (sizeof(T) == 2) {
-                                    const bf16x4_t y4 = *(const bf16x4_t*)((const T*)p.nb_y + vox * p.nb_ldy + co);
-                                    const bf16x4_t a4 = *(const bf16x4_t*)((const T*)p.nb_a + vox * p.nb_lda + co);
+                                    const bf16x4_t y4 = *(const bf16x4_t*)((const T*)p.fused.nb_y + vox * p.fused.nb_ldy + co);
+                                    const bf16x4_t a4 = *(const bf16x4_t*)((const T*)p.fused.nb_a + vox * p.fused.nb_lda + co);
     #pragma unroll
                                     for (int e = 0; e < 4; ++e) { yv[e] = (float)y4[e]; av[e] = (float)a4[e]; }
                                 } else {
-                                    yv = *(const f32x4_t*)((const T*)p.nb_y + vox * p.nb_ldy + co);
-                                    av = *(const f32x4_t*)((const T*)p.nb_a + vox * p.nb_lda + co);
+                                    yv = *(const f32x4_t*)((const T*)p.fused.nb_y + vox * p.fused.nb_ldy + co);
+                                    av = *(const f32x4_t*)((const T*)p.fused.nb_a + vox * p.fused.nb_lda + co);
                                 }
     #pragma unroll
                                 for (int e = 0; e < 4; ++e) {
                                     const float da = (float)(T)o[e];
-                                    const float dz = av[e] > 0.f ? da : da * p.nb_slope;
+                                    const float dz = av[e] > 0.f ? da : da * p.fused.nb_slope;
                                     st[j][e] += dz;
                                     st2[j][e] += dz * yv[e];
                                 }
@@ -572,48 +562,48 @@ __global__ __launch_bounds__(WAVES * 64, 1) void igemm_fwd_kernel(const IgemmPar
             if (cur_n >= 0) flush_stats(cur_n);
             __syncthreads();
             const int PN = p.N * COUTB * 2;
-            float* wsp = p.stats_ws + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * PN;
+            float* wsp = p.fused.stats_ws + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * PN;
             for (int i = tid; i < PN; i += NTHREADS) wsp[i] = spart[i];
         }
     }
 }
 
-// second step of the fused epilogue reductions: see K3FinParams (k3pp.h)
-__global__ __launch_bounds__(256) void k3_stats_finalize_kernel(const K3FinParams f) {
+// second step of the fused epilogue reductions: see msseg_k3_fused_finalize (k3pp.h); R = partial rows per cout block
+__global__ __launch_bounds__(256) void k3_stats_finalize_kernel(const K3Fused f, int R, int N, int coutb, int M, bool inbwd) {
     __shared__ __attribute__((aligned(16))) float fin[256 * 4 + 8 * 48 * 2];
     const int tid = threadIdx.x;
-    const int L = f.N * f.coutb * 2;
-    const int cbase = blockIdx.x * f.coutb;
-    if (f.nb_stats == nullptr) {
+    const int L = N * coutb * 2;
+    const int cbase = blockIdx.x * coutb;
+    if (!inbwd) {
         // forward statistics: one block per (cout block, sample) sums that sample's column slice of the partial rows
         // (with one block per cout block a thread walked 64 ... 128 rows: 5 us at N = 2, 8 us at N = 8)
-        const int n = blockIdx.y, Ls = f.coutb * 2;
-        block_rows_sum<256>(f.ws + (long long)blockIdx.x * f.R * L + n * Ls, f.R, Ls, fin, L);
+        const int n = blockIdx.y, Ls = coutb * 2;
+        block_rows_sum<256>(f.stats_ws + (long long)blockIdx.x * R * L + n * Ls, R, Ls, fin, L);
         const float* tot = fin + 256 * 4;   // [cl][2]
         for (int i = tid; i < Ls; i += 256) {
             const int cl = i >> 1, k = i & 1;
-            if (cbase + cl < f.M) f.stats[((long long)n * f.M + cbase + cl) * 2 + k] = tot[i];
+            if (cbase + cl < M) f.stats[((long long)n * M + cbase + cl) * 2 + k] = tot[i];
         }
         return;
     }
-    block_rows_sum<256>(f.ws + (long long)blockIdx.x * f.R * L, f.R, L, fin);
+    block_rows_sum<256>(f.stats_ws + (long long)blockIdx.x * R * L, R, L, fin);
     const float* tot = fin + 256 * 4;   // [n][cl][2]
-    if (tid < f.coutb && cbase + tid < f.M) {
+    if (tid < coutb && cbase + tid < M) {
         // sum dz*xhat = rstd * (sum dz*yraw - mean * sum dz); dbeta / dgamma = sums over the samples
         const int cg = cbase + tid;
         float g0 = 0.f, g1 = 0.f;
         const float inv = 1.0f / (float)f.nb_S;
-        for (int nn = 0; nn < f.N; ++nn) {
-            const float a = tot[(nn * f.coutb + tid) * 2], b0 = tot[(nn * f.coutb + tid) * 2 + 1];
-            const float fs = f.nb_stats[((long long)nn * f.M + cg) * 2], fs2 = f.nb_stats[((long long)nn * f.M + cg) * 2 + 1];
+        for (int nn = 0; nn < N; ++nn) {
+            const float a = tot[(nn * coutb + tid) * 2], b0 = tot[(nn * coutb + tid) * 2 + 1];
+            const float fs = f.nb_stats[((long long)nn * M + cg) * 2], fs2 = f.nb_stats[((long long)nn * M + cg) * 2 + 1];
             const float mean = fs * inv;
             float var = fs2 * inv - mean * mean;
             var = var > 0.f ? var : 0.f;
             const float b2 = rsqrtf(var + f.nb_eps) * (b0 - mean * a);
             g0 += a;
             g1 += b2;
-            f.stats[((long long)nn * f.M + cg) * 2 + 0] = a;
-            f.stats[((long long)nn * f.M + cg) * 2 + 1] = b2;
+            f.stats[((long long)nn * M + cg) * 2 + 0] = a;
+            f.stats[((long long)nn * M + cg) * 2 + 1] = b2;
         }
         if (f.nb_dgamma != nullptr) {
             f.nb_dbeta[cg] = f.nb_acc ? f.nb_dbeta[cg] + g0 : g0;
@@ -651,13 +641,8 @@ int launch_cfg(IgemmParams& p, hipStream_t stream) {
                                           : (TD * TH * TW == 128 ? "igemm_fwd_kernel<27,4x4x8>" : "igemm_fwd_kernel<27,2x4x8>"));
     MSSEG_KTIMED(kt_name, stream, hipLaunchKernelGGL(kern, grid, dim3(C::NTHREADS), C::LDS_BYTES, stream, p));
     MSSEG_CHECK_LAUNCH("igemm_fwd");
-    if (EPI == EPI_STORE && p.stats != nullptr) {
-        K3FinParams f{};
-        f.ws = p.stats_ws; f.R = gx; f.N = p.N; f.coutb = C::COUTB; f.M = p.M; f.stats = p.stats;
-        f.nb_stats = p.nb_y ? p.nb_stats : nullptr; f.nb_eps = p.nb_eps; f.nb_S = p.nb_S;
-        f.nb_dgamma = p.nb_dgamma; f.nb_dbeta = p.nb_dbeta; f.nb_acc = p.nb_acc;
-        return msseg_k3_stats_finalize(f, ncb, stream);
-    }
+    if (EPI == EPI_STORE && p.fused.stats != nullptr)
+        return msseg_k3_fused_finalize(p.fused, gx, p.N, C::COUTB, p.M, p.fused.nb_y != nullptr, ncb, stream);
     return MSSEG_OK;
 }
 
@@ -719,8 +704,8 @@ int check_common(const void* x, long long ldx, const void* wp, const void* y, lo
 
 }  // namespace
 
-int msseg_k3_stats_finalize(const K3FinParams& f, int ncb, hipStream_t stream) {
-    hipLaunchKernelGGL(k3_stats_finalize_kernel, dim3(ncb, f.nb_stats ? 1 : f.N), dim3(256), 0, stream, f);
+int msseg_k3_fused_finalize(const K3Fused& f, int gx, int N, int coutb, int M, bool inbwd, int ncb, hipStream_t stream) {
+    hipLaunchKernelGGL(k3_stats_finalize_kernel, dim3(ncb, inbwd ? 1 : N), dim3(256), 0, stream, f, gx, N, coutb, M, inbwd);
     MSSEG_CHECK_LAUNCH("k3_stats_finalize");
     return MSSEG_OK;
 }
@@ -759,17 +744,53 @@ int msseg_conv3d_k3_kernel(int N, int D, int H, int W, int Cin, int Cout, int dt
     return cfg;
 }
 
+// conv k3 p1 with the optional fused reductions f (f.stats == nullptr: none); stats_ws and nb_S are filled in here
 static int k3_fwd_impl(const void* x, long long ldx, const void* wp, const float* bias, void* y, long long ldy, int N,
-                       int D, int H, int W, int Cin, int Cout, float* stats, void* scratch, size_t scratch_bytes,
-                       const void* nb_y, long long nb_ldy, const void* nb_a, long long nb_lda, const float* nb_stats,
-                       float nb_slope, float nb_eps, float* nb_dgamma, float* nb_dbeta, int nb_acc, int dtype,
-                       msseg_stream_t stream);
+                       int D, int H, int W, int Cin, int Cout, K3Fused f, void* scratch, size_t scratch_bytes, int dtype,
+                       msseg_stream_t stream) {
+    const int esz = dtype == MSSEG_F32 ? 4 : 2;
+    int rc = check_common(x, ldx, wp, y, ldy, dtype, esz);
+    if (rc) return rc;
+    if (N < 1 || D < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3: bad shape");
+    if (Cin % (16 / esz)) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3: Cin=%d must be a multiple of %d (use conv3d_gather)", Cin, 16 / esz);
+    if (ldx < Cin || ldy < Cout) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3: ld smaller than channels");
+    if (f.stats) {
+        if (N > MSSEG_STATS_NMAX) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3: fused statistics need N <= %d", MSSEG_STATS_NMAX);
+        if (Cout > 64 * 16) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3: fused statistics need Cout <= 1024");
+        if ((rc = scratch_ok(scratch, scratch_bytes, "conv3d_k3 (fused statistics)"))) return rc;
+        f.stats_ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
+        f.nb_S = (long long)D * H * W;
+    }
+    if (dtype == MSSEG_BF16) {
+        // the 32-input-channel layers (the 96^3 / 48^3 levels) run on the ping-pong kernel when the grid is large enough
+        K3ppParams pp{};
+        pp.x = x; pp.ldx = ldx; pp.wp = wp; pp.bias = bias; pp.y = y; pp.ldy = ldy;
+        pp.N = N; pp.D = D; pp.H = H; pp.W = W; pp.K = Cin; pp.M = Cout;
+        pp.fused = f;
+        if (Cin == 48 && msseg_k3c48_shape_ok(N, D, H, W, Cout)) {
+            // the packed image is the four-part one of the 48-channel kernel (msseg_conv3d_k3_kernel() == 4): no fallback
+            if (!msseg_k3c48_eligible(pp))
+                MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3: 48-input-channel layer on a large grid needs 16-byte aligned x, 8-byte "
+                                         "aligned y and ldx <= 256");
+            return msseg_k3c48_launch(pp, (hipStream_t)stream);
+        }
+        int cfg, cb;
+        k3_plan(N, D, H, W, Cout, &cfg, &cb);   // the packed weight image must be the 32-wide one
+        if (cb == 32 && msseg_k3pp_eligible(pp)) return msseg_k3pp_launch(pp, (hipStream_t)stream);
+    }
+    IgemmParams p{};
+    p.x = x; p.ldx = ldx; p.wp = wp; p.bias = bias; p.y = y; p.ldy = ldy;
+    p.N = N; p.D = D; p.H = H; p.W = W; p.K = Cin; p.M = Cout;
+    p.fused = f;
+    return dtype == MSSEG_F32 ? launch_k3<float>(p, (hipStream_t)stream) : launch_k3<bf16_t>(p, (hipStream_t)stream);
+}
 
 int msseg_conv3d_k3_fwd(const void* x, long long ldx, const void* wp, const float* bias, void* y, long long ldy,
                         int N, int D, int H, int W, int Cin, int Cout, float* stats, void* scratch,
                         size_t scratch_bytes, int dtype, msseg_stream_t stream) {
-    return k3_fwd_impl(x, ldx, wp, bias, y, ldy, N, D, H, W, Cin, Cout, stats, scratch, scratch_bytes, nullptr, 0, nullptr,
-                       0, nullptr, 0.f, 0.f, nullptr, nullptr, 0, dtype, stream);
+    K3Fused f{};
+    f.stats = stats;
+    return k3_fwd_impl(x, ldx, wp, bias, y, ldy, N, D, H, W, Cin, Cout, f, scratch, scratch_bytes, dtype, stream);
 }
 
 int msseg_conv3d_k3_fwd_accumulate(const void* x, long long ldx, const void* wp, void* y, long long ldy, int N, int D, int H,
@@ -777,13 +798,12 @@ int msseg_conv3d_k3_fwd_accumulate(const void* x, long long ldx, const void* wp,
                                    msseg_stream_t stream) {
     if (!x || !wp || !y || !stats) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_fwd_accumulate: null pointer");
     if (dtype != MSSEG_BF16 || N < 1 || N > MSSEG_STATS_NMAX) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_fwd_accumulate: bf16, N <= %d", MSSEG_STATS_NMAX);
-    if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < msseg_reduce_scratch_bytes())
-        MSSEG_FAIL(MSSEG_EWORKSPACE, "conv3d_k3_fwd_accumulate: needs the reduce scratch of %zu bytes", msseg_reduce_scratch_bytes());
+    if (int rc = scratch_ok(scratch, scratch_bytes, "conv3d_k3_fwd_accumulate")) return rc;
     K3ppParams pp{};
     pp.x = x; pp.ldx = ldx; pp.wp = wp; pp.y = y; pp.ldy = ldy;
     pp.N = N; pp.D = D; pp.H = H; pp.W = W; pp.K = Cin; pp.M = Cout;
-    pp.stats = stats; pp.counter = (unsigned int*)scratch;
-    pp.stats_ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
+    pp.fused.stats = stats;
+    pp.fused.stats_ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
     pp.accumulate = 1;
     if (Cin == 48) {
         if (!msseg_k3c48_eligible(pp))
@@ -807,58 +827,12 @@ int msseg_conv3d_k3_dgrad_inbwd(const void* dy, long long lddy, const void* wp, 
     const int esz = dtype == MSSEG_F32 ? 4 : 2;
     if (Cout % 4 || (ldyraw % 4) || (ldact % 4) || ((uintptr_t)yraw % (4 * esz)) || ((uintptr_t)act % (4 * esz)))
         MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_dgrad_inbwd: channel count / strides must be multiples of 4");
-    return k3_fwd_impl(dy, lddy, wp, nullptr, da, ldda, N, D, H, W, Cin, Cout, red, scratch, scratch_bytes, yraw, ldyraw,
-                       act, ldact, fwd_stats, slope, eps, dgamma, dbeta, accumulate, dtype, stream);
-}
-
-static int k3_fwd_impl(const void* x, long long ldx, const void* wp, const float* bias, void* y, long long ldy, int N,
-                       int D, int H, int W, int Cin, int Cout, float* stats, void* scratch, size_t scratch_bytes,
-                       const void* nb_y, long long nb_ldy, const void* nb_a, long long nb_lda, const float* nb_stats,
-                       float nb_slope, float nb_eps, float* nb_dgamma, float* nb_dbeta, int nb_acc, int dtype,
-                       msseg_stream_t stream) {
-    const int esz = dtype == MSSEG_F32 ? 4 : 2;
-    int rc = check_common(x, ldx, wp, y, ldy, dtype, esz);
-    if (rc) return rc;
-    if (N < 1 || D < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3: bad shape");
-    if (Cin % (16 / esz)) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3: Cin=%d must be a multiple of %d (use conv3d_gather)", Cin, 16 / esz);
-    if (ldx < Cin || ldy < Cout) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3: ld smaller than channels");
-    IgemmParams p{};
-    p.x = x; p.ldx = ldx; p.wp = wp; p.bias = bias; p.y = y; p.ldy = ldy;
-    p.N = N; p.D = D; p.H = H; p.W = W; p.K = Cin; p.M = Cout;
-    if (stats) {
-        if (N > MSSEG_STATS_NMAX) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3: fused statistics need N <= %d", MSSEG_STATS_NMAX);
-        if (Cout > 64 * 16) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3: fused statistics need Cout <= 1024 (one counter per cout block)");
-        if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < msseg_reduce_scratch_bytes())
-            MSSEG_FAIL(MSSEG_EWORKSPACE, "conv3d_k3: fused statistics need a zero-initialised scratch of %zu bytes",
-                       msseg_reduce_scratch_bytes());
-        p.stats = stats;
-        p.counter = (unsigned int*)scratch;
-        p.stats_ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
-        p.nb_y = nb_y; p.nb_ldy = nb_ldy; p.nb_a = nb_a; p.nb_lda = nb_lda; p.nb_stats = nb_stats;
-        p.nb_slope = nb_slope; p.nb_eps = nb_eps; p.nb_S = (long long)D * H * W;
-        p.nb_dgamma = nb_dgamma; p.nb_dbeta = nb_dbeta; p.nb_acc = nb_acc;
-    }
-    if (dtype == MSSEG_BF16) {
-        // the 32-input-channel layers (the 96^3 / 48^3 levels) run on the ping-pong kernel when the grid is large enough
-        K3ppParams pp{};
-        pp.x = x; pp.ldx = ldx; pp.wp = wp; pp.bias = bias; pp.y = y; pp.ldy = ldy;
-        pp.N = N; pp.D = D; pp.H = H; pp.W = W; pp.K = Cin; pp.M = Cout;
-        pp.stats = p.stats; pp.stats_ws = p.stats_ws; pp.counter = p.counter;
-        pp.nb_y = p.nb_y; pp.nb_ldy = p.nb_ldy; pp.nb_a = p.nb_a; pp.nb_lda = p.nb_lda; pp.nb_stats = p.nb_stats;
-        pp.nb_slope = p.nb_slope; pp.nb_eps = p.nb_eps; pp.nb_S = p.nb_S;
-        pp.nb_dgamma = p.nb_dgamma; pp.nb_dbeta = p.nb_dbeta; pp.nb_acc = p.nb_acc;
-        if (Cin == 48 && msseg_k3c48_shape_ok(N, D, H, W, Cout)) {
-            // the packed image is the four-part one of the 48-channel kernel (msseg_conv3d_k3_kernel() == 4): no fallback
-            if (!msseg_k3c48_eligible(pp))
-                MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3: 48-input-channel layer on a large grid needs 16-byte aligned x, 8-byte "
-                                         "aligned y and ldx <= 256");
-            return msseg_k3c48_launch(pp, (hipStream_t)stream);
-        }
-        int cfg, cb;
-        k3_plan(N, D, H, W, Cout, &cfg, &cb);   // the packed weight image must be the 32-wide one
-        if (cb == 32 && msseg_k3pp_eligible(pp)) return msseg_k3pp_launch(pp, (hipStream_t)stream);
-    }
-    return dtype == MSSEG_F32 ? launch_k3<float>(p, (hipStream_t)stream) : launch_k3<bf16_t>(p, (hipStream_t)stream);
+    K3Fused f{};
+    f.stats = red;
+    f.nb_y = yraw; f.nb_ldy = ldyraw; f.nb_a = act; f.nb_lda = ldact; f.nb_stats = fwd_stats;
+    f.nb_slope = slope; f.nb_eps = eps;
+    f.nb_dgamma = dgamma; f.nb_dbeta = dbeta; f.nb_acc = accumulate;
+    return k3_fwd_impl(dy, lddy, wp, nullptr, da, ldda, N, D, H, W, Cin, Cout, f, scratch, scratch_bytes, dtype, stream);
 }
 
 int msseg_conv3d_k3s2_fwd(const void* x, long long ldx, const void* wp, const float* bias, void* y, long long ldy,
@@ -935,7 +909,21 @@ int msseg_conv3d_gather_fwd(const void* x, long long ldx, const void* wp, const 
 
 static int stem_fwd_taps(const void* x, long long ldx, const void* wp, const float* bias, void* y, long long ldy, int N, int D,
                          int H, int W, int Cout, float* stats, void* scratch, size_t scratch_bytes, int dtype, int taps,
-                         msseg_stream_t stream);
+                         msseg_stream_t stream) {
+    if (!x || !wp || (!y && !stats) || N < 1 || D < 1 || H < 1 || W < 1) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_stem: bad args");
+    if (!msseg_stem_eligible(dtype, 1, Cout, 3, 1, 1, ldx, y ? ldy : 4, y))   // y == NULL: statistics only
+        MSSEG_FAIL(MSSEG_EINVAL, "conv3d_stem: bf16, Cout a multiple of 32 or 48 (<= 256), 8-byte aligned output rows only");
+    StemParams sp{};
+    sp.x = x; sp.ldx = ldx; sp.wp = wp; sp.bias = bias; sp.y = y; sp.ldy = ldy;
+    sp.N = N; sp.D = D; sp.H = H; sp.W = W; sp.M = Cout; sp.taps = taps;
+    if (stats) {
+        if (N > MSSEG_STATS_NMAX) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_stem: fused statistics need N <= %d", MSSEG_STATS_NMAX);
+        if (int rc = scratch_ok(scratch, scratch_bytes, "conv3d_stem (fused statistics)")) return rc;
+        sp.stats = stats;
+        sp.stats_ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
+    }
+    return msseg_stem_fwd_launch(sp, (hipStream_t)stream);
+}
 
 int msseg_conv3d_stem_fwd(const void* x, long long ldx, const void* wp, const float* bias, void* y, long long ldy,
                           int N, int D, int H, int W, int Cout, float* stats, void* scratch, size_t scratch_bytes,
@@ -947,25 +935,6 @@ int msseg_conv3d_stem_k1_fwd(const void* x, long long ldx, const void* wp, const
                              int N, int D, int H, int W, int Cout, float* stats, void* scratch, size_t scratch_bytes,
                              int dtype, msseg_stream_t stream) {
     return stem_fwd_taps(x, ldx, wp, bias, y, ldy, N, D, H, W, Cout, stats, scratch, scratch_bytes, dtype, 1, stream);
-}
-
-static int stem_fwd_taps(const void* x, long long ldx, const void* wp, const float* bias, void* y, long long ldy, int N, int D,
-                         int H, int W, int Cout, float* stats, void* scratch, size_t scratch_bytes, int dtype, int taps,
-                         msseg_stream_t stream) {
-    if (!x || !wp || (!y && !stats) || N < 1 || D < 1 || H < 1 || W < 1) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_stem: bad args");
-    if (!msseg_stem_eligible(dtype, 1, Cout, 3, 1, 1, ldx, y ? ldy : 4, y))   // y == NULL: statistics only
-        MSSEG_FAIL(MSSEG_EINVAL, "conv3d_stem: bf16, Cout a multiple of 32 or 48 (<= 256), 8-byte aligned output rows only");
-    StemParams sp{};
-    sp.x = x; sp.ldx = ldx; sp.wp = wp; sp.bias = bias; sp.y = y; sp.ldy = ldy;
-    sp.N = N; sp.D = D; sp.H = H; sp.W = W; sp.M = Cout; sp.taps = taps;
-    if (stats) {
-        if (N > MSSEG_STATS_NMAX) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_stem: fused statistics need N <= %d", MSSEG_STATS_NMAX);
-        if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < msseg_reduce_scratch_bytes())
-            MSSEG_FAIL(MSSEG_EWORKSPACE, "conv3d_stem: fused statistics need a scratch of %zu bytes", msseg_reduce_scratch_bytes());
-        sp.stats = stats;
-        sp.stats_ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
-    }
-    return msseg_stem_fwd_launch(sp, (hipStream_t)stream);
 }
 
 int msseg_deconv_k2s2_fwd(const void* x, long long ldx, const void* wp, const float* bias, void* y, long long ldy,
@@ -1022,15 +991,13 @@ static int flat_inbwd_common(IgemmParams& p, int N, long long S, int Cout, const
     if (Cout % 4 || (ldyraw % 4) || (ldact % 4) || ((uintptr_t)yraw % (4 * esz)) || ((uintptr_t)act % (4 * esz)))
         MSSEG_FAIL(MSSEG_EINVAL, "%s: channel count / strides must be multiples of 4", who);
     if (Cout > 64 * 16) MSSEG_FAIL(MSSEG_EINVAL, "%s: at most 1024 output channels", who);
-    if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < msseg_reduce_scratch_bytes())
-        MSSEG_FAIL(MSSEG_EWORKSPACE, "%s: needs a scratch of %zu bytes", who, msseg_reduce_scratch_bytes());
+    if (int rc = scratch_ok(scratch, scratch_bytes, who)) return rc;
     p.N = N; p.D = 1; p.H = 1; p.W = (int)S;
-    p.stats = red;
-    p.counter = (unsigned int*)scratch;
-    p.stats_ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
-    p.nb_y = yraw; p.nb_ldy = ldyraw; p.nb_a = act; p.nb_lda = ldact; p.nb_stats = fwd_stats;
-    p.nb_slope = slope; p.nb_eps = eps; p.nb_S = S;
-    p.nb_dgamma = dgamma; p.nb_dbeta = dbeta; p.nb_acc = accumulate;
+    p.fused.stats = red;
+    p.fused.stats_ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
+    p.fused.nb_y = yraw; p.fused.nb_ldy = ldyraw; p.fused.nb_a = act; p.fused.nb_lda = ldact; p.fused.nb_stats = fwd_stats;
+    p.fused.nb_slope = slope; p.fused.nb_eps = eps; p.fused.nb_S = S;
+    p.fused.nb_dgamma = dgamma; p.fused.nb_dbeta = dbeta; p.fused.nb_acc = accumulate;
     return MSSEG_OK;
 }
 

@@ -2,6 +2,41 @@
 #pragma once
 #include "common.h"
 
+// Operands of the reductions fused into a conv epilogue (all optional; stats == nullptr: none).  The kernel writes one
+// partial row per workgroup to stats_ws, msseg_k3_fused_finalize adds the rows.
+struct K3Fused {
+    float* stats;        // per-(n, cout) (sum, sum of squares) of the stored output, [N][M][2]
+    float* stats_ws;     // partial rows (the reduce scratch past its counter block)
+    long long nb_S;      // voxels per sample
+    // InstanceNorm-BACKWARD sums (nb_y != nullptr): the launch produces da, the gradient w.r.t. the activation
+    // a = lrelu(IN(yraw)); the epilogue accumulates (sum dz, sum dz * yraw), dz = da * lrelu'(a), and the finalise step
+    // turns them into stats[n][c] = (sum dz, sum dz * xhat) and emits dbeta / dgamma
+    const void* nb_y; long long nb_ldy;   // yraw
+    const void* nb_a; long long nb_lda;   // a
+    const float* nb_stats;                // [N][M][2] forward statistics (sum, sum of squares) of yraw
+    float nb_slope, nb_eps;
+    float* nb_dgamma; float* nb_dbeta; int nb_acc;
+};
+// Second step of the fused reductions (igemm_fwd.hip): one small block per cout block (and sample, forward) adds the gx
+// partial rows ws[(y * gx + x) * N * coutb * 2 ..] of the ncb cout blocks in a fixed order and writes the per-(n, channel)
+// results; inbwd: the InstanceNorm-backward form.  A separate launch: the kernel boundary makes the partial rows visible
+// without release/acquire fences (which would write back / invalidate whole L2s at the end of every conv launch).
+int msseg_k3_fused_finalize(const K3Fused& f, int gx, int N, int coutb, int M, bool inbwd, int ncb, hipStream_t stream);
+
+// Workgroups per cout block (grid.x) of a persistent tile-walking kernel with per_cu workgroups per CU and ncb blocks in
+// grid.y: a multiple of 8, so that the XCD-contiguous tile schedule applies, and at most one per tile
+static inline int msseg_k3_grid_x(int per_cu, int ncb, long long tiles) {
+    int gx = msseg_num_cus() * per_cu / ncb;
+    gx &= ~7;
+    if (gx < 8) gx = 8;
+    if (gx > tiles) gx = (int)tiles;
+    return gx;
+}
+// 4 x 4 x 16 output tiles of an [N, D, H, W] grid
+static inline long long msseg_k3_tiles(int N, int D, int H, int W) {
+    return (long long)N * ceil_div(D, 4) * ceil_div(H, 4) * ceil_div(W, 16);
+}
+
 struct K3ppParams {
     const void* x;
     long long ldx;
@@ -10,15 +45,7 @@ struct K3ppParams {
     void* y;
     long long ldy;
     int N, D, H, W, K, M;
-    // optional fused reductions (same meaning as IgemmParams in igemm_fwd.hip)
-    float* stats;
-    float* stats_ws;
-    unsigned int* counter;
-    const void* nb_y; long long nb_ldy;
-    const void* nb_a; long long nb_lda;
-    const float* nb_stats;
-    float nb_slope, nb_eps; long long nb_S;
-    float* nb_dgamma; float* nb_dbeta; int nb_acc;
+    K3Fused fused;
     int accumulate;      // 1: y += conv(x) (the stored bf16 values are read back in the epilogue), statistics of the sums
 };
 
@@ -30,20 +57,6 @@ int msseg_k3pp_launch(const K3ppParams& p, hipStream_t stream);
 bool msseg_k3c48_shape_ok(int N, int D, int H, int W, int M);   // grid / channel conditions (what the packer must know)
 bool msseg_k3c48_eligible(const K3ppParams& p);                 // ... and operand alignment
 int msseg_k3c48_launch(const K3ppParams& p, hipStream_t stream);
-
-// ---- second step of the fused conv-epilogue reductions (igemm_fwd.hip): one small block per cout block adds the
-// per-workgroup partial rows ws[(y * R + x) * L ..] in a fixed order and writes the per-(n, channel) results.  A
-// separate launch: the kernel boundary makes the partial rows visible without release/acquire fences (which would
-// write back / invalidate whole L2s at the end of every conv launch).
-struct K3FinParams {
-    const float* ws;
-    int R, N, coutb, M;        // partial rows per cout block, samples, cout block width, logical output channels
-    float* stats;              // [N][M][2]
-    const float* nb_stats;     // non-null: InstanceNorm-backward mode (see IgemmParams)
-    float nb_eps; long long nb_S;
-    float* nb_dgamma; float* nb_dbeta; int nb_acc;
-};
-int msseg_k3_stats_finalize(const K3FinParams& f, int ncb, hipStream_t stream);
 
 // ---- weight gradient (conv3d_k3_wgrad_pp.hip) ----
 struct K3WgParams {
@@ -63,7 +76,7 @@ struct StemParams {
     const float* bias;
     void* y; long long ldy;
     int N, D, H, W, M;
-    float* stats; float* stats_ws;    // optional fused statistics (partial rows -> msseg_k3_stats_finalize)
+    float* stats; float* stats_ws;    // optional fused statistics (partial rows -> msseg_k3_fused_finalize)
     int taps;                         // 27 (or 0): conv k3 p1; 1: the 1x1x1 conv of a one-channel volume (image with K = 1)
     // y == nullptr (with stats): statistics only, nothing is stored.  nstats != nullptr: y = lrelu(instance_norm(conv) * gamma +
     // beta) with the statistics nstats[N][M][2] of a previous statistics-only launch (inference: the raw output never exists)

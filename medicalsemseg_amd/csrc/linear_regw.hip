@@ -23,6 +23,7 @@
 //                 (swin_nnformer.py:243-262) without the separate add pass
 // with the arithmetic of gelu_kernel (attention.hip) on the bf16-rounded operands, i.e. bit-identical to the unfused chain.
 #include "k3pp.h"
+#include "pingpong.h"   // pack_bf16x2
 
 namespace {
 
@@ -44,13 +45,6 @@ enum { EPI_NONE = 0, EPI_GELU = 1, EPI_GELU_BWD = 2, EPI_ADD = 3 };
 MSSEG_DEVFN float bf16_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
 MSSEG_DEVFN float bf16_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
 MSSEG_DEVFN float gelu_cdf(float v) { return 0.5f * (1.f + erff(v * 0.70710678118654752f)); }
-
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-MSSEG_DEVFN unsigned pack_bf16x2(float a, float b) {
-    const bf16x2_t v = {(bf16_t)a, (bf16_t)b};
-    return __builtin_bit_cast(unsigned, v);
-}
 
 template <int KS, int NH, int EPI>   // KS = ceil(K / 32) k-steps, NH = M / 16 output tiles
 __global__ __launch_bounds__(LR_THREADS, 2) void linear_regw_kernel(const LinParams p) {

@@ -16,6 +16,7 @@
 //           (8 consecutive voxels of one tap per lane) is ONE ds_read_b128 from one of three copies of the halo
 //           shifted by kw = 0, 1, 2 (so that every read is 16-byte aligned).
 #include "k3pp.h"
+#include "pingpong.h"
 
 namespace {
 
@@ -23,37 +24,7 @@ constexpr int TD = 4, TH = 4, TW = 16;
 constexpr int PD = TD + 2, PH = TH + 2, PW = TW + 2;
 constexpr int HV = PD * PH * PW;   // 648
 
-typedef __attribute__((address_space(3))) unsigned char lds_u8;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-
-struct TileCo { int n, d0, h0, w0; };
-
-struct Sched {
-    int tiles_w, tiles_h, tiles_d, t_first, t_step, n_my;
-    MSSEG_DEVFN void init(int N, int D, int H, int W) {
-        tiles_w = (W + TW - 1) / TW; tiles_h = (H + TH - 1) / TH; tiles_d = (D + TD - 1) / TD;
-        const int ntiles = N * tiles_d * tiles_h * tiles_w;
-        int t_end;
-        if ((gridDim.x & 7) == 0) {   // XCD-contiguous walk (conv3d_k3_pp.hip)
-            const int chunk = (ntiles + 7) >> 3, xcd = blockIdx.x & 7;
-            t_first = xcd * chunk + (blockIdx.x >> 3);
-            t_step = gridDim.x >> 3;
-            t_end = min(ntiles, (xcd + 1) * chunk);
-        } else {
-            t_first = blockIdx.x; t_step = gridDim.x; t_end = ntiles;
-        }
-        n_my = t_first < t_end ? (t_end - t_first + t_step - 1) / t_step : 0;
-    }
-    MSSEG_DEVFN TileCo tile(int k) const {
-        int t = t_first + k * t_step;
-        TileCo tc;
-        tc.w0 = (t % tiles_w) * TW; t /= tiles_w;
-        tc.h0 = (t % tiles_h) * TH; t /= tiles_h;
-        tc.d0 = (t % tiles_d) * TD; t /= tiles_d;
-        tc.n = t;
-        return tc;
-    }
-};
 
 // ------------------------------------------------------------------------------------------------------------
 // forward
@@ -67,16 +38,16 @@ constexpr int F_THREADS = 512;
 template <int STATS, int JT, int NORM = 0>
 __global__ __launch_bounds__(F_THREADS) void stem_fwd_kernel(const StemParams p) {
     constexpr int CBW = JT * 16;
-    constexpr int F_STAT_FLOATS = 8 * MSSEG_STATS_NMAX * CBW * 2;
+    using Stats = StatAcc<JT, MSSEG_STATS_NMAX, false>;   // the compiler's own instructions for the sums: nothing shares the SIMD
     __shared__ __attribute__((aligned(16))) unsigned short halo[2][HV + 8];
-    __shared__ float ldsS[STATS ? F_STAT_FLOATS : 1];
+    __shared__ float ldsS[STATS ? Stats::LDS_FLOATS : 1];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, q = lane >> 4;
     const int coutblk = blockIdx.y;
     const unsigned short* __restrict__ xg = (const unsigned short*)p.x;
     bf16_t* __restrict__ yg = (bf16_t*)p.y;
-    Sched sc;
+    Sched<TD, TH, TW> sc;
     sc.init(p.N, p.D, p.H, p.W);
 
     // weights: A operand fragments straight from the packed image [q][cout 32][16 B] of this cout block
@@ -98,9 +69,9 @@ __global__ __launch_bounds__(F_THREADS) void stem_fwd_kernel(const StemParams p)
         const int k = q * 8 + j;
         toff[j] = ntaps == 1 ? (PH + 1) * PW + 1 : ((k < 27) ? ((k / 9) * PH + ((k / 3) % 3)) * PW + (k % 3) : 0);   // k >= taps: any valid element
     }
-    if (STATS) {
-        for (int i = tid; i < F_STAT_FLOATS; i += F_THREADS) ldsS[i] = 0.f;
-    }
+    Stats sacc;
+    sacc.init(ldsS, wave, lane);
+    if (STATS) sacc.zero_slots();
     float nsc[NORM ? JT : 1][4], nsh[NORM ? JT : 1][4];
     int n_n = -1;
     auto load_norm = [&](int n) {   // scale / shift of sample n: instnorm_kernel's arithmetic (elementwise.hip mean_rstd)
@@ -121,34 +92,6 @@ __global__ __launch_bounds__(F_THREADS) void stem_fwd_kernel(const StemParams p)
                 }
         }
     };
-    float s1[JT][4], s2[JT][4];
-    int s_n = -1;
-#pragma unroll
-    for (int jt = 0; jt < JT; ++jt)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s1[jt][e] = s2[jt][e] = 0.f;
-    auto flush_stats = [&]() {
-        if (s_n < 0) return;
-        float* slot = ldsS + ((wave * MSSEG_STATS_NMAX + s_n) * CBW) * 2;
-#pragma unroll
-        for (int jt = 0; jt < JT; ++jt)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float a = s1[jt][e], b = s2[jt][e];
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1) {
-                    a += __shfl_xor(a, o);
-                    b += __shfl_xor(b, o);
-                }
-                if (r == 0) {
-                    float* sp = slot + (jt * 16 + q * 4 + e) * 2;
-                    sp[0] += a;
-                    sp[1] += b;
-                }
-                s1[jt][e] = s2[jt][e] = 0.f;
-            }
-    };
-
     // halo staging: two elements per thread, register-staged one tile ahead
     unsigned short st[2];
     auto fetch = [&](const TileCo& tc) {
@@ -179,9 +122,7 @@ __global__ __launch_bounds__(F_THREADS) void stem_fwd_kernel(const StemParams p)
         const TileCo tc = sc.tile(k);
         if (k + 1 < sc.n_my) fetch(sc.tile(k + 1));
         const unsigned short* hb = halo[k & 1];
-        if constexpr (STATS != 0) {
-            if (tc.n != s_n) { flush_stats(); s_n = tc.n; }
-        }
+        if constexpr (STATS != 0) sacc.sample(tc.n);
         if constexpr (NORM != 0) {
             if (tc.n != n_n) { load_norm(tc.n); n_n = tc.n; }
         }
@@ -220,29 +161,14 @@ __global__ __launch_bounds__(F_THREADS) void stem_fwd_kernel(const StemParams p)
                 }
                 if constexpr (STATS != 0) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float rv = ok ? (float)ob[e] : 0.f;
-                        s1[jt][e] += rv;
-                        s2[jt][e] += rv * rv;
-                    }
+                    for (int e = 0; e < 4; ++e) sacc.add(jt, e, ok ? (float)ob[e] : 0.f);
                 }
             }
         }
         if (k + 1 < sc.n_my) commit((k + 1) & 1);
         __syncthreads();
     }
-    if constexpr (STATS != 0) {
-        flush_stats();
-        __syncthreads();
-        const int PN = p.N * CBW * 2;
-        float* wsp = p.stats_ws + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * PN;
-        for (int i = tid; i < PN; i += F_THREADS) {
-            float s = 0.f;
-#pragma unroll
-            for (int wv = 0; wv < 8; ++wv) s += ldsS[wv * MSSEG_STATS_NMAX * CBW * 2 + i];
-            wsp[i] = s;
-        }
-    }
+    if constexpr (STATS != 0) sacc.finish(p.stats_ws, p.N);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -252,16 +178,6 @@ constexpr int W_THREADS = 256;
 constexpr int XP = 24;                              // row pitch (elements) of the shifted halo copies: 16-byte aligned rows
 constexpr int XS_ELEMS = PD * PH * XP;              // one shifted copy
 constexpr int P_BYTES = TD * TH * TW * 64;          // dy tile, 32 channels
-
-__device__ u32x4_t g_stem_zero_chunk;
-
-MSSEG_DEVFN void glds16(const void* g, void* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-MSSEG_DEVFN bf16x4_t lds_tr(lds_u8* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)p);
-}
 
 __global__ __launch_bounds__(W_THREADS) void stem_wgrad_kernel(const StemWgParams p) {
     extern __shared__ __attribute__((aligned(256))) unsigned char smem[];
@@ -273,7 +189,7 @@ __global__ __launch_bounds__(W_THREADS) void stem_wgrad_kernel(const StemWgParam
     const int mblk = blockIdx.y;
     const unsigned char* dyg = (const unsigned char*)p.dy + mblk * 64;
     const unsigned short* __restrict__ xg = (const unsigned short*)p.x;
-    Sched sc;
+    Sched<TD, TH, TW> sc;
     sc.init(p.N, p.D, p.H, p.W);
 
     // dy tile DMA: 16 wave-instructions of 16 rows x 64 B; wave w issues instructions w, w+4, ...
@@ -290,7 +206,7 @@ __global__ __launch_bounds__(W_THREADS) void stem_wgrad_kernel(const StemWgParam
         const long long pvox = (((long long)tc.n * p.D + tc.d0) * p.H + tc.h0) * p.W + tc.w0;
         const unsigned char* pb = dyg + pvox * p.lddy * 2;
         const bool full = tc.d0 + TD <= p.D && tc.h0 + TH <= p.H && tc.w0 + TW <= p.W;
-        const unsigned char* zsrc = (const unsigned char*)&g_stem_zero_chunk;
+        const unsigned char* zsrc = (const unsigned char*)&g_zero_chunk;
         const bool ch_ok = mblk * 32 + (lane & 3) * 8 < p.M;   // 48 couts: the second block's upper half is padding
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -359,11 +275,10 @@ __global__ __launch_bounds__(W_THREADS) void stem_wgrad_kernel(const StemWgParam
         for (int i4 = 0; i4 < 4; ++i4) {
             const int row = wave * 4 + i4;
             const int td = row >> 2, th = row & 3;
-            const bf16x4_t lo = lds_tr(bb + a_rd[0] + row * 1024), hi = lds_tr(bb + a_rd[1] + row * 1024);
-            const bf16x8_t af = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            const u32x4_t af = tr_frag(bb + a_rd[0] + row * 1024, bb + a_rd[1] + row * 1024);
             u32x4_t bfr = *(const u32x4_t*)(smem + buf * BUF_BYTES + b_rd + ((td * PH + th) * XP) * 2);
             if (!tap_ok) bfr = u32x4_t{0u, 0u, 0u, 0u};
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, __builtin_bit_cast(bf16x8_t, bfr), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, af), __builtin_bit_cast(bf16x8_t, bfr), acc, 0, 0, 0);
         }
         if (k + 1 < sc.n_my) commit_x(buf ^ 1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -390,11 +305,7 @@ bool msseg_stem_eligible(int dtype, int Cin, int Cout, int k, int s, int pd, lon
 int msseg_stem_fwd_launch(const StemParams& p, hipStream_t stream) {
     const int cbw = (p.M % 32 == 0) ? 32 : 48;   // = msseg_cout_block(M): the block width of the packed image
     const int ncb = p.M / cbw;
-    const int tiles = p.N * ceil_div(p.D, TD) * ceil_div(p.H, TH) * ceil_div(p.W, TW);
-    int gx = msseg_num_cus() * 2 / ncb;
-    gx &= ~7;
-    if (gx < 8) gx = 8;
-    if (gx > tiles) gx = tiles;
+    const int gx = msseg_k3_grid_x(2, ncb, msseg_k3_tiles(p.N, p.D, p.H, p.W));
     if (p.nstats != nullptr && p.stats != nullptr) MSSEG_FAIL(MSSEG_EINVAL, "stem_fwd: the normalised form emits no statistics");
     if (p.y == nullptr && p.stats == nullptr) MSSEG_FAIL(MSSEG_EINVAL, "stem_fwd: nothing to produce");
     if (cbw == 32) {
@@ -408,20 +319,15 @@ int msseg_stem_fwd_launch(const StemParams& p, hipStream_t stream) {
     }
     MSSEG_CHECK_LAUNCH("stem_fwd");
     if (p.stats) {
-        K3FinParams f{};
-        f.ws = p.stats_ws; f.R = gx; f.N = p.N; f.coutb = cbw; f.M = p.M; f.stats = p.stats;
-        return msseg_k3_stats_finalize(f, ncb, stream);
+        K3Fused f{};
+        f.stats = p.stats; f.stats_ws = p.stats_ws;
+        return msseg_k3_fused_finalize(f, gx, p.N, cbw, p.M, false, ncb, stream);
     }
     return MSSEG_OK;
 }
 
 int msseg_stem_wgrad_grid(const StemWgParams& p) {
-    const int tiles = p.N * ceil_div(p.D, TD) * ceil_div(p.H, TH) * ceil_div(p.W, TW);
-    int gx = msseg_num_cus() * 2 / ceil_div(p.M, 32);
-    gx &= ~7;
-    if (gx < 8) gx = 8;
-    if (gx > tiles) gx = tiles;
-    return gx;
+    return msseg_k3_grid_x(2, ceil_div(p.M, 32), msseg_k3_tiles(p.N, p.D, p.H, p.W));
 }
 
 int msseg_stem_wgrad_launch(const StemWgParams& p, int gx, hipStream_t stream) {

@@ -254,6 +254,33 @@ def test_conv3d_k3_96_channels_two_accumulating_launches_exact():
     assert_exact(op.w.grad, r["dw"], "conv 96 -> 48 wgrad")
 
 
+def test_conv3d_k3_64_channels_two_accumulating_launches_exact():
+    """64 -> 32 through Conv3.fwd_split on the two 32-channel halves of the input: two launches of the ping-pong kernel, the
+    second (csrc/conv3d_k3_pp.hip, STATS == 3) accumulating onto the stored bf16 result of the first and emitting the statistics.
+    The first launch's stored intermediate is a partial sum of the same products: an integer, asserted here to stay within
+    256, so the extra rounding is exact too."""
+    from medicalsemseg_amd import hip
+    from medicalsemseg_amd.layers import Conv3
+    dev, L = _dev(), hip.lib()
+    cin, cout, sp = 64, 32, (30, 29, 70)
+    N = _grow_n(2, lambda n: L.msseg_conv3d_k3_kernel(n, *sp, 32, cout, hip.BF16) == 3, f"ping-pong 32->{cout} @ {sp}")
+    assert L.msseg_conv3d_k3_kernel(N, *sp, 32, cout, hip.BF16) == 3
+    r = _k3_ref(cin, cout, sp, N)
+    part = F.conv3d(r["x"][:, :32], r["w"][:, :32], r["b"], padding=1)
+    assert bool((part == part.round()).all()) and float(part.abs().max()) <= 256, "the first half's partial sum is not exact in bf16"
+    op = Conv3(torch.nn.Parameter(r["w"].float().to(dev)), torch.nn.Parameter(r["b"].float().to(dev)))
+    xg = cl(r["x"], BF16, dev)
+    xa, xb = xg[..., :32].contiguous(), xg[..., 32:].contiguous()
+    with launched() as k:
+        y, stats = op.fwd_split(xa, xb)
+    print(f"conv3d_k3 64->32 @ {sp} N={N} as halves: first half max |y| {float(part.abs().max()):.0f}, launched {sorted(k.names)}")
+    assert k.names == {"k3pp_kernel"}
+    assert_exact(vol(y), r["y"], "conv 64 -> 32 as two halves")
+    err = _sumsq_err(stats, r["y"])
+    print(f"  fused sum of squares: relative error {err:.3e}")
+    assert err < SUMSQ_GATES["k3"]
+
+
 @pytest.mark.parametrize("sp,want", [((8, 9, 17), 3), ((7, 9, 17), 0)])
 def test_conv3d_k3_wgrad_pingpong_min_dim_cut_exact(sp, want):
     """64 -> 32 with enough samples that the tile count admits the ping-pong weight gradient: 8 x 9 x 17 takes it, 7 x 9 x 17 (the
