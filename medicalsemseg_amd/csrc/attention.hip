@@ -322,29 +322,6 @@ struct LnVecParams {
     const void* add; long long ldadd;   // backward: dx = T(layernorm backward) + add (the gradient of a residual branch that left x)
 };
 
-template <typename T> MSSEG_DEVFN void ln_load(const T* p, float (&v)[DT<T>::EPC]) {
-    const u32x4_t raw = *(const u32x4_t*)p;
-    if constexpr (sizeof(T) == 2) {
-        const bf16x8_t h = __builtin_bit_cast(bf16x8_t, raw);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = (float)h[e];
-    } else {
-        const f32x4_t f = __builtin_bit_cast(f32x4_t, raw);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = f[e];
-    }
-}
-template <typename T> MSSEG_DEVFN void ln_store(T* p, const float (&v)[DT<T>::EPC]) {
-    if constexpr (sizeof(T) == 2) {
-        bf16x8_t h;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) h[e] = (bf16_t)v[e];
-        *(u32x4_t*)p = __builtin_bit_cast(u32x4_t, h);
-    } else {
-        *(f32x4_t*)p = f32x4_t{v[0], v[1], v[2], v[3]};
-    }
-}
-
 template <typename T, int MAXCH, bool BWD>
 __global__ __launch_bounds__(256) void layernorm_vec_kernel(const LnVecParams p) {
     constexpr int EPC = DT<T>::EPC;
@@ -374,8 +351,8 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(const LnVecParams p)
 #pragma unroll
             for (int e = 0; e < EPC; ++e) xv[k][e] = dv[k][e] = 0.f;
             if (ok) {
-                ln_load<T>((const T*)p.x + r * p.ldx + ch * EPC, xv[k]);
-                if constexpr (BWD) ln_load<T>((const T*)p.dy + r * p.lddy + ch * EPC, dv[k]);
+                Chunk<T>::load((const T*)p.x + r * p.ldx + ch * EPC, xv[k]);
+                if constexpr (BWD) Chunk<T>::load((const T*)p.dy + r * p.lddy + ch * EPC, dv[k]);
             }
         }
         if constexpr (!BWD) {
@@ -407,7 +384,7 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(const LnVecParams p)
                     float o[EPC];
 #pragma unroll
                     for (int e = 0; e < EPC; ++e) o[e] = (xv[k][e] - mu) * rs * gv[k][e] + bv[k][e];
-                    ln_store<T>((T*)p.y + r * p.ldy + ch * EPC, o);
+                    Chunk<T>::store((T*)p.y + r * p.ldy + ch * EPC, o);
                 }
             }
         } else {
@@ -432,11 +409,11 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(const LnVecParams p)
                     for (int e = 0; e < EPC; ++e) o[e] = rs * (dv[k][e] * gv[k][e] - a - (xv[k][e] - mu) * rs * b);
                     if (p.add) {   // the sum autograd forms for a tensor with two consumers: both terms rounded to T, then added
                         float r2[EPC];
-                        ln_load<T>((const T*)p.add + r * p.ldadd + ch * EPC, r2);
+                        Chunk<T>::load((const T*)p.add + r * p.ldadd + ch * EPC, r2);
 #pragma unroll
                         for (int e = 0; e < EPC; ++e) o[e] = (float)(T)o[e] + r2[e];
                     }
-                    ln_store<T>((T*)p.y + r * p.ldy + ch * EPC, o);
+                    Chunk<T>::store((T*)p.y + r * p.ldy + ch * EPC, o);
                 }
             }
         }
@@ -483,15 +460,15 @@ __global__ void gelu_kernel(const T* __restrict__ x, const T* __restrict__ dy, T
     const long long nvec = vec ? n / EPC : 0;
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < nvec; i += (long long)gridDim.x * 256) {
         float v[EPC], g[EPC], o[EPC];
-        ln_load<T>(x + i * EPC, v);
-        if constexpr (BWD) ln_load<T>(dy + i * EPC, g);
+        Chunk<T>::load(x + i * EPC, v);
+        if constexpr (BWD) Chunk<T>::load(dy + i * EPC, g);
 #pragma unroll
         for (int e = 0; e < EPC; ++e) {
             const float cdf = 0.5f * (1.f + erff(v[e] * 0.70710678118654752f));
             if constexpr (!BWD) o[e] = v[e] * cdf;
             else o[e] = g[e] * (cdf + v[e] * 0.3989422804014327f * expf(-0.5f * v[e] * v[e]));
         }
-        ln_store<T>(out + i * EPC, o);
+        Chunk<T>::store(out + i * EPC, o);
     }
     for (long long i = nvec * EPC + blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const float v = DT<T>::ld(x + i);
@@ -499,14 +476,6 @@ __global__ void gelu_kernel(const T* __restrict__ x, const T* __restrict__ dy, T
         if constexpr (!BWD) DT<T>::st(out + i, v * cdf);
         else DT<T>::st(out + i, DT<T>::ld(dy + i) * (cdf + v * 0.3989422804014327f * expf(-0.5f * v * v)));
     }
-}
-
-inline int grid_for(long long total, int per_thread = 4) {
-    long long b = ceil_div_ll(total, 256LL * per_thread);
-    const long long cap = (long long)msseg_num_cus() * 16;
-    if (b > cap) b = cap;
-    if (b < 1) b = 1;
-    return (int)b;
 }
 
 int fill_attn(AttnParams& p, int B, int S, int H, int W, int C, int heads, int ws, int shift, int bias_ws) {
@@ -528,19 +497,26 @@ int fill_attn(AttnParams& p, int B, int S, int H, int W, int C, int heads, int w
     return MSSEG_OK;
 }
 
-#define ATTN_LAUNCH(KERN, T_, SMEM)                                                                      \
+// KERN<dtype's T, head dim>; returns from the entry point on a failed LDS setting or a dtype that is neither code
+#define ATTN_LAUNCH(KERN, SMEM, WHO)                                                                     \
     do {                                                                                                 \
-        int gx__ = p.nwin_total < msseg_num_cus() * 2 ? p.nwin_total : msseg_num_cus() * 2;              \
-        int gy__ = (msseg_num_cus() * 2 + gx__ - 1) / gx__;                                              \
-        if (gy__ > p.heads) gy__ = p.heads;                                                              \
-        if (p.dtab_all_heads) gy__ = 1;                                                                  \
-        dim3 grid(gx__, gy__);                                                                            \
-        if (p.hd == 8) { if (int rc__ = attn_set_lds((const void*)KERN<T_, 8>, SMEM)) return rc__;          \
-            hipLaunchKernelGGL((KERN<T_, 8>), grid, dim3(256), SMEM, (hipStream_t)stream, p); }              \
-        else if (p.hd == 16) { if (int rc__ = attn_set_lds((const void*)KERN<T_, 16>, SMEM)) return rc__;   \
-            hipLaunchKernelGGL((KERN<T_, 16>), grid, dim3(256), SMEM, (hipStream_t)stream, p); }             \
-        else { if (int rc__ = attn_set_lds((const void*)KERN<T_, 32>, SMEM)) return rc__;                   \
-            hipLaunchKernelGGL((KERN<T_, 32>), grid, dim3(256), SMEM, (hipStream_t)stream, p); }             \
+        int rc__ = MSSEG_OK;                                                                             \
+        const bool known__ = for_dtype(dtype, [&](auto t__) {                                            \
+            using T_ = typename decltype(t__)::type;                                                     \
+            int gx__ = p.nwin_total < msseg_num_cus() * 2 ? p.nwin_total : msseg_num_cus() * 2;          \
+            int gy__ = (msseg_num_cus() * 2 + gx__ - 1) / gx__;                                          \
+            if (gy__ > p.heads) gy__ = p.heads;                                                          \
+            if (p.dtab_all_heads) gy__ = 1;                                                              \
+            dim3 grid(gx__, gy__);                                                                       \
+            if (p.hd == 8) { if (!(rc__ = attn_set_lds((const void*)KERN<T_, 8>, SMEM)))                 \
+                hipLaunchKernelGGL((KERN<T_, 8>), grid, dim3(256), SMEM, (hipStream_t)stream, p); }      \
+            else if (p.hd == 16) { if (!(rc__ = attn_set_lds((const void*)KERN<T_, 16>, SMEM)))          \
+                hipLaunchKernelGGL((KERN<T_, 16>), grid, dim3(256), SMEM, (hipStream_t)stream, p); }     \
+            else { if (!(rc__ = attn_set_lds((const void*)KERN<T_, 32>, SMEM)))                          \
+                hipLaunchKernelGGL((KERN<T_, 32>), grid, dim3(256), SMEM, (hipStream_t)stream, p); }     \
+        });                                                                                              \
+        if (!known__) MSSEG_FAIL(MSSEG_EINVAL, WHO ": bad dtype");                                       \
+        if (rc__) return rc__;                                                                           \
     } while (0)
 
 }  // namespace
@@ -576,9 +552,7 @@ int msseg_window_attention_fwd(const void* qkv, const float* qkv_bias, const flo
         // bf16: QK^T and PV on the matrix cores (attention_mfma.hip)
         return msseg_window_attention_fwd_mfma(p, (hipStream_t)stream);
     }
-    if (dtype == MSSEG_F32) ATTN_LAUNCH(win_attn_fwd_kernel, float, smem);
-    else if (dtype == MSSEG_BF16) ATTN_LAUNCH(win_attn_fwd_kernel, bf16_t, smem);
-    else MSSEG_FAIL(MSSEG_EINVAL, "window_attention_fwd: bad dtype");
+    ATTN_LAUNCH(win_attn_fwd_kernel, smem, "window_attention_fwd");
     MSSEG_CHECK_LAUNCH("window_attention_fwd");
     return MSSEG_OK;
 }
@@ -631,9 +605,7 @@ int msseg_window_attention_bwd(const void* qkv, const float* qkv_bias, const flo
     p.dtab_all_heads = (table_stride == 0 && base + (size_t)heads * p.M3 * 4 <= 96 * 1024) ? 1 : 0;
     const size_t smem = base + (size_t)(p.dtab_all_heads ? heads : 1) * p.M3 * 4;
     if (smem > 160 * 1024) MSSEG_FAIL(MSSEG_EINVAL, "window_attention_bwd: window too large for LDS (%zu bytes)", smem);
-    if (dtype == MSSEG_F32) ATTN_LAUNCH(win_attn_bwd_kernel, float, smem);
-    else if (dtype == MSSEG_BF16) ATTN_LAUNCH(win_attn_bwd_kernel, bf16_t, smem);
-    else MSSEG_FAIL(MSSEG_EINVAL, "window_attention_bwd: bad dtype");
+    ATTN_LAUNCH(win_attn_bwd_kernel, smem, "window_attention_bwd");
     MSSEG_CHECK_LAUNCH("window_attention_bwd");
     return MSSEG_OK;
 }
@@ -641,22 +613,17 @@ int msseg_window_attention_bwd(const void* qkv, const float* qkv_bias, const flo
 int msseg_layernorm_fwd(const void* x, long long ldx, const float* gamma, const float* beta, void* y, long long ldy,
                         float* mean, float* rstd, long long rows, int C, float eps, int dtype, msseg_stream_t stream) {
     if (!x || !y || rows < 1 || C < 1) MSSEG_FAIL(MSSEG_EINVAL, "layernorm_fwd: bad args");
-    if (dtype == MSSEG_F32 || dtype == MSSEG_BF16) {
-        LnVecParams v{};
-        v.x = x; v.ldx = ldx; v.g = gamma; v.b = beta; v.y = y; v.ldy = ldy; v.mean = mean; v.rstd = rstd;
-        v.rows = rows; v.C = C; v.eps = eps;
-        const bool done = dtype == MSSEG_F32 ? launch_ln_vec<float, false>(v, (hipStream_t)stream)
-                                             : launch_ln_vec<bf16_t, false>(v, (hipStream_t)stream);
-        if (done) { MSSEG_CHECK_LAUNCH("layernorm_fwd"); return MSSEG_OK; }
-    }
-    const int g = grid_for(rows, 1);
-    if (dtype == MSSEG_F32)
-        hipLaunchKernelGGL(layernorm_fwd_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)x, ldx,
-                           gamma, beta, (float*)y, ldy, mean, rstd, rows, C, eps);
-    else if (dtype == MSSEG_BF16)
-        hipLaunchKernelGGL(layernorm_fwd_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx,
-                           gamma, beta, (bf16_t*)y, ldy, mean, rstd, rows, C, eps);
-    else MSSEG_FAIL(MSSEG_EINVAL, "layernorm_fwd: bad dtype");
+    LnVecParams v{};
+    v.x = x; v.ldx = ldx; v.g = gamma; v.b = beta; v.y = y; v.ldy = ldy; v.mean = mean; v.rstd = rstd;
+    v.rows = rows; v.C = C; v.eps = eps;
+    bool done = false;   // by the vector kernel
+    for_dtype(dtype, [&](auto t) { done = launch_ln_vec<typename decltype(t)::type, false>(v, (hipStream_t)stream); });
+    const bool known = done || for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(layernorm_fwd_kernel<T>, dim3(stream_grid(rows)), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx,
+                           gamma, beta, (T*)y, ldy, mean, rstd, rows, C, eps);
+    });
+    if (!known) MSSEG_FAIL(MSSEG_EINVAL, "layernorm_fwd: bad dtype");
     MSSEG_CHECK_LAUNCH("layernorm_fwd");
     return MSSEG_OK;
 }
@@ -665,25 +632,19 @@ int msseg_layernorm_bwd(const void* x, long long ldx, const float* gamma, const 
                         const void* dy, long long lddy, void* dx, long long lddx, long long rows, int C, int dtype,
                         msseg_stream_t stream) {
     if (!x || !mean || !rstd || !dy || !dx || rows < 1 || C < 1) MSSEG_FAIL(MSSEG_EINVAL, "layernorm_bwd: bad args");
-    if (dtype == MSSEG_F32 || dtype == MSSEG_BF16) {
-        LnVecParams v{};
-        v.x = x; v.ldx = ldx; v.g = gamma; v.y = dx; v.ldy = lddx; v.mean = (float*)mean; v.rstd = (float*)rstd;
-        v.dy = dy; v.lddy = lddy; v.rows = rows; v.C = C;
-        const bool done = dtype == MSSEG_F32 ? launch_ln_vec<float, true>(v, (hipStream_t)stream)
-                                             : launch_ln_vec<bf16_t, true>(v, (hipStream_t)stream);
-        if (done) { MSSEG_CHECK_LAUNCH("layernorm_bwd"); return MSSEG_OK; }
-    }
+    LnVecParams v{};
+    v.x = x; v.ldx = ldx; v.g = gamma; v.y = dx; v.ldy = lddx; v.mean = (float*)mean; v.rstd = (float*)rstd;
+    v.dy = dy; v.lddy = lddy; v.rows = rows; v.C = C;
     float* dgamma = nullptr;
     float* dbeta = nullptr;
-    const int g = grid_for(rows, 1);
-    const size_t smem = 0;
-    if (dtype == MSSEG_F32)
-        hipLaunchKernelGGL(layernorm_bwd_kernel<float>, dim3(g), dim3(256), smem, (hipStream_t)stream, (const float*)x, ldx,
-                           gamma, mean, rstd, (const float*)dy, lddy, (float*)dx, lddx, dgamma, dbeta, rows, C);
-    else if (dtype == MSSEG_BF16)
-        hipLaunchKernelGGL(layernorm_bwd_kernel<bf16_t>, dim3(g), dim3(256), smem, (hipStream_t)stream, (const bf16_t*)x,
-                           ldx, gamma, mean, rstd, (const bf16_t*)dy, lddy, (bf16_t*)dx, lddx, dgamma, dbeta, rows, C);
-    else MSSEG_FAIL(MSSEG_EINVAL, "layernorm_bwd: bad dtype");
+    bool done = false;   // by the vector kernel
+    for_dtype(dtype, [&](auto t) { done = launch_ln_vec<typename decltype(t)::type, true>(v, (hipStream_t)stream); });
+    const bool known = done || for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(layernorm_bwd_kernel<T>, dim3(stream_grid(rows)), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx,
+                           gamma, mean, rstd, (const T*)dy, lddy, (T*)dx, lddx, dgamma, dbeta, rows, C);
+    });
+    if (!known) MSSEG_FAIL(MSSEG_EINVAL, "layernorm_bwd: bad dtype");
     MSSEG_CHECK_LAUNCH("layernorm_bwd");
     return MSSEG_OK;
 }
@@ -698,8 +659,8 @@ int msseg_layernorm_bwd_add(const void* x, long long ldx, const float* gamma, co
     LnVecParams v{};
     v.x = x; v.ldx = ldx; v.g = gamma; v.y = dx; v.ldy = lddx; v.mean = (float*)mean; v.rstd = (float*)rstd;
     v.dy = dy; v.lddy = lddy; v.rows = rows; v.C = C; v.add = add; v.ldadd = ldadd;
-    const bool done = dtype == MSSEG_F32 ? launch_ln_vec<float, true>(v, (hipStream_t)stream)
-                                         : launch_ln_vec<bf16_t, true>(v, (hipStream_t)stream);
+    bool done = false;
+    for_dtype(dtype, [&](auto t) { done = launch_ln_vec<typename decltype(t)::type, true>(v, (hipStream_t)stream); });
     if (!done) MSSEG_FAIL(MSSEG_EINVAL, "layernorm_bwd_add: rows of %d channels do not take the vector kernel (16-byte chunks, <= 4096 channels)", C);
     MSSEG_CHECK_LAUNCH("layernorm_bwd_add");
     return MSSEG_OK;
@@ -707,26 +668,24 @@ int msseg_layernorm_bwd_add(const void* x, long long ldx, const float* gamma, co
 
 int msseg_gelu_fwd(const void* x, void* y, long long n, int dtype, msseg_stream_t stream) {
     if (!x || !y || n < 1) MSSEG_FAIL(MSSEG_EINVAL, "gelu_fwd: bad args");
-    if (dtype == MSSEG_F32)
-        hipLaunchKernelGGL((gelu_kernel<float, false>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream,
-                           (const float*)x, (const float*)nullptr, (float*)y, n);
-    else if (dtype == MSSEG_BF16)
-        hipLaunchKernelGGL((gelu_kernel<bf16_t, false>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_t*)x, (const bf16_t*)nullptr, (bf16_t*)y, n);
-    else MSSEG_FAIL(MSSEG_EINVAL, "gelu_fwd: bad dtype");
+    const bool known = for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((gelu_kernel<T, false>), dim3(stream_grid(n, 1024)), dim3(256), 0, (hipStream_t)stream, (const T*)x,
+                           (const T*)nullptr, (T*)y, n);
+    });
+    if (!known) MSSEG_FAIL(MSSEG_EINVAL, "gelu_fwd: bad dtype");
     MSSEG_CHECK_LAUNCH("gelu_fwd");
     return MSSEG_OK;
 }
 
 int msseg_gelu_bwd(const void* x, const void* dy, void* dx, long long n, int dtype, msseg_stream_t stream) {
     if (!x || !dy || !dx || n < 1) MSSEG_FAIL(MSSEG_EINVAL, "gelu_bwd: bad args");
-    if (dtype == MSSEG_F32)
-        hipLaunchKernelGGL((gelu_kernel<float, true>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
-                           (const float*)dy, (float*)dx, n);
-    else if (dtype == MSSEG_BF16)
-        hipLaunchKernelGGL((gelu_kernel<bf16_t, true>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, n);
-    else MSSEG_FAIL(MSSEG_EINVAL, "gelu_bwd: bad dtype");
+    const bool known = for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((gelu_kernel<T, true>), dim3(stream_grid(n, 1024)), dim3(256), 0, (hipStream_t)stream, (const T*)x,
+                           (const T*)dy, (T*)dx, n);
+    });
+    if (!known) MSSEG_FAIL(MSSEG_EINVAL, "gelu_bwd: bad dtype");
     MSSEG_CHECK_LAUNCH("gelu_bwd");
     return MSSEG_OK;
 }

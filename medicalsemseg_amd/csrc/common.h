@@ -115,12 +115,45 @@ static inline bool msseg_aligned_bf16(int dtype, const void* a, long long lda, i
     return dtype == MSSEG_BF16 && !((lda % 8) || (ldb % 8) || ((uintptr_t)a & 15) || ((uintptr_t)b & 15) || lda < ca || ldb < cb);
 }
 
-// store 4 consecutive channel values
-template <typename T> MSSEG_DEVFN void store4(T* p, const f32x4_t& v);
-template <> MSSEG_DEVFN void store4<float>(float* p, const f32x4_t& v) { *(f32x4_t*)p = v; }
-template <> MSSEG_DEVFN void store4<bf16_t>(bf16_t* p, const f32x4_t& v) {
-    bf16x4_t o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-    *(bf16x4_t*)p = o;
+// ---- the streaming kernels' accesses: channels as floats in registers -------------------------------------
+// one 16-byte chunk at p (16-byte aligned) <-> DT<T>::EPC floats
+template <typename T> struct Chunk;
+template <> struct Chunk<bf16_t> {
+    static constexpr int E = 8;
+    static MSSEG_DEVFN void load(const bf16_t* p, float* f) {
+        const bf16x8_t v = *(const bf16x8_t*)p;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = (float)v[e];
+    }
+    static MSSEG_DEVFN void store(bf16_t* p, const float* f) {
+        bf16x8_t v;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = (bf16_t)f[e];
+        *(bf16x8_t*)p = v;
+    }
+};
+template <> struct Chunk<float> {
+    static constexpr int E = 4;
+    static MSSEG_DEVFN void load(const float* p, float* f) {
+        const f32x4_t v = *(const f32x4_t*)p;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) f[e] = v[e];
+    }
+    static MSSEG_DEVFN void store(float* p, const float* f) { *(f32x4_t*)p = f32x4_t{f[0], f[1], f[2], f[3]}; }
+};
+
+// 4 consecutive channels at p (aligned to 4 elements) <-> 4 floats
+template <typename T> MSSEG_DEVFN void load4(const T* p, float* f);
+template <> MSSEG_DEVFN void load4<float>(const float* p, float* f) { Chunk<float>::load(p, f); }
+template <> MSSEG_DEVFN void load4<bf16_t>(const bf16_t* p, float* f) {
+    const bf16x4_t v = *(const bf16x4_t*)p;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) f[e] = (float)v[e];
+}
+template <typename T> MSSEG_DEVFN void store4(T* p, const float* f);
+template <> MSSEG_DEVFN void store4<float>(float* p, const float* f) { Chunk<float>::store(p, f); }
+template <> MSSEG_DEVFN void store4<bf16_t>(bf16_t* p, const float* f) {
+    *(bf16x4_t*)p = bf16x4_t{(bf16_t)f[0], (bf16_t)f[1], (bf16_t)f[2], (bf16_t)f[3]};
 }
 
 MSSEG_DEVFN float wave_sum(float v) {
@@ -192,3 +225,27 @@ static inline int scratch_ok(const void* scratch, size_t bytes, const char* who)
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline long long ceil_div_ll(long long a, long long b) { return (a + b - 1) / b; }
+
+// ---- host side of the streaming launches ------------------------------------------------------------------
+// grid of a grid-stride launch over `items`, a block taking items_per_block per pass: enough blocks for one pass, at most
+// 16 per CU, at least one
+static inline int stream_grid(long long items, long long items_per_block = 256) {
+    long long b = ceil_div_ll(items, items_per_block);
+    const long long cap = (long long)msseg_num_cus() * 16;
+    if (b > cap) b = cap;
+    return (int)(b < 1 ? 1 : b);
+}
+
+// elements of a 16-byte chunk for a run-time dtype code (DT<T>::EPC)
+static inline int epc_of(int dtype) { return dtype == MSSEG_F32 ? 4 : 8; }
+
+// calls f(type_tag<T>{}) with T = float / bf16_t for a run-time dtype code, so that a templated launch is written once:
+//   for_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type; hipLaunchKernelGGL(kernel<T>, ...); });
+// false, and f not called, for any other code
+template <typename T> struct type_tag { using type = T; };
+template <typename F> static inline bool for_dtype(int dtype, F&& f) {
+    if (dtype == MSSEG_F32) f(type_tag<float>{});
+    else if (dtype == MSSEG_BF16) f(type_tag<bf16_t>{});
+    else return false;
+    return true;
+}

@@ -412,13 +412,6 @@ __global__ __launch_bounds__(256) void cc_hist_kernel(const unsigned char* map, 
     if (c > 0 && c < C && s_h[c] > 0) atomicAdd(stats + S * c + col, s_h[c]);
 }
 
-inline unsigned cc_grid(long long n, int per) {
-    long long g = ceil_div_ll(n, per);
-    const long long cap = (long long)msseg_num_cus() * 16;
-    if (g > cap) g = cap;
-    return (unsigned)(g < 1 ? 1 : g);
-}
-
 // One labelling.  fc == 0: the components of every foreground class; afterwards L[v] is the root of v's component (-1 where
 // v joins nothing) and cnt[root] its size.  fc >= 1: the components of the complement of class fc (cc_key), without the
 // flatten + count pass: L[v] leads to the root (cc_final_root) and cnt[root] >= 1.
@@ -429,13 +422,13 @@ void cc_label(hipStream_t s, const unsigned char* map, int D, int H, int W, int 
     if (connectivity == 6) {
         hipLaunchKernelGGL(cc_tile_kernel<6>, dim3((unsigned)tiles), dim3(256), 0, s, map, D, H, W, C, fc, tiles_y, tiles_x, L,
                            cnt);
-        hipLaunchKernelGGL(cc_border_kernel<6>, dim3(cc_grid(V, 256)), dim3(256), 0, s, map, D, H, W, C, fc, L);
+        hipLaunchKernelGGL(cc_border_kernel<6>, dim3(stream_grid(V)), dim3(256), 0, s, map, D, H, W, C, fc, L);
     } else {
         hipLaunchKernelGGL(cc_tile_kernel<26>, dim3((unsigned)tiles), dim3(256), 0, s, map, D, H, W, C, fc, tiles_y, tiles_x, L,
                            cnt);
-        hipLaunchKernelGGL(cc_border_kernel<26>, dim3(cc_grid(V, 256)), dim3(256), 0, s, map, D, H, W, C, fc, L);
+        hipLaunchKernelGGL(cc_border_kernel<26>, dim3(stream_grid(V)), dim3(256), 0, s, map, D, H, W, C, fc, L);
     }
-    if (!fc) hipLaunchKernelGGL(cc_count_kernel, dim3(cc_grid(V, 256)), dim3(256), 0, s, (int)V, L, cnt);
+    if (!fc) hipLaunchKernelGGL(cc_count_kernel, dim3(stream_grid(V)), dim3(256), 0, s, (int)V, L, cnt);
 }
 
 }  // namespace
@@ -457,8 +450,8 @@ extern "C" int msseg_keep_largest_u8(const uint8_t* lab, int D, int H, int W, in
     if (hipMemsetAsync(stats, 0, (size_t)n_classes * 4 * sizeof(int32_t), s) != hipSuccess)
         MSSEG_FAIL(MSSEG_ELAUNCH, "keep_largest_u8: memset failed");
     cc_label(s, lab, D, H, W, n_classes, connectivity, 0, L, cnt);
-    hipLaunchKernelGGL(cc_select_kernel, dim3(cc_grid(V, 256)), dim3(256), 0, s, lab, (int)V, n_classes, L, cnt, 0, 4, stats);
-    hipLaunchKernelGGL(cc_filter_kernel, dim3(cc_grid(V, 256)), dim3(256), 0, s, lab, (int)V, n_classes, L, cnt, 0, 1, 4, stats,
+    hipLaunchKernelGGL(cc_select_kernel, dim3(stream_grid(V)), dim3(256), 0, s, lab, (int)V, n_classes, L, cnt, 0, 4, stats);
+    hipLaunchKernelGGL(cc_filter_kernel, dim3(stream_grid(V)), dim3(256), 0, s, lab, (int)V, n_classes, L, cnt, 0, 1, 4, stats,
                        out);
     hipLaunchKernelGGL(cc_finalize_kernel, dim3(1), dim3(64), 0, s, n_classes, stats);
     MSSEG_CHECK_LAUNCH("keep_largest_u8");
@@ -483,7 +476,7 @@ extern "C" int msseg_postprocess_u8(const uint8_t* lab, int D, int H, int W, int
     hipStream_t s = (hipStream_t)stream;
     int* L = work;
     int* cnt = work + V;
-    const unsigned grid = cc_grid(V, 256);
+    const unsigned grid = stream_grid(V);
     const int labelled = min_size > 1 || keep_largest;
     const int hist = fill_holes || !labelled;      // else the final voxel counts follow from the labelling's own sums
     if (hipMemsetAsync(stats, 0, (size_t)n_classes * 6 * sizeof(int32_t), s) != hipSuccess)
@@ -503,7 +496,7 @@ extern "C" int msseg_postprocess_u8(const uint8_t* lab, int D, int H, int W, int
         const long long faces = 2 * ((long long)H * W + (long long)D * W + (long long)D * H);
         for (int fc = 1; fc < n_classes; ++fc) {      // in ascending order, each class on the map the class before left
             cc_label(s, out, D, H, W, n_classes, hole_connectivity, fc, L, cnt);
-            hipLaunchKernelGGL(cc_face_kernel, dim3(cc_grid(faces, 256)), dim3(256), 0, s, out, D, H, W, fc, L, cnt);
+            hipLaunchKernelGGL(cc_face_kernel, dim3(stream_grid(faces)), dim3(256), 0, s, out, D, H, W, fc, L, cnt);
             hipLaunchKernelGGL(cc_fill_kernel, dim3(grid), dim3(256), 0, s, out, (int)V, fc, L, cnt, stats + 6 * fc + 4);
         }
     }

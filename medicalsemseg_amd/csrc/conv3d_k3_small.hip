@@ -178,11 +178,6 @@ struct K3sFinParams {
 constexpr int FCH = 4;        // channels of a finish workgroup (one float4 per stage group and voxel)
 constexpr int NKG_MAX = 8;    // stage groups
 
-MSSEG_DEVFN void store4_bf16(bf16_t* p, const float* v) {
-    bf16x4_t o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-    *(bf16x4_t*)p = o;
-}
-
 // fixed-order sum of NV per-thread values over the BS threads of the block: lanes by xor-shuffles, then the per-wave rows
 // are added in wave order by the first NV threads and broadcast through LDS.  lds: >= (BS / 64 + 1) * NV floats.
 template <int BS, int NV>
@@ -317,7 +312,7 @@ __global__ __launch_bounds__(BS) void k3s_fwd_finish_kernel(const K3sFinParams p
 #pragma unroll
                 for (int e = 0; e < FCH; ++e) m[e] = fmaxf(m[e], (float)a[e]);
             }
-            store4_bf16(p.pooled + ((long long)n * PD * PH * PW + pv) * p.ldp + c0, m);
+            store4(p.pooled + ((long long)n * PD * PH * PW + pv) * p.ldp + c0, m);
         }
     }
 }
@@ -336,7 +331,7 @@ __global__ __launch_bounds__(BS) void k3s_bwd_plain_kernel(const K3sFinParams p)
     sum_partials<VPT, NKG>(p, blockIdx.x, row, ok, a);
 #pragma unroll
     for (int i = 0; i < VPT; ++i)
-        if (ok[i]) store4_bf16(p.dx + row[i] * p.lddx + c0, a[i]);
+        if (ok[i]) store4(p.dx + row[i] * p.lddx + c0, a[i]);
 }
 
 // input-gradient finish, unit mode: the conv's input was the activation of a conv + InstanceNorm + LeakyReLU unit (raw
@@ -425,7 +420,7 @@ __global__ __launch_bounds__(BS) void k3s_bwd_unit_kernel(const K3sFinParams p) 
                     const float xh = ((float)yb[i][e] - mean[j][e]) * rstd[j][e];
                     o[e] = rstd[j][e] * ga[e] * (a[i][e] - s[j * 8 + e] * inv - xh * (s[j * 8 + 4 + e] * inv));
                 }
-                store4_bf16(p.dx + row[i] * p.lddx + c0, o);
+                store4(p.dx + row[i] * p.lddx + c0, o);
             }
         }
     }

@@ -275,7 +275,8 @@ __global__ __launch_bounds__(256) void aug_crop_multi_kernel(const VolDesc* __re
                 f32x4_t v = *(const f32x4u_t*)(vd.img + (long long)c * V + srow + sx);
                 if (fx) v = f32x4_t{v[3], v[2], v[1], v[0]};
                 v = (v + row.shift) * row.scale;
-                store4<TO>(out_img + ((long long)b * C + c) * R3 + orow + x, v);
+                const float o[4] = {v[0], v[1], v[2], v[3]};
+                store4<TO>(out_img + ((long long)b * C + c) * R3 + orow + x, o);
             }
             if (vd.lab) {
                 const unsigned char* l = vd.lab + srow + sx;
@@ -458,13 +459,12 @@ int msseg_aug_crop_multi(const void* volumes, int nvol, const void* rows, const 
     const int nruns = ceil_div(R, 4);
     const int bx = nruns < 256 ? nruns : 256, by = 256 / bx;
     dim3 block(bx, by), grid((unsigned)ceil_div(R, by), (unsigned)R, (unsigned)npatch);
-    if (out_dtype == MSSEG_F32)
-        hipLaunchKernelGGL(aug_crop_multi_kernel<float>, grid, block, 0, (hipStream_t)stream, (const VolDesc*)volumes, nvol,
-                           (const PickRow*)rows, picks, (float*)out_img, out_lab, C, R);
-    else if (out_dtype == MSSEG_BF16)
-        hipLaunchKernelGGL(aug_crop_multi_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (const VolDesc*)volumes, nvol,
-                           (const PickRow*)rows, picks, (bf16_t*)out_img, out_lab, C, R);
-    else MSSEG_FAIL(MSSEG_EINVAL, "aug_crop_multi: bad dtype");
+    const bool known = for_dtype(out_dtype, [&](auto t) {
+        using TO = typename decltype(t)::type;
+        hipLaunchKernelGGL(aug_crop_multi_kernel<TO>, grid, block, 0, (hipStream_t)stream, (const VolDesc*)volumes, nvol,
+                           (const PickRow*)rows, picks, (TO*)out_img, out_lab, C, R);
+    });
+    if (!known) MSSEG_FAIL(MSSEG_EINVAL, "aug_crop_multi: bad dtype");
     MSSEG_CHECK_LAUNCH("aug_crop_multi");
     return MSSEG_OK;
 }
@@ -475,13 +475,12 @@ int msseg_aug_crop_affine(const void* volumes, int nvol, const void* rows, const
         R < 1 || R > 65535)
         MSSEG_FAIL(MSSEG_EINVAL, "aug_crop_affine: bad args");
     dim3 block(32, 8), grid((unsigned)ceil_div(R, 8), (unsigned)R, (unsigned)npatch);
-    if (out_dtype == MSSEG_F32)
-        hipLaunchKernelGGL(aug_crop_affine_kernel<float>, grid, block, 0, (hipStream_t)stream, (const VolDesc*)volumes, nvol,
-                           (const PickRow*)rows, picks, mats, (float*)out_img, out_lab, C, R, pad_value);
-    else if (out_dtype == MSSEG_BF16)
-        hipLaunchKernelGGL(aug_crop_affine_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (const VolDesc*)volumes, nvol,
-                           (const PickRow*)rows, picks, mats, (bf16_t*)out_img, out_lab, C, R, pad_value);
-    else MSSEG_FAIL(MSSEG_EINVAL, "aug_crop_affine: bad dtype");
+    const bool known = for_dtype(out_dtype, [&](auto t) {
+        using TO = typename decltype(t)::type;
+        hipLaunchKernelGGL(aug_crop_affine_kernel<TO>, grid, block, 0, (hipStream_t)stream, (const VolDesc*)volumes, nvol,
+                           (const PickRow*)rows, picks, mats, (TO*)out_img, out_lab, C, R, pad_value);
+    });
+    if (!known) MSSEG_FAIL(MSSEG_EINVAL, "aug_crop_affine: bad dtype");
     MSSEG_CHECK_LAUNCH("aug_crop_affine");
     return MSSEG_OK;
 }

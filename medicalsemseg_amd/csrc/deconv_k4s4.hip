@@ -296,8 +296,9 @@ int msseg_deconv_k4s4_fwd(const void* x, long long ldx, const void* wp, const fl
         return MSSEG_OK;
     }
     const int gx = grid_plain((long long)N * D * H * W * 64 * Cout);
-    if (dtype == MSSEG_F32) hipLaunchKernelGGL(dc4_fwd_plain_kernel<float>, dim3(gx), dim3(D4_THREADS), 0, stream, p);
-    else hipLaunchKernelGGL(dc4_fwd_plain_kernel<bf16_t>, dim3(gx), dim3(D4_THREADS), 0, stream, p);
+    for_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL(dc4_fwd_plain_kernel<typename decltype(t)::type>, dim3(gx), dim3(D4_THREADS), 0, stream, p);
+    });
     MSSEG_CHECK_LAUNCH("deconv_k4s4_fwd");
     return MSSEG_OK;
 }
@@ -331,8 +332,9 @@ int msseg_deconv_k4s4_bwd_data(const void* dy, long long lddy, const void* wp, v
         return MSSEG_OK;
     }
     const int gx = grid_plain((long long)N * D * H * W * Cin);
-    if (dtype == MSSEG_F32) hipLaunchKernelGGL(dc4_bwd_plain_kernel<float>, dim3(gx), dim3(D4_THREADS), 0, stream, p);
-    else hipLaunchKernelGGL(dc4_bwd_plain_kernel<bf16_t>, dim3(gx), dim3(D4_THREADS), 0, stream, p);
+    for_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL(dc4_bwd_plain_kernel<typename decltype(t)::type>, dim3(gx), dim3(D4_THREADS), 0, stream, p);
+    });
     MSSEG_CHECK_LAUNCH("deconv_k4s4_bwd_data");
     return MSSEG_OK;
 }
@@ -380,8 +382,10 @@ int msseg_deconv_k4s4_wgrad(const void* x, long long ldx, const void* dy, long l
         if (gx < 1) gx = 1;
         const long long per = (NV + gx - 1) / gx;
         dim3 grid((unsigned)gx, 16);
-        if (dtype == MSSEG_F32) hipLaunchKernelGGL(dc4_wgrad_plain_kernel<float>, grid, dim3(D4_THREADS), 0, stream, p, (float*)workspace, per);
-        else hipLaunchKernelGGL(dc4_wgrad_plain_kernel<bf16_t>, grid, dim3(D4_THREADS), 0, stream, p, (float*)workspace, per);
+        for_dtype(dtype, [&](auto t) {
+            hipLaunchKernelGGL(dc4_wgrad_plain_kernel<typename decltype(t)::type>, grid, dim3(D4_THREADS), 0, stream, p,
+                               (float*)workspace, per);
+        });
         MSSEG_CHECK_LAUNCH("deconv_k4s4_wgrad");
         r.CH = 4; r.nwg = (int)gx;
     }

@@ -16,31 +16,6 @@
 
 namespace {
 
-template <typename T> struct Chunk;
-template <> struct Chunk<bf16_t> {
-    static constexpr int E = 8;
-    static MSSEG_DEVFN void load(const bf16_t* p, float* f) {
-        const bf16x8_t v = *(const bf16x8_t*)p;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] = (float)v[e];
-    }
-    static MSSEG_DEVFN void store(bf16_t* p, const float* f) {
-        bf16x8_t v;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = (bf16_t)f[e];
-        *(bf16x8_t*)p = v;
-    }
-};
-template <> struct Chunk<float> {
-    static constexpr int E = 4;
-    static MSSEG_DEVFN void load(const float* p, float* f) {
-        const f32x4_t v = *(const f32x4_t*)p;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) f[e] = v[e];
-    }
-    static MSSEG_DEVFN void store(float* p, const float* f) { *(f32x4_t*)p = f32x4_t{f[0], f[1], f[2], f[3]}; }
-};
-
 struct DwParams {
     const void* x; long long ldx;
     const void* w;         // [27][C] tap-major, compute dtype (one 16-byte chunk per tap and thread)
@@ -222,7 +197,7 @@ __global__ __launch_bounds__(256) void dwconv3_wgrad_finalize_kernel(const float
 int check(const void* x, long long ldx, const void* y, long long ldy, int N, int D, int H, int W, int C, int dtype, const char* what) {
     if (!x || !y) MSSEG_FAIL(MSSEG_EINVAL, "%s: null pointer", what);
     if (dtype != MSSEG_F32 && dtype != MSSEG_BF16) MSSEG_FAIL(MSSEG_EINVAL, "%s: bad dtype", what);
-    const int esz = dtype == MSSEG_F32 ? 4 : 2, epc = 16 / esz;
+    const int epc = epc_of(dtype);
     if (N < 1 || D < 1 || H < 1 || W < 1 || C < 1 || C % epc) MSSEG_FAIL(MSSEG_EINVAL, "%s: channels must be a multiple of %d", what, epc);
     if (ldx < C || ldy < C || ldx % epc || ldy % epc || ((uintptr_t)x & 15) || ((uintptr_t)y & 15))
         MSSEG_FAIL(MSSEG_EINVAL, "%s: tensors must be 16-byte aligned with voxel strides that are multiples of %d", what, epc);
@@ -230,13 +205,11 @@ int check(const void* x, long long ldx, const void* y, long long ldy, int N, int
 }
 
 int launch_dw(const DwParams& p, int dtype, msseg_stream_t stream) {
-    const int N = p.N, D = p.D, H = p.H, W = p.W, C = p.C;
-    const long long total = (long long)N * D * H * W * (C / (dtype == MSSEG_F32 ? 4 : 8));
-    long long gx = (total + 255) / 256;
-    const long long cap = (long long)msseg_num_cus() * 16;
-    if (gx > cap) gx = cap;
-    if (dtype == MSSEG_F32) hipLaunchKernelGGL(dwconv3_kernel<float>, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(dwconv3_kernel<bf16_t>, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, p);
+    const long long total = (long long)p.N * p.D * p.H * p.W * (p.C / epc_of(dtype));
+    for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(dwconv3_kernel<T>, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, p);
+    });
     MSSEG_CHECK_LAUNCH("dwconv3d_k3_fwd");
     return MSSEG_OK;
 }
@@ -272,18 +245,17 @@ int msseg_dwconv3d_k3_wgrad(const void* x, long long ldx, const void* dy, long l
     const size_t row_bytes = (size_t)28 * C * sizeof(float);
     long long rows = (long long)((scratch_bytes - MSSEG_SCRATCH_COUNTER_BYTES) / row_bytes);
     if (rows < 1) MSSEG_FAIL(MSSEG_EINVAL, "dwconv3d_k3_wgrad: %d channels exceed the reduce scratch", C);
-    const int epc = dtype == MSSEG_F32 ? 4 : 8;
-    const int gy = ceil_div(3 * (C / epc), 64);
+    const int gy = ceil_div(3 * (C / epc_of(dtype)), 64);
     long long want = (long long)msseg_num_cus() * 8 / gy;      // several workgroups per CU in total: the voxel loop is latency-bound
     if (want < 1) want = 1;
     if (rows > want) rows = want;
     if (rows > (NV + 3) / 4) rows = (NV + 3) / 4;
     DwWgParams p{x, ldx, dy, lddy, ws, N, D, H, W, C, ceil_div_ll(NV, rows)};
     rows = ceil_div_ll(NV, p.vox_per_row);
-    if (dtype == MSSEG_F32)
-        hipLaunchKernelGGL(dwconv3_wgrad_kernel<float>, dim3((unsigned)rows, gy), dim3(256), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(dwconv3_wgrad_kernel<bf16_t>, dim3((unsigned)rows, gy), dim3(256), 0, (hipStream_t)stream, p);
+    for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(dwconv3_wgrad_kernel<T>, dim3((unsigned)rows, gy), dim3(256), 0, (hipStream_t)stream, p);
+    });
     MSSEG_CHECK_LAUNCH("dwconv3d_k3_wgrad");
     hipLaunchKernelGGL(dwconv3_wgrad_finalize_kernel, dim3(ceil_div(28 * C, 64)), dim3(256), 0, (hipStream_t)stream, ws,
                        (int)rows, C, dw, dbias, accumulate_w, accumulate_b);

@@ -34,6 +34,7 @@ template <int K, int L> struct Geo {
     static constexpr int HALO = ZD * PS;  // chunks
 };
 
+// unpack of a chunk that is already in registers (the LDS halo reads); memory <-> floats is Chunk<T> of common.h
 template <typename T> struct Cv;
 template <> struct Cv<bf16_t> {
     static constexpr int E = 8;
@@ -44,12 +45,6 @@ template <> struct Cv<bf16_t> {
             f[2 * i + 1] = __builtin_bit_cast(float, v[i] & 0xffff0000u);
         }
     }
-    static MSSEG_DEVFN void store(bf16_t* p, const float* f) {
-        bf16x8_t v;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = (bf16_t)f[e];
-        *(bf16x8_t*)p = v;
-    }
 };
 template <> struct Cv<float> {
     static constexpr int E = 4;
@@ -58,7 +53,6 @@ template <> struct Cv<float> {
 #pragma unroll
         for (int i = 0; i < 4; ++i) f[i] = fv[i];
     }
-    static MSSEG_DEVFN void store(float* p, const float* f) { *(f32x4_t*)p = f32x4_t{f[0], f[1], f[2], f[3]}; }
 };
 
 struct DwLParams {
@@ -170,7 +164,7 @@ __global__ __launch_bounds__(NT) void dwconvl_fwd_kernel(const DwLParams p) {
 #pragma unroll
     for (int o = 0; o < TW; ++o) {
         const int gw = tw * TW + o;
-        if (gw < p.W) Cv<T>::store(yg + (vrow + gw) * p.ldy + c0, acc[o]);
+        if (gw < p.W) Chunk<T>::store(yg + (vrow + gw) * p.ldy + c0, acc[o]);
     }
 }
 
@@ -331,7 +325,7 @@ int launch_wgrad(const DwLWgParams& p, int rows, hipStream_t stream) {
 // partial rows a launch uses: enough blocks to fill the chip, never more than there are tiles
 long long wgrad_rows(int N, int D, int H, int W, int C, int dtype) {
     const long long jobs = (long long)N * ceil_div(D, TD) * ceil_div(H, TH) * ceil_div(W, TW);
-    const int nch = C / (dtype == MSSEG_F32 ? 4 : 8);
+    const int nch = C / epc_of(dtype);
     long long rows = ceil_div(2 * msseg_num_cus(), nch);
     if (rows > jobs) rows = jobs;
     return rows < 1 ? 1 : rows;

@@ -35,31 +35,13 @@ int msseg_num_cus(void) {
 
 namespace {
 
-template <typename T> struct Chunk {
+// A chunk's floats as one object, filled and written by Chunk<T> of common.h.  The kernels here keep this member form:
+// on plain float arrays they compile to different code (the struct member carries its own alias information).
+template <typename T> struct ChunkV {
     static constexpr int EPC = DT<T>::EPC;
     float v[EPC];
-    MSSEG_DEVFN void load(const T* p) {
-        if constexpr (sizeof(T) == 4) {
-            f32x4_t t = *(const f32x4_t*)p;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = t[e];
-        } else {
-            bf16x8_t t = *(const bf16x8_t*)p;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = (float)t[e];
-        }
-    }
-    MSSEG_DEVFN void store(T* p) const {
-        if constexpr (sizeof(T) == 4) {
-            f32x4_t t = {v[0], v[1], v[2], v[3]};
-            *(f32x4_t*)p = t;
-        } else {
-            bf16x8_t t;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) t[e] = (bf16_t)v[e];
-            *(bf16x8_t*)p = t;
-        }
-    }
+    MSSEG_DEVFN void load(const T* p) { Chunk<T>::load(p, v); }
+    MSSEG_DEVFN void store(T* p) const { Chunk<T>::store(p, v); }
 };
 
 inline bool vec_ok(const void* p, long long ld, int C, int esz) {
@@ -201,7 +183,7 @@ __global__ __launch_bounds__(RED_THREADS) void channel_stats_kernel(const T* __r
 #pragma unroll 8
             for (long long r = r0 + rl; r < r1; r += rows_par) {
                 if constexpr (VEC) {
-                    Chunk<T> c;
+                    ChunkV<T> c;
                     c.load(xn + r * ldx + gg * W);
 #pragma unroll
                     for (int e = 0; e < W; ++e) { s[e] += c.v[e]; s2[e] += c.v[e] * c.v[e]; }
@@ -263,7 +245,7 @@ __global__ __launch_bounds__(256) void ln_param_grad_kernel(const T* __restrict_
             for (long long r = r0 + rl; r < r1; r += rows_par) {
                 const float mu = mean[r], rs = rstd[r];
                 if constexpr (VEC) {
-                    Chunk<T> cx, cd;
+                    ChunkV<T> cx, cd;
                     cx.load(x + r * ldx + gg * W);
                     cd.load(dy + r * lddy + gg * W);
 #pragma unroll
@@ -430,7 +412,7 @@ __global__ __launch_bounds__(MODE == 1 ? RED_THREADS : 256) void instnorm_kernel
             for (long long r = r0 + rl; r < r1; r += p.rows_par) {
                 float xv[W], o[W], yv[W], dv[W];
                 if constexpr (VEC) {
-                    Chunk<T> c; c.load(xn + r * p.ldx + gg * W);
+                    ChunkV<T> c; c.load(xn + r * p.ldx + gg * W);
 #pragma unroll
                     for (int e = 0; e < W; ++e) xv[e] = c.v[e];
                 } else {
@@ -442,7 +424,7 @@ __global__ __launch_bounds__(MODE == 1 ? RED_THREADS : 256) void instnorm_kernel
                     for (int e = 0; e < W; ++e) rv[e] = 0.f;
                     if (resn) {
                         if constexpr (VEC) {
-                            Chunk<T> c; c.load(resn + r * p.ldr + gg * W);
+                            ChunkV<T> c; c.load(resn + r * p.ldr + gg * W);
 #pragma unroll
                             for (int e = 0; e < W; ++e) rv[e] = c.v[e];
                         } else {
@@ -455,7 +437,7 @@ __global__ __launch_bounds__(MODE == 1 ? RED_THREADS : 256) void instnorm_kernel
                         o[e] = z > 0.f ? z : z * p.slope;
                     }
                     if constexpr (VEC) {
-                        Chunk<T> c;
+                        ChunkV<T> c;
 #pragma unroll
                         for (int e = 0; e < W; ++e) c.v[e] = o[e];
                         c.store(yo + r * p.ldy + gg * W);
@@ -464,11 +446,11 @@ __global__ __launch_bounds__(MODE == 1 ? RED_THREADS : 256) void instnorm_kernel
                     }
                 } else {
                     if constexpr (VEC) {
-                        Chunk<T> d; d.load(dyn + r * p.lddy + gg * W);
+                        ChunkV<T> d; d.load(dyn + r * p.lddy + gg * W);
 #pragma unroll
                         for (int e = 0; e < W; ++e) dv[e] = d.v[e];
                         if (yn != nullptr) {
-                            Chunk<T> c; c.load(yn + r * p.ldy + gg * W);
+                            ChunkV<T> c; c.load(yn + r * p.ldy + gg * W);
 #pragma unroll
                             for (int e = 0; e < W; ++e) yv[e] = c.v[e];
                         } else {   // sign of the pre-activation, recomputed exactly as the forward formed it
@@ -493,7 +475,7 @@ __global__ __launch_bounds__(MODE == 1 ? RED_THREADS : 256) void instnorm_kernel
                     }
                     if constexpr (MODE == 2) {
                         if constexpr (VEC) {
-                            Chunk<T> c;
+                            ChunkV<T> c;
 #pragma unroll
                             for (int e = 0; e < W; ++e) c.v[e] = o[e];
                             c.store(dxn + r * p.lddx + gg * W);
@@ -576,7 +558,7 @@ __global__ __launch_bounds__(256) void instnorm_pool_fwd_kernel(const NormPoolPa
             sh[e] = (p.beta ? p.beta[c] : 0.f) - mean * sc[e];
             best[e] = -INFINITY;
         }
-        Chunk<T> in[8];
+        ChunkV<T> in[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const long long vox = (((long long)n * p.D + 2 * od + (k >> 2)) * p.H + 2 * oh + ((k >> 1) & 1)) * p.W + 2 * ow + (k & 1);
@@ -585,7 +567,7 @@ __global__ __launch_bounds__(256) void instnorm_pool_fwd_kernel(const NormPoolPa
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const long long vox = (((long long)n * p.D + 2 * od + (k >> 2)) * p.H + 2 * oh + ((k >> 1) & 1)) * p.W + 2 * ow + (k & 1);
-            Chunk<T> o;
+            ChunkV<T> o;
 #pragma unroll
             for (int e = 0; e < WD; ++e) {
                 const float z = in[k].v[e] * sc[e] + sh[e];
@@ -595,7 +577,7 @@ __global__ __launch_bounds__(256) void instnorm_pool_fwd_kernel(const NormPoolPa
             }
             o.store((T*)p.y + vox * p.ldy + g * WD);
         }
-        Chunk<T> b;
+        ChunkV<T> b;
 #pragma unroll
         for (int e = 0; e < WD; ++e) b.v[e] = best[e];
         const long long ovox = (((long long)n * OD + od) * OH + oh) * OW + ow;
@@ -650,8 +632,8 @@ __global__ __launch_bounds__(RED_THREADS) void instnorm_poolbwd_reduce_kernel(co
         if (act && rl < p.rows_par) {
             for (long long cell = c0 + rl; cell < c1; cell += p.rows_par) {
                 const int ow = (int)(cell % OW), oh = (int)((cell / OW) % OH), od = (int)(cell / ((long long)OW * OH));
-                Chunk<T> xin[8], gv;
-                Chunk<T> skin[8];
+                ChunkV<T> xin[8], gv;
+                ChunkV<T> skin[8];
                 long long vox[8];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
@@ -676,7 +658,7 @@ __global__ __launch_bounds__(RED_THREADS) void instnorm_poolbwd_reduce_kernel(co
                 }
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
-                    Chunk<T> o;
+                    ChunkV<T> o;
 #pragma unroll
                     for (int e = 0; e < WD; ++e) {
                         const float dv = (float)(T)(skin[k].v[e] + (arg[e] == k ? gv.v[e] : 0.f));
@@ -794,7 +776,7 @@ __global__ __launch_bounds__(RED_THREADS) void head_dgrad_inbwd_kernel(const Hea
             constexpr int UNR = DW ? 2 : 4;   // the weight-gradient variant carries 32 more accumulators: stay under 256 VGPRs
 #pragma unroll UNR
             for (long long r = r0 + rl; r < r1; r += p.rows_par) {
-                Chunk<T> xc, dc, o;
+                ChunkV<T> xc, dc, o;
                 xc.load(xn + r * p.ldx + gg * WD);
                 dc.load(dyn + r * p.lddy);            // the first EPC (>= 4) channels of the class gradient
 #pragma unroll
@@ -909,7 +891,7 @@ __global__ __launch_bounds__(256) void maxpool2_kernel(const T* __restrict__ x, 
             const long long vox = (((long long)n * D + 2 * od + (k >> 2)) * H + 2 * oh + ((k >> 1) & 1)) * W + 2 * ow + (k & 1);
             float v[WD];
             if constexpr (VEC) {
-                Chunk<T> c; c.load(x + vox * ldx + g * WD);
+                ChunkV<T> c; c.load(x + vox * ldx + g * WD);
 #pragma unroll
                 for (int e = 0; e < WD; ++e) v[e] = c.v[e];
             } else {
@@ -922,7 +904,7 @@ __global__ __launch_bounds__(256) void maxpool2_kernel(const T* __restrict__ x, 
         const long long ovox = (((long long)n * OD + od) * OH + oh) * OW + ow;
         if constexpr (!BWD) {
             if constexpr (VEC) {
-                Chunk<T> c;
+                ChunkV<T> c;
 #pragma unroll
                 for (int e = 0; e < WD; ++e) c.v[e] = best[e];
                 c.store(out + ovox * ldo + g * WD);
@@ -932,7 +914,7 @@ __global__ __launch_bounds__(256) void maxpool2_kernel(const T* __restrict__ x, 
         } else {
             float gv[WD];
             if constexpr (VEC) {
-                Chunk<T> c; c.load(dy + ovox * lddy + g * WD);
+                ChunkV<T> c; c.load(dy + ovox * lddy + g * WD);
 #pragma unroll
                 for (int e = 0; e < WD; ++e) gv[e] = c.v[e];
             } else {
@@ -943,7 +925,7 @@ __global__ __launch_bounds__(256) void maxpool2_kernel(const T* __restrict__ x, 
                 const long long vox = (((long long)n * D + 2 * od + (k >> 2)) * H + 2 * oh + ((k >> 1) & 1)) * W + 2 * ow + (k & 1);
                 T* dst = out + vox * ldo + g * WD;
                 if constexpr (VEC) {
-                    Chunk<T> c;
+                    ChunkV<T> c;
                     if (accumulate) c.load(dst);
                     else {
 #pragma unroll
@@ -1028,7 +1010,7 @@ __global__ __launch_bounds__(256) void add_vec_kernel(const T* __restrict__ a, l
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const long long r = i / cpr;
         const int c = (int)(i - r * cpr) * EPC;
-        Chunk<T> ca, cb, o;
+        ChunkV<T> ca, cb, o;
         ca.load(a + r * lda + c);
         cb.load(b + r * ldb + c);
 #pragma unroll
@@ -1047,7 +1029,7 @@ __global__ __launch_bounds__(256) void axpy_rows_vec_kernel(const T* __restrict_
     constexpr int EPC = DT<T>::EPC;
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total_chunks; i += (long long)gridDim.x * 256) {
         const float sc = s ? s[i / chunks_per_sample] : 1.f;
-        Chunk<T> cb, ca, o;
+        ChunkV<T> cb, ca, o;
         cb.load(b + i * EPC);
         if (a) ca.load(a + i * EPC);
 #pragma unroll
@@ -1185,7 +1167,7 @@ __global__ __launch_bounds__(256) void conv1x1_head_kernel(const T* __restrict__
         // the row in pieces of up to four chunks with all loads of a piece issued before the first multiply (a loop of one load
         // per trip kept 16 bytes in flight per thread: 1.7 TB/s on the 48-channel rows of Swin-UNETR's output block)
         for (int k0 = 0; k0 < Cin; k0 += 4 * WD) {
-            Chunk<T> xc[4];
+            ChunkV<T> xc[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 if (k0 + j * WD < Cin) xc[j].load(xr + k0 + j * WD);
@@ -1238,7 +1220,7 @@ __global__ __launch_bounds__(256) void conv1x1_head_norm_kernel(const T* __restr
         const T* xr = xn + v * ldx;
         // the row in pieces of up to four chunks, all loads of a piece issued before the first use (as conv1x1_head_kernel)
         for (int k0 = 0; k0 < Cin; k0 += 4 * WD) {
-            Chunk<T> xc[4];
+            ChunkV<T> xc[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 if (k0 + j * WD < Cin) xc[j].load(xr + k0 + j * WD);
@@ -1331,27 +1313,14 @@ __global__ __launch_bounds__(256) void sumsq_finalize_kernel(const float* __rest
     if (threadIdx.x == 0) *out = red[0];
 }
 
-inline int grid_for(long long total, int per_thread = 4) {
-    long long b = ceil_div_ll(total, 256LL * per_thread);
-    const long long cap = (long long)msseg_num_cus() * 16;
-    if (b > cap) b = cap;
-    if (b < 1) b = 1;
-    return (int)b;
-}
+int bad_dtype(int dtype) { MSSEG_FAIL(MSSEG_EINVAL, "bad dtype %d", dtype); }
 
 }  // namespace
-
-#define DISPATCH_T(dtype, CALL_F32, CALL_BF16)                                   \
-    do {                                                                         \
-        if ((dtype) == MSSEG_F32) { CALL_F32; }                                  \
-        else if ((dtype) == MSSEG_BF16) { CALL_BF16; }                           \
-        else MSSEG_FAIL(MSSEG_EINVAL, "bad dtype %d", (int)(dtype));             \
-    } while (0)
 
 extern "C" {
 
 size_t msseg_packed_weight_bytes(int M, int T, int K, int cout_block, int dtype) {
-    const int epc = dtype == MSSEG_F32 ? 4 : 8;
+    const int epc = epc_of(dtype);
     const size_t ncb = (size_t)ceil_div(M, cout_block), nkb = (size_t)ceil_div(K, 4 * epc);
     return ncb * nkb * (size_t)T * 4 * (size_t)cout_block * 16;
 }
@@ -1364,11 +1333,12 @@ int msseg_pack_weights(const float* src, void* dst, int dtype, int M, int M0, in
     const int esz = dtype == MSSEG_F32 ? 4 : 2;
     const long long total = (long long)(msseg_packed_weight_bytes(M, T, K, cout_block, dtype) / esz);
     const int nkb = ceil_div(K, 64 / esz);
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(pack_weights_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                                  src, (float*)dst, M, M0, T, K, K0, s_m1, s_m0, s_t, s_k1, s_k0, flip, cout_block, nkb, total),
-               hipLaunchKernelGGL(pack_weights_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                                  src, (bf16_t*)dst, M, M0, T, K, K0, s_m1, s_m0, s_t, s_k1, s_k0, flip, cout_block, nkb, total));
+    const bool known = for_dtype(dtype, [&](auto t) {
+        using TD = typename decltype(t)::type;
+        hipLaunchKernelGGL(pack_weights_kernel<TD>, dim3(stream_grid(total, 1024)), dim3(256), 0, (hipStream_t)stream, src,
+                           (TD*)dst, M, M0, T, K, K0, s_m1, s_m0, s_t, s_k1, s_k0, flip, cout_block, nkb, total);
+    });
+    if (!known) return bad_dtype(dtype);
     MSSEG_CHECK_LAUNCH("pack_weights");
     return MSSEG_OK;
 }
@@ -1377,14 +1347,17 @@ int msseg_pack_weights_batch(const msseg_pack_job* jobs_dev, int njobs, long lon
                              msseg_stream_t stream) {
     if (!jobs_dev || njobs < 1 || njobs > 65535 || max_total < 1 || sum_total < max_total)
         MSSEG_FAIL(MSSEG_EINVAL, "pack_weights_batch: bad args");
-    const long long epc = dtype == MSSEG_F32 ? 4 : 8;
+    const long long epc = epc_of(dtype);
     if (max_total / epc >= 0x7fffffffLL) MSSEG_FAIL(MSSEG_EINVAL, "pack_weights_batch: image too large");
     // sum over the jobs of ceil(chunks / PACK_CPB) <= sum of chunks / PACK_CPB + njobs: the blocks past the end find no job and exit
     const long long gx = sum_total / epc / PACK_CPB + njobs + 1;
     if (gx >= 0x7fffffffLL) MSSEG_FAIL(MSSEG_EINVAL, "pack_weights_batch: too many blocks");
     dim3 grid((unsigned)gx);
-    DISPATCH_T(dtype, hipLaunchKernelGGL(pack_weights_batch_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, jobs_dev, njobs),
-               hipLaunchKernelGGL(pack_weights_batch_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, jobs_dev, njobs));
+    const bool known = for_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL(pack_weights_batch_kernel<typename decltype(t)::type>, grid, dim3(256), 0, (hipStream_t)stream, jobs_dev,
+                           njobs);
+    });
+    if (!known) return bad_dtype(dtype);
     MSSEG_CHECK_LAUNCH("pack_weights_batch");
     return MSSEG_OK;
 }
@@ -1397,25 +1370,34 @@ int msseg_layernorm_param_grad(const void* x, long long ldx, const float* mean, 
     if (!x || !mean || !rstd || !dy || !dgamma || !dbeta || rows < 1 || C < 1)
         MSSEG_FAIL(MSSEG_EINVAL, "layernorm_param_grad: bad args");
     if (int rc = scratch_ok(scratch, scratch_bytes, "layernorm_param_grad")) return rc;
-    DISPATCH_T(dtype,
-               return launch_ln_param_grad<float>(x, ldx, dy, lddy, mean, rstd, dgamma, dbeta, accumulate, rows, C, scratch, (hipStream_t)stream),
-               return launch_ln_param_grad<bf16_t>(x, ldx, dy, lddy, mean, rstd, dgamma, dbeta, accumulate, rows, C, scratch, (hipStream_t)stream));
+    int rc = MSSEG_OK;
+    const bool known = for_dtype(dtype, [&](auto t) {
+        rc = launch_ln_param_grad<typename decltype(t)::type>(x, ldx, dy, lddy, mean, rstd, dgamma, dbeta, accumulate, rows, C, scratch,
+                                                              (hipStream_t)stream);
+    });
+    return known ? rc : bad_dtype(dtype);
 }
 
 int msseg_channel_stats(const void* x, long long ldx, float* stats, int N, long long S, int C, void* scratch,
                         size_t scratch_bytes, int dtype, msseg_stream_t stream) {
     if (!x || !stats || N < 1 || S < 1 || C < 1 || ldx < C) MSSEG_FAIL(MSSEG_EINVAL, "channel_stats: bad args");
     if (int rc = scratch_ok(scratch, scratch_bytes, "channel_stats")) return rc;
-    DISPATCH_T(dtype, return launch_stats<float>(x, ldx, stats, N, S, C, 2, 0, scratch, (hipStream_t)stream),
-               return launch_stats<bf16_t>(x, ldx, stats, N, S, C, 2, 0, scratch, (hipStream_t)stream));
+    int rc = MSSEG_OK;
+    const bool known = for_dtype(dtype, [&](auto t) {
+        rc = launch_stats<typename decltype(t)::type>(x, ldx, stats, N, S, C, 2, 0, scratch, (hipStream_t)stream);
+    });
+    return known ? rc : bad_dtype(dtype);
 }
 
 int msseg_channel_sum(const void* x, long long ldx, float* out, long long rows, int C, int accumulate, void* scratch,
                       size_t scratch_bytes, int dtype, msseg_stream_t stream) {
     if (!x || !out || rows < 1 || C < 1 || ldx < C) MSSEG_FAIL(MSSEG_EINVAL, "channel_sum: bad args");
     if (int rc = scratch_ok(scratch, scratch_bytes, "channel_sum")) return rc;
-    DISPATCH_T(dtype, return launch_stats<float>(x, ldx, out, 1, rows, C, 1, accumulate, scratch, (hipStream_t)stream),
-               return launch_stats<bf16_t>(x, ldx, out, 1, rows, C, 1, accumulate, scratch, (hipStream_t)stream));
+    int rc = MSSEG_OK;
+    const bool known = for_dtype(dtype, [&](auto t) {
+        rc = launch_stats<typename decltype(t)::type>(x, ldx, out, 1, rows, C, 1, accumulate, scratch, (hipStream_t)stream);
+    });
+    return known ? rc : bad_dtype(dtype);
 }
 
 int msseg_instnorm_act_fwd(const void* x, long long ldx, const float* stats, const float* gamma, const float* beta,
@@ -1427,8 +1409,9 @@ int msseg_instnorm_act_fwd(const void* x, long long ldx, const float* stats, con
     p.y = y; p.ldy = ldy; p.S = S; p.C = C; p.eps = eps; p.slope = slope;
     const int esz = dtype == MSSEG_F32 ? 4 : 2;
     const bool vec = vec_ok(x, ldx, C, esz) && vec_ok(y, ldy, C, esz) && (!residual || vec_ok(residual, ldr, C, esz));
-    DISPATCH_T(dtype, return (launch_norm<float, 0>(p, N, vec, (hipStream_t)stream)),
-               return (launch_norm<bf16_t, 0>(p, N, vec, (hipStream_t)stream)));
+    int rc = MSSEG_OK;
+    const bool known = for_dtype(dtype, [&](auto t) { rc = launch_norm<typename decltype(t)::type, 0>(p, N, vec, (hipStream_t)stream); });
+    return known ? rc : bad_dtype(dtype);
 }
 
 int msseg_conv3d_k1_head_fwd(const void* x, long long ldx, const float* w, const float* bias, void* y, long long ldy,
@@ -1438,11 +1421,11 @@ int msseg_conv3d_k1_head_fwd(const void* x, long long ldx, const float* w, const
     if (dtype != MSSEG_F32 && dtype != MSSEG_BF16) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k1_head: bad dtype");
     if (Cout < 1 || Cout > 4 || Cin < 1 || Cin > 64 || !vec_ok(x, ldx, Cin, esz) || ldy < Cout)
         MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k1_head: needs 1 <= Cout <= 4, Cin <= 64 in 16-byte chunks (got %d -> %d)", Cin, Cout);
-    const int g = grid_for(NV, 1);
+    const int g = stream_grid(NV);
 #define HEAD(T_, C_) hipLaunchKernelGGL((conv1x1_head_kernel<T_, C_>), dim3(g), dim3(256), 0, (hipStream_t)stream, \
                                         (const T_*)x, ldx, w, bias, (T_*)y, ldy, NV, Cin)
 #define HEAD_C(T_) do { if (Cout == 1) HEAD(T_, 1); else if (Cout == 2) HEAD(T_, 2); else if (Cout == 3) HEAD(T_, 3); else HEAD(T_, 4); } while (0)
-    DISPATCH_T(dtype, HEAD_C(float), HEAD_C(bf16_t));
+    for_dtype(dtype, [&](auto t) { HEAD_C(typename decltype(t)::type); });
 #undef HEAD_C
 #undef HEAD
     MSSEG_CHECK_LAUNCH("conv3d_k1_head");
@@ -1474,11 +1457,15 @@ static int head_bwd_impl(const void* dy, long long lddy, const float* w, void* d
     blocks = ceil_div_ll(S, p.rows_per_block);
     dim3 grid((unsigned)blocks, N);
     if (dw) {
-        DISPATCH_T(dtype, hipLaunchKernelGGL((head_dgrad_inbwd_kernel<float, true>), grid, dim3(RED_THREADS), 0, (hipStream_t)stream, p),
-                   hipLaunchKernelGGL((head_dgrad_inbwd_kernel<bf16_t, true>), grid, dim3(RED_THREADS), 0, (hipStream_t)stream, p));
+        for_dtype(dtype, [&](auto t) {
+            hipLaunchKernelGGL((head_dgrad_inbwd_kernel<typename decltype(t)::type, true>), grid, dim3(RED_THREADS), 0,
+                               (hipStream_t)stream, p);
+        });
     } else {
-        DISPATCH_T(dtype, hipLaunchKernelGGL((head_dgrad_inbwd_kernel<float, false>), grid, dim3(RED_THREADS), 0, (hipStream_t)stream, p),
-                   hipLaunchKernelGGL((head_dgrad_inbwd_kernel<bf16_t, false>), grid, dim3(RED_THREADS), 0, (hipStream_t)stream, p));
+        for_dtype(dtype, [&](auto t) {
+            hipLaunchKernelGGL((head_dgrad_inbwd_kernel<typename decltype(t)::type, false>), grid, dim3(RED_THREADS), 0,
+                               (hipStream_t)stream, p);
+        });
     }
     MSSEG_CHECK_LAUNCH("conv3d_k1_head_dgrad_inbwd");
     HeadFinArgs a{p.ws, N, (int)blocks, C, nper, Cout, red, dbeta, dgamma, dw, accumulate, dw_accumulate};
@@ -1522,7 +1509,7 @@ int msseg_conv3d_k1_head_norm_fwd(const void* x, long long ldx, const float* sta
 #define HEADN(T_, C_) hipLaunchKernelGGL((conv1x1_head_norm_kernel<T_, C_>), grid, dim3(256), 0, (hipStream_t)stream, \
                                          (const T_*)x, ldx, stats, gamma, beta, slope, eps, w, bias, (T_*)y, ldy, S, Cin)
 #define HEADN_C(T_) do { if (Cout == 1) HEADN(T_, 1); else if (Cout == 2) HEADN(T_, 2); else if (Cout == 3) HEADN(T_, 3); else HEADN(T_, 4); } while (0)
-    DISPATCH_T(dtype, HEADN_C(float), HEADN_C(bf16_t));
+    for_dtype(dtype, [&](auto t) { HEADN_C(typename decltype(t)::type); });
 #undef HEADN_C
 #undef HEADN
     MSSEG_CHECK_LAUNCH("conv3d_k1_head_norm");
@@ -1542,9 +1529,10 @@ int msseg_instnorm_act_pool_fwd(const void* x, long long ldx, const float* stats
     const long long total = (long long)N * (D / 2) * (H / 2) * (W / 2) * (C / (16 / esz));
     if (total >= 0x7fffffffLL) MSSEG_FAIL(MSSEG_EINVAL, "instnorm_act_pool_fwd: too many elements");
     NormPoolParams p{x, ldx, stats, gamma, beta, y, ldy, pooled, ldp, N, D, H, W, C, eps, slope};
-    const int g = grid_for(total, 1);
-    DISPATCH_T(dtype, hipLaunchKernelGGL(instnorm_pool_fwd_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, p),
-               hipLaunchKernelGGL(instnorm_pool_fwd_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, p));
+    for_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL(instnorm_pool_fwd_kernel<typename decltype(t)::type>, dim3(stream_grid(total)), dim3(256), 0,
+                           (hipStream_t)stream, p);
+    });
     MSSEG_CHECK_LAUNCH("instnorm_act_pool_fwd");
     return MSSEG_OK;
 }
@@ -1573,9 +1561,10 @@ int msseg_instnorm_act_poolbwd_reduce(const void* x, long long ldx, const float*
     p.cells_per_block = ceil_div_ll(cells, blocks);
     blocks = ceil_div_ll(cells, p.cells_per_block);
     dim3 grid((unsigned)blocks, N);
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(instnorm_poolbwd_reduce_kernel<float>, grid, dim3(RED_THREADS), 0, (hipStream_t)stream, p),
-               hipLaunchKernelGGL(instnorm_poolbwd_reduce_kernel<bf16_t>, grid, dim3(RED_THREADS), 0, (hipStream_t)stream, p));
+    for_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL(instnorm_poolbwd_reduce_kernel<typename decltype(t)::type>, grid, dim3(RED_THREADS), 0,
+                           (hipStream_t)stream, p);
+    });
     MSSEG_CHECK_LAUNCH("instnorm_act_poolbwd_reduce");
     FinalizeArgs a{p.ws, N, (int)blocks, C, 2, 2, red, dbeta, dgamma, accumulate};
     hipLaunchKernelGGL(channels_finalize_kernel, channels_finalize_grid(a), dim3(256), 0, (hipStream_t)stream, a);
@@ -1598,8 +1587,9 @@ int msseg_instnorm_act_bwd_reduce(const void* x, long long ldx, const float* sta
     p.S = S; p.C = C; p.eps = eps; p.slope = slope;
     const int esz = dtype == MSSEG_F32 ? 4 : 2;
     const bool vec = vec_ok(x, ldx, C, esz) && vec_ok(y, ldy, C, esz) && vec_ok(dy, lddy, C, esz);
-    DISPATCH_T(dtype, return (launch_norm<float, 1>(p, N, vec, (hipStream_t)stream)),
-               return (launch_norm<bf16_t, 1>(p, N, vec, (hipStream_t)stream)));
+    int rc = MSSEG_OK;
+    const bool known = for_dtype(dtype, [&](auto t) { rc = launch_norm<typename decltype(t)::type, 1>(p, N, vec, (hipStream_t)stream); });
+    return known ? rc : bad_dtype(dtype);
 }
 
 int msseg_instnorm_act_bwd_apply(const void* x, long long ldx, const float* stats, const float* gamma,
@@ -1614,8 +1604,9 @@ int msseg_instnorm_act_bwd_apply(const void* x, long long ldx, const float* stat
     const int esz = dtype == MSSEG_F32 ? 4 : 2;
     const bool vec = vec_ok(x, ldx, C, esz) && vec_ok(y, ldy, C, esz) && vec_ok(dy, lddy, C, esz) &&
                      vec_ok(dx, lddx, C, esz) && (!dres || vec_ok(dres, lddres, C, esz));
-    DISPATCH_T(dtype, return (launch_norm<float, 2>(p, N, vec, (hipStream_t)stream)),
-               return (launch_norm<bf16_t, 2>(p, N, vec, (hipStream_t)stream)));
+    int rc = MSSEG_OK;
+    const bool known = for_dtype(dtype, [&](auto t) { rc = launch_norm<typename decltype(t)::type, 2>(p, N, vec, (hipStream_t)stream); });
+    return known ? rc : bad_dtype(dtype);
 }
 
 int msseg_maxpool2_fwd(const void* x, long long ldx, void* y, long long ldy, int N, int D, int H, int W, int C,
@@ -1625,11 +1616,14 @@ int msseg_maxpool2_fwd(const void* x, long long ldx, void* y, long long ldy, int
     const bool vec = vec_ok(x, ldx, C, esz) && vec_ok(y, ldy, C, esz);
     const long long total = (long long)N * (D / 2) * (H / 2) * (W / 2) * ceil_div(C, vec ? 16 / esz : 1);
     if (total >= 0x7fffffffLL) MSSEG_FAIL(MSSEG_EINVAL, "maxpool2_fwd: too many elements");
-    const int g = grid_for(total, 1);
+    const int g = stream_grid(total);
 #define MP_F(T_, V_) hipLaunchKernelGGL((maxpool2_kernel<T_, V_, false>), dim3(g), dim3(256), 0, (hipStream_t)stream, \
                                         (const T_*)x, ldx, (const T_*)nullptr, 0LL, (T_*)y, ldy, N, D, H, W, C, 0)
-    DISPATCH_T(dtype, if (vec) MP_F(float, true); else MP_F(float, false),
-               if (vec) MP_F(bf16_t, true); else MP_F(bf16_t, false));
+    const bool known = for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (vec) MP_F(T, true); else MP_F(T, false);
+    });
+    if (!known) return bad_dtype(dtype);
 #undef MP_F
     MSSEG_CHECK_LAUNCH("maxpool2_fwd");
     return MSSEG_OK;
@@ -1642,11 +1636,14 @@ int msseg_maxpool2_bwd(const void* x, long long ldx, const void* dy, long long l
     const bool vec = vec_ok(x, ldx, C, esz) && vec_ok(dy, lddy, C, esz) && vec_ok(dx, lddx, C, esz);
     const long long total = (long long)N * (D / 2) * (H / 2) * (W / 2) * ceil_div(C, vec ? 16 / esz : 1);
     if (total >= 0x7fffffffLL) MSSEG_FAIL(MSSEG_EINVAL, "maxpool2_bwd: too many elements");
-    const int g = grid_for(total, 1);
+    const int g = stream_grid(total);
 #define MP_B(T_, V_) hipLaunchKernelGGL((maxpool2_kernel<T_, V_, true>), dim3(g), dim3(256), 0, (hipStream_t)stream, \
                                         (const T_*)x, ldx, (const T_*)dy, lddy, (T_*)dx, lddx, N, D, H, W, C, accumulate)
-    DISPATCH_T(dtype, if (vec) MP_B(float, true); else MP_B(float, false),
-               if (vec) MP_B(bf16_t, true); else MP_B(bf16_t, false));
+    const bool known = for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (vec) MP_B(T, true); else MP_B(T, false);
+    });
+    if (!known) return bad_dtype(dtype);
 #undef MP_B
     MSSEG_CHECK_LAUNCH("maxpool2_bwd");
     return MSSEG_OK;
@@ -1655,7 +1652,7 @@ int msseg_maxpool2_bwd(const void* x, long long ldx, const void* dy, long long l
 int msseg_ncdhw_to_ndhwc(const void* src, int src_dtype, void* dst, long long ldd, int dst_dtype, int N, int C,
                          long long S, msseg_stream_t stream) {
     if (!src || !dst || N < 1 || C < 1 || S < 1 || ldd < C) MSSEG_FAIL(MSSEG_EINVAL, "ncdhw_to_ndhwc: bad args");
-    const int g = grid_for((long long)N * C * S);
+    const int g = stream_grid((long long)N * C * S, 1024);
     hipStream_t st = (hipStream_t)stream;
     if (src_dtype == MSSEG_F32 && dst_dtype == MSSEG_F32)
         hipLaunchKernelGGL((ncdhw_to_ndhwc_kernel<float, float>), dim3(g), dim3(256), 0, st, (const float*)src, (float*)dst, ldd, N, C, S);
@@ -1673,7 +1670,7 @@ int msseg_ncdhw_to_ndhwc(const void* src, int src_dtype, void* dst, long long ld
 int msseg_ndhwc_to_ncdhw(const void* src, long long lds, int src_dtype, void* dst, int dst_dtype, int N, int C,
                          long long S, msseg_stream_t stream) {
     if (!src || !dst || N < 1 || C < 1 || S < 1 || lds < C) MSSEG_FAIL(MSSEG_EINVAL, "ndhwc_to_ncdhw: bad args");
-    const int g = grid_for((long long)N * C * S);
+    const int g = stream_grid((long long)N * C * S, 1024);
     hipStream_t st = (hipStream_t)stream;
     if (src_dtype == MSSEG_F32 && dst_dtype == MSSEG_F32)
         hipLaunchKernelGGL((ndhwc_to_ncdhw_kernel<float, float>), dim3(g), dim3(256), 0, st, (const float*)src, lds, (float*)dst, N, C, S);
@@ -1691,12 +1688,13 @@ int msseg_ndhwc_to_ncdhw(const void* src, long long lds, int src_dtype, void* ds
 int msseg_zero_stuff2(const void* dy, long long lddy, void* out, long long ldo, int N, int OD, int OH, int OW, int ID,
                       int IH, int IW, int C, int dtype, msseg_stream_t stream) {
     if (!dy || !out || N < 1 || C < 1) MSSEG_FAIL(MSSEG_EINVAL, "zero_stuff2: bad args");
-    const int g = grid_for((long long)N * ID * IH * IW * C);
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(zero_stuff2_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)dy,
-                                  lddy, (float*)out, ldo, N, OD, OH, OW, ID, IH, IW, C),
-               hipLaunchKernelGGL(zero_stuff2_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream,
-                                  (const bf16_t*)dy, lddy, (bf16_t*)out, ldo, N, OD, OH, OW, ID, IH, IW, C));
+    const int g = stream_grid((long long)N * ID * IH * IW * C, 1024);
+    const bool known = for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(zero_stuff2_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const T*)dy, lddy, (T*)out, ldo, N, OD,
+                           OH, OW, ID, IH, IW, C);
+    });
+    if (!known) return bad_dtype(dtype);
     MSSEG_CHECK_LAUNCH("zero_stuff2");
     return MSSEG_OK;
 }
@@ -1705,26 +1703,28 @@ int msseg_add(const void* a, long long lda, const void* b, long long ldb, void* 
               int dtype, msseg_stream_t stream) {
     if (!a || !b || !y || rows < 1 || C < 1) MSSEG_FAIL(MSSEG_EINVAL, "add: bad args");
     {
-        const int esz = dtype == MSSEG_F32 ? 4 : 2, epc = 16 / esz;
+        const int epc = epc_of(dtype);
         if (C % epc == 0 && lda % epc == 0 && ldb % epc == 0 && ldy % epc == 0 &&
             ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)y)) & 15) == 0) {
             const int cpr = C / epc;
-            const int gv = grid_for(rows * cpr, 2);
-            DISPATCH_T(dtype,
-                       hipLaunchKernelGGL(add_vec_kernel<float>, dim3(gv), dim3(256), 0, (hipStream_t)stream, (const float*)a,
-                                          lda, (const float*)b, ldb, (float*)y, ldy, rows, cpr),
-                       hipLaunchKernelGGL(add_vec_kernel<bf16_t>, dim3(gv), dim3(256), 0, (hipStream_t)stream,
-                                          (const bf16_t*)a, lda, (const bf16_t*)b, ldb, (bf16_t*)y, ldy, rows, cpr));
+            const int gv = stream_grid(rows * cpr, 512);
+            const bool known = for_dtype(dtype, [&](auto t) {
+            using T = typename decltype(t)::type;
+                hipLaunchKernelGGL(add_vec_kernel<T>, dim3(gv), dim3(256), 0, (hipStream_t)stream, (const T*)a, lda, (const T*)b, ldb,
+                                   (T*)y, ldy, rows, cpr);
+            });
+            if (!known) return bad_dtype(dtype);
             MSSEG_CHECK_LAUNCH("add");
             return MSSEG_OK;
         }
     }
-    const int g = grid_for(rows * C);
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(add_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)a, lda,
-                                  (const float*)b, ldb, (float*)y, ldy, rows, C),
-               hipLaunchKernelGGL(add_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, lda,
-                                  (const bf16_t*)b, ldb, (bf16_t*)y, ldy, rows, C));
+    const int g = stream_grid(rows * C, 1024);
+    const bool known = for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(add_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const T*)a, lda, (const T*)b, ldb, (T*)y, ldy,
+                           rows, C);
+    });
+    if (!known) return bad_dtype(dtype);
     MSSEG_CHECK_LAUNCH("add");
     return MSSEG_OK;
 }
@@ -1732,17 +1732,16 @@ int msseg_add(const void* a, long long lda, const void* b, long long ldb, void* 
 int msseg_axpy_rows(const void* a, const void* b, const float* scale, void* y, int N, long long elems_per_sample, int dtype,
                     msseg_stream_t stream) {
     if (!b || !y || N < 1 || elems_per_sample < 1) MSSEG_FAIL(MSSEG_EINVAL, "axpy_rows: bad args");
-    const int esz = dtype == MSSEG_F32 ? 4 : 2, epc = 16 / esz;
+    const int epc = epc_of(dtype);
     if (dtype != MSSEG_F32 && dtype != MSSEG_BF16) MSSEG_FAIL(MSSEG_EINVAL, "axpy_rows: bad dtype");
     if ((elems_per_sample % epc) || ((uintptr_t)b & 15) || ((uintptr_t)y & 15) || (a && ((uintptr_t)a & 15)))
         MSSEG_FAIL(MSSEG_EINVAL, "axpy_rows: dense 16-byte aligned tensors with elems_per_sample %% %d == 0 expected", epc);
     const long long cps = elems_per_sample / epc, total = cps * N;
-    const int g = grid_for(total, 2);
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(axpy_rows_vec_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)a,
-                                  (const float*)b, scale, (float*)y, cps, total),
-               hipLaunchKernelGGL(axpy_rows_vec_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a,
-                                  (const bf16_t*)b, scale, (bf16_t*)y, cps, total));
+    for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(axpy_rows_vec_kernel<T>, dim3(stream_grid(total, 512)), dim3(256), 0, (hipStream_t)stream, (const T*)a,
+                           (const T*)b, scale, (T*)y, cps, total);
+    });
     MSSEG_CHECK_LAUNCH("axpy_rows");
     return MSSEG_OK;
 }
@@ -1754,7 +1753,7 @@ int msseg_adamw_step(float* param, const float* grad, float* exp_avg, float* exp
         MSSEG_FAIL(MSSEG_EINVAL, "adamw_step: bad args");
     const float bc1 = 1.f - powf(beta1, (float)step);
     const float bc2 = sqrtf(1.f - powf(beta2, (float)step));
-    hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+    hipLaunchKernelGGL(adamw_kernel, dim3(stream_grid(n, 1024)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
                        exp_avg_sq, decay_mask, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, dev_hyper);
     MSSEG_CHECK_LAUNCH("adamw_step");
     return MSSEG_OK;
@@ -1762,7 +1761,7 @@ int msseg_adamw_step(float* param, const float* grad, float* exp_avg, float* exp
 
 int msseg_sumsq(const float* x, long long n, float* out, float* partials, int n_partials, msseg_stream_t stream) {
     if (!x || !out || !partials || n < 1 || n_partials < 1) MSSEG_FAIL(MSSEG_EINVAL, "sumsq: bad args");
-    int nblk = grid_for(n, 16);
+    int nblk = stream_grid(n, 4096);
     if (nblk > n_partials) nblk = n_partials;
     hipLaunchKernelGGL(sumsq_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, x, n, partials);
     MSSEG_CHECK_LAUNCH("sumsq");

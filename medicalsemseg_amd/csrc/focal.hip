@@ -14,31 +14,6 @@
 
 namespace {
 
-template <typename T> struct Chunk;
-template <> struct Chunk<bf16_t> {
-    static constexpr int E = 8;
-    static MSSEG_DEVFN void load(const bf16_t* p, float* f) {
-        const bf16x8_t v = *(const bf16x8_t*)p;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] = (float)v[e];
-    }
-    static MSSEG_DEVFN void store(bf16_t* p, const float* f) {
-        bf16x8_t v;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = (bf16_t)f[e];
-        *(bf16x8_t*)p = v;
-    }
-};
-template <> struct Chunk<float> {
-    static constexpr int E = 4;
-    static MSSEG_DEVFN void load(const float* p, float* f) {
-        const f32x4_t v = *(const f32x4_t*)p;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) f[e] = v[e];
-    }
-    static MSSEG_DEVFN void store(float* p, const float* f) { *(f32x4_t*)p = f32x4_t{f[0], f[1], f[2], f[3]}; }
-};
-
 MSSEG_DEVFN float gelu_cdf(float v) { return 0.5f * (1.f + erff(v * 0.70710678118654752f)); }
 
 // ---- spatial sum -------------------------------------------------------------------------------------------------
@@ -204,19 +179,12 @@ __global__ __launch_bounds__(256) void focal_mul_kernel(const T* __restrict__ a,
 
 int chk(int dtype, int C, const char* what) {
     if (dtype != MSSEG_F32 && dtype != MSSEG_BF16) MSSEG_FAIL(MSSEG_EINVAL, "%s: bad dtype", what);
-    const int epc = dtype == MSSEG_F32 ? 4 : 8;
+    const int epc = epc_of(dtype);
     if (C < 1 || C % epc) MSSEG_FAIL(MSSEG_EINVAL, "%s: channels must be a multiple of %d", what, epc);
     return MSSEG_OK;
 }
 
 bool al16(const void* p) { return p && !((uintptr_t)p & 15); }
-
-unsigned grid_for(long long threads) {
-    long long b = (threads + 255) / 256;
-    const long long cap = (long long)msseg_num_cus() * 16;
-    if (b > cap) b = cap;
-    return (unsigned)(b < 1 ? 1 : b);
-}
 
 }  // namespace
 
@@ -226,7 +194,7 @@ int msseg_focal_spatial_sum(const void* x, long long ldx, const void* g, long lo
                             float scale, int mode, int N, long long S, int C, void* scratch, size_t scratch_bytes, int dtype,
                             msseg_stream_t stream) {
     if (int rc = chk(dtype, C, "focal_spatial_sum")) return rc;
-    const int epc = dtype == MSSEG_F32 ? 4 : 8;
+    const int epc = epc_of(dtype);
     if (!al16(x) || !out0 || N < 1 || S < 1 || ldx < C || ldx % epc || C / epc > 256 || (mode != 0 && mode != 1) ||
         (mode == 1 && !m_in) || (g && ldg < 1))
         MSSEG_FAIL(MSSEG_EINVAL, "focal_spatial_sum: bad args");
@@ -242,12 +210,11 @@ int msseg_focal_spatial_sum(const void* x, long long ldx, const void* g, long lo
     const long long vpb = ceil_div_ll(S, blocks);
     blocks = ceil_div_ll(S, vpb);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == MSSEG_F32)
-        hipLaunchKernelGGL(focal_sum_kernel<float>, dim3((unsigned)blocks, N), dim3(256), 0, s, (const float*)x, ldx, (const float*)g,
-                           ldg, S, C, vpb, part);
-    else
-        hipLaunchKernelGGL(focal_sum_kernel<bf16_t>, dim3((unsigned)blocks, N), dim3(256), 0, s, (const bf16_t*)x, ldx,
-                           (const bf16_t*)g, ldg, S, C, vpb, part);
+    for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(focal_sum_kernel<T>, dim3((unsigned)blocks, N), dim3(256), 0, s, (const T*)x, ldx, (const T*)g, ldg, S, C,
+                           vpb, part);
+    });
     MSSEG_CHECK_LAUNCH("focal_spatial_sum");
     hipLaunchKernelGGL(focal_sum_finalize_kernel, dim3(ceil_div(N * C, 256)), dim3(256), 0, s, part, (int)blocks, N * C, C, m_in, out0,
                        out1, scale, mode);
@@ -260,14 +227,12 @@ int msseg_focal_aggregate_fwd(const void* c1, const void* c2, const void* gates,
     if (int rc = chk(dtype, C, "focal_aggregate_fwd")) return rc;
     if (!al16(c1) || !al16(c2) || !al16(out) || !gates || !gm || N < 1 || S < 1 || ldg < 3)
         MSSEG_FAIL(MSSEG_EINVAL, "focal_aggregate_fwd: bad args");
-    const long long total = (long long)N * S * (C / (dtype == MSSEG_F32 ? 4 : 8));
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == MSSEG_F32)
-        hipLaunchKernelGGL(focal_agg_fwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, (const float*)c1, (const float*)c2,
-                           (const float*)gates, ldg, gm, (float*)out, S, C, total);
-    else
-        hipLaunchKernelGGL(focal_agg_fwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)c1, (const bf16_t*)c2,
-                           (const bf16_t*)gates, ldg, gm, (bf16_t*)out, S, C, total);
+    const long long total = (long long)N * S * (C / epc_of(dtype));
+    for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(focal_agg_fwd_kernel<T>, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, (const T*)c1,
+                           (const T*)c2, (const T*)gates, ldg, gm, (T*)out, S, C, total);
+    });
     MSSEG_CHECK_LAUNCH("focal_aggregate_fwd");
     return MSSEG_OK;
 }
@@ -279,19 +244,16 @@ int msseg_focal_aggregate_bwd(const void* da, const void* c1, const void* c2, co
     if (!al16(da) || !al16(c1) || !al16(c2) || !al16(dc1) || !al16(dc2) || !gates || !gm || !dmv || !dgates || N < 1 || S < 1 ||
         ldg < 3 || gate_width < 3 || lddg < gate_width)
         MSSEG_FAIL(MSSEG_EINVAL, "focal_aggregate_bwd: bad args");
-    const int nch = C / (dtype == MSSEG_F32 ? 4 : 8);
+    const int nch = C / epc_of(dtype);
     int G = 1;
     while (G < nch && G < 64) G <<= 1;
     const long long NV = (long long)N * S;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == MSSEG_F32)
-        hipLaunchKernelGGL(focal_agg_bwd_kernel<float>, dim3(grid_for(NV * G)), dim3(256), 0, s, (const float*)da, (const float*)c1,
-                           (const float*)c2, (const float*)gates, ldg, gm, dmv, (float*)dc1, (float*)dc2, (float*)dgates, lddg,
-                           gate_width, S, C, NV, G);
-    else
-        hipLaunchKernelGGL(focal_agg_bwd_kernel<bf16_t>, dim3(grid_for(NV * G)), dim3(256), 0, s, (const bf16_t*)da, (const bf16_t*)c1,
-                           (const bf16_t*)c2, (const bf16_t*)gates, ldg, gm, dmv, (bf16_t*)dc1, (bf16_t*)dc2, (bf16_t*)dgates, lddg,
-                           gate_width, S, C, NV, G);
+    for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(focal_agg_bwd_kernel<T>, dim3(stream_grid(NV * G)), dim3(256), 0, (hipStream_t)stream, (const T*)da,
+                           (const T*)c1, (const T*)c2, (const T*)gates, ldg, gm, dmv, (T*)dc1, (T*)dc2, (T*)dgates, lddg, gate_width,
+                           S, C, NV, G);
+    });
     MSSEG_CHECK_LAUNCH("focal_aggregate_bwd");
     return MSSEG_OK;
 }
@@ -299,16 +261,14 @@ int msseg_focal_aggregate_bwd(const void* da, const void* c1, const void* c2, co
 int msseg_focal_mul_fwd(const void* q, long long ldq, const void* h, void* y, long long rows, int C, int dtype,
                         msseg_stream_t stream) {
     if (int rc = chk(dtype, C, "focal_mul_fwd")) return rc;
-    const int epc = dtype == MSSEG_F32 ? 4 : 8;
+    const int epc = epc_of(dtype);
     if (!al16(q) || !al16(h) || !al16(y) || rows < 1 || ldq < C || ldq % epc) MSSEG_FAIL(MSSEG_EINVAL, "focal_mul_fwd: bad args");
     const long long total = rows * (C / epc);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == MSSEG_F32)
-        hipLaunchKernelGGL((focal_mul_kernel<float, false>), dim3(grid_for(total)), dim3(256), 0, s, (const float*)nullptr,
-                           (const float*)q, ldq, (const float*)h, (float*)y, (long long)C, (float*)nullptr, C, total);
-    else
-        hipLaunchKernelGGL((focal_mul_kernel<bf16_t, false>), dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)nullptr,
-                           (const bf16_t*)q, ldq, (const bf16_t*)h, (bf16_t*)y, (long long)C, (bf16_t*)nullptr, C, total);
+    for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((focal_mul_kernel<T, false>), dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream,
+                           (const T*)nullptr, (const T*)q, ldq, (const T*)h, (T*)y, (long long)C, (T*)nullptr, C, total);
+    });
     MSSEG_CHECK_LAUNCH("focal_mul_fwd");
     return MSSEG_OK;
 }
@@ -316,17 +276,15 @@ int msseg_focal_mul_fwd(const void* q, long long ldq, const void* h, void* y, lo
 int msseg_focal_mul_bwd(const void* dy, const void* q, long long ldq, const void* h, void* dq, long long lddq, void* dh,
                         long long rows, int C, int dtype, msseg_stream_t stream) {
     if (int rc = chk(dtype, C, "focal_mul_bwd")) return rc;
-    const int epc = dtype == MSSEG_F32 ? 4 : 8;
+    const int epc = epc_of(dtype);
     if (!al16(dy) || !al16(q) || !al16(h) || !al16(dq) || !al16(dh) || rows < 1 || ldq < C || ldq % epc || lddq < C || lddq % epc)
         MSSEG_FAIL(MSSEG_EINVAL, "focal_mul_bwd: bad args");
     const long long total = rows * (C / epc);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == MSSEG_F32)
-        hipLaunchKernelGGL((focal_mul_kernel<float, true>), dim3(grid_for(total)), dim3(256), 0, s, (const float*)dy, (const float*)q,
-                           ldq, (const float*)h, (float*)dq, lddq, (float*)dh, C, total);
-    else
-        hipLaunchKernelGGL((focal_mul_kernel<bf16_t, true>), dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)dy,
-                           (const bf16_t*)q, ldq, (const bf16_t*)h, (bf16_t*)dq, lddq, (bf16_t*)dh, C, total);
+    for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((focal_mul_kernel<T, true>), dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, (const T*)dy,
+                           (const T*)q, ldq, (const T*)h, (T*)dq, lddq, (T*)dh, C, total);
+    });
     MSSEG_CHECK_LAUNCH("focal_mul_bwd");
     return MSSEG_OK;
 }

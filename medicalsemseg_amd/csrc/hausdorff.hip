@@ -135,13 +135,6 @@ __global__ __launch_bounds__(256) void hd_pass_z_hist_kernel(const int* __restri
     }
 }
 
-inline unsigned grid_for(long long n, int per = 256) {
-    long long g = ceil_div_ll(n, per);
-    const long long cap = (long long)msseg_num_cus() * 16;
-    if (g > cap) g = cap;
-    return (unsigned)(g < 1 ? 1 : g);
-}
-
 }  // namespace
 
 extern "C" {
@@ -152,7 +145,7 @@ int msseg_hd_edges(const uint8_t* pred, const uint8_t* gt, int D, int H, int W, 
         MSSEG_FAIL(MSSEG_EINVAL, "hd_edges: bad args (%dx%dx%d, %d classes)", D, H, W, C);
     if (D > 16000 || H > 16000 || W > 16000) MSSEG_FAIL(MSSEG_EINVAL, "hd_edges: axis longer than 16000 voxels");
     hipLaunchKernelGGL(hd_stats_init_kernel, dim3(ceil_div(C * 8, 256)), dim3(256), 0, (hipStream_t)stream, stats, C);
-    hipLaunchKernelGGL(hd_edges_kernel, dim3(grid_for((long long)D * H * W)), dim3(256), 0, (hipStream_t)stream, pred, gt, D,
+    hipLaunchKernelGGL(hd_edges_kernel, dim3(stream_grid((long long)D * H * W)), dim3(256), 0, (hipStream_t)stream, pred, gt, D,
                        H, W, C, edges_pred, edges_gt, stats);
     MSSEG_CHECK_LAUNCH("hd_edges");
     return MSSEG_OK;
@@ -185,9 +178,9 @@ int msseg_hd_directed_hist(const uint8_t* edges_src, const uint8_t* edges_tgt, i
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(hist, 0, (size_t)nbins * sizeof(int), s) != hipSuccess)
         MSSEG_FAIL(MSSEG_ELAUNCH, "hd_directed_hist: memset failed");
-    hipLaunchKernelGGL(hd_pass_x_kernel, dim3(grid_for((long long)bz * by, 64)), dim3(256), 0, s, edges_src, cls, H, W, b, gx);
-    hipLaunchKernelGGL(hd_pass_y_kernel, dim3(grid_for((long long)v)), dim3(256), 0, s, gx, b, h);
-    hipLaunchKernelGGL(hd_pass_z_hist_kernel, dim3(grid_for((long long)v)), dim3(256), 0, s, h, edges_tgt, cls, H, W, b, hist,
+    hipLaunchKernelGGL(hd_pass_x_kernel, dim3(stream_grid((long long)bz * by, 64)), dim3(256), 0, s, edges_src, cls, H, W, b, gx);
+    hipLaunchKernelGGL(hd_pass_y_kernel, dim3(stream_grid((long long)v)), dim3(256), 0, s, gx, b, h);
+    hipLaunchKernelGGL(hd_pass_z_hist_kernel, dim3(stream_grid((long long)v)), dim3(256), 0, s, h, edges_tgt, cls, H, W, b, hist,
                        nbins);
     MSSEG_CHECK_LAUNCH("hd_directed_hist");
     return MSSEG_OK;

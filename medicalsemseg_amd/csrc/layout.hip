@@ -110,17 +110,10 @@ __global__ __launch_bounds__(256) void merge_gather_bwd_kernel(const T* __restri
     }
 }
 
-int grid_for(long long total) {
-    long long b = (total + 255) / 256;
-    const long long cap = (long long)msseg_num_cus() * 16;
-    if (b > cap) b = cap;
-    return (int)(b < 1 ? 1 : b);
-}
-
 int check(const void* a, long long lda, const void* b, long long ldb, int C, int dtype, long long total, const char* who) {
     if (!a || !b) MSSEG_FAIL(MSSEG_EINVAL, "%s: null pointer", who);
     if (dtype != MSSEG_F32 && dtype != MSSEG_BF16) MSSEG_FAIL(MSSEG_EINVAL, "%s: bad dtype", who);
-    const int epc = dtype == MSSEG_F32 ? 4 : 8;
+    const int epc = epc_of(dtype);
     if (C < epc || C % epc || lda % epc || ldb % epc || (((uintptr_t)a | (uintptr_t)b) & 15))
         MSSEG_FAIL(MSSEG_EINVAL, "%s: channels and strides must be multiples of %d, pointers 16-byte aligned", who, epc);
     if (total < 1 || total > 0x7fffffffLL) MSSEG_FAIL(MSSEG_EINVAL, "%s: bad element count", who);
@@ -133,15 +126,15 @@ extern "C" {
 
 int msseg_box_copy(const void* src, long long lds, int SD, int SH, int SW, void* dst, long long ldd, int DD, int DH, int DW, int N,
                    int C, int dtype, msseg_stream_t stream) {
-    const long long total = (long long)N * DD * DH * DW * (C / (dtype == MSSEG_F32 ? 4 : 8));
+    const long long total = (long long)N * DD * DH * DW * (C / epc_of(dtype));
     if (int rc = check(src, lds, dst, ldd, C, dtype, total, "box_copy")) return rc;
     if (SD < 1 || SH < 1 || SW < 1 || lds < C || ldd < C || (long long)N * SD * SH * SW > 0x7fffffffLL)
         MSSEG_FAIL(MSSEG_EINVAL, "box_copy: bad shape");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MSSEG_F32)
-        hipLaunchKernelGGL(box_copy_kernel<float>, dim3(grid_for(total)), dim3(256), 0, st, (const float*)src, lds, SD, SH, SW, (float*)dst, ldd, DD, DH, DW, N, C);
-    else
-        hipLaunchKernelGGL(box_copy_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, st, (const bf16_t*)src, lds, SD, SH, SW, (bf16_t*)dst, ldd, DD, DH, DW, N, C);
+    for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(box_copy_kernel<T>, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, (const T*)src, lds, SD, SH, SW,
+                           (T*)dst, ldd, DD, DH, DW, N, C);
+    });
     MSSEG_CHECK_LAUNCH("box_copy");
     return MSSEG_OK;
 }
@@ -149,28 +142,28 @@ int msseg_box_copy(const void* src, long long lds, int SD, int SH, int SW, void*
 int msseg_merge_gather_fwd(const void* x, long long ldx, int D, int H, int W, void* out, long long ldo, int N, int C, unsigned subs,
                            int dtype, msseg_stream_t stream) {
     const long long OV = (long long)N * ((D + 1) / 2) * ((H + 1) / 2) * ((W + 1) / 2);
-    const long long total = OV * 8 * (C / (dtype == MSSEG_F32 ? 4 : 8));
+    const long long total = OV * 8 * (C / epc_of(dtype));
     if (int rc = check(x, ldx, out, ldo, C, dtype, total, "merge_gather_fwd")) return rc;
     if (D < 1 || H < 1 || W < 1 || ldx < C || ldo < 8LL * C) MSSEG_FAIL(MSSEG_EINVAL, "merge_gather_fwd: bad shape");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MSSEG_F32)
-        hipLaunchKernelGGL(merge_gather_fwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, st, (const float*)x, ldx, D, H, W, (float*)out, ldo, N, C, subs);
-    else
-        hipLaunchKernelGGL(merge_gather_fwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, st, (const bf16_t*)x, ldx, D, H, W, (bf16_t*)out, ldo, N, C, subs);
+    for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(merge_gather_fwd_kernel<T>, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx, D, H, W,
+                           (T*)out, ldo, N, C, subs);
+    });
     MSSEG_CHECK_LAUNCH("merge_gather_fwd");
     return MSSEG_OK;
 }
 
 int msseg_merge_gather_bwd(const void* dy, long long lddy, void* dx, long long lddx, int N, int D, int H, int W, int C, unsigned subs,
                            int dtype, msseg_stream_t stream) {
-    const long long total = (long long)N * D * H * W * (C / (dtype == MSSEG_F32 ? 4 : 8));
+    const long long total = (long long)N * D * H * W * (C / epc_of(dtype));
     if (int rc = check(dy, lddy, dx, lddx, C, dtype, total, "merge_gather_bwd")) return rc;
     if (D < 1 || H < 1 || W < 1 || lddx < C || lddy < 8LL * C) MSSEG_FAIL(MSSEG_EINVAL, "merge_gather_bwd: bad shape");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MSSEG_F32)
-        hipLaunchKernelGGL(merge_gather_bwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, st, (const float*)dy, lddy, (float*)dx, lddx, N, D, H, W, C, subs);
-    else
-        hipLaunchKernelGGL(merge_gather_bwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, st, (const bf16_t*)dy, lddy, (bf16_t*)dx, lddx, N, D, H, W, C, subs);
+    for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(merge_gather_bwd_kernel<T>, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, (const T*)dy, lddy, (T*)dx,
+                           lddx, N, D, H, W, C, subs);
+    });
     MSSEG_CHECK_LAUNCH("merge_gather_bwd");
     return MSSEG_OK;
 }

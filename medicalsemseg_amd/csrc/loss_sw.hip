@@ -504,14 +504,6 @@ int launch_blend_batch(const void* win, long long ldw, const float* imp, float* 
     return MSSEG_OK;
 }
 
-inline int grid_for(long long total, int per_thread = 4) {
-    long long b = ceil_div_ll(total, 256LL * per_thread);
-    const long long cap = (long long)msseg_num_cus() * 16;
-    if (b > cap) b = cap;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 // calls f(std::integral_constant<int, KIND>) for a run-time loss kind (checked by the entry points)
 template <typename F> void for_kind(int kind, F&& f) {
     if (kind == KIND_TVERSKY) f(std::integral_constant<int, KIND_TVERSKY>{});
@@ -571,16 +563,14 @@ int launch_bwd(const void* logits, long long ld, const void* labels, int label_d
 
 #define DISPATCH_TC(dtype, C, FN, ...)                                                        \
     do {                                                                                      \
-        if ((dtype) == MSSEG_F32) {                                                           \
-            if ((C) <= 4) return FN<float, 4>(__VA_ARGS__);                                   \
-            if ((C) <= 8) return FN<float, 8>(__VA_ARGS__);                                   \
-            return FN<float, 16>(__VA_ARGS__);                                                \
-        } else if ((dtype) == MSSEG_BF16) {                                                   \
-            if ((C) <= 4) return FN<bf16_t, 4>(__VA_ARGS__);                                  \
-            if ((C) <= 8) return FN<bf16_t, 8>(__VA_ARGS__);                                  \
-            return FN<bf16_t, 16>(__VA_ARGS__);                                               \
-        }                                                                                     \
-        MSSEG_FAIL(MSSEG_EINVAL, "bad dtype %d", (int)(dtype));                               \
+        int rc__ = MSSEG_OK;                                                                  \
+        const bool known__ = for_dtype(dtype, [&](auto t__) {                                 \
+            using T_ = typename decltype(t__)::type;                                          \
+            rc__ = (C) <= 4 ? FN<T_, 4>(__VA_ARGS__)                                          \
+                 : (C) <= 8 ? FN<T_, 8>(__VA_ARGS__) : FN<T_, 16>(__VA_ARGS__);               \
+        });                                                                                   \
+        if (!known__) MSSEG_FAIL(MSSEG_EINVAL, "bad dtype %d", (int)(dtype));                 \
+        return rc__;                                                                          \
     } while (0)
 
 extern "C" {
@@ -657,7 +647,7 @@ int msseg_dice_ce_bwd(const void* logits, long long ld, int dtype, const void* l
 
 int msseg_sw_normalize(float* out, const float* cnt, int C, long long V, msseg_stream_t stream) {
     if (!out || !cnt || C < 1 || V < 1) MSSEG_FAIL(MSSEG_EINVAL, "sw_normalize: bad args");
-    hipLaunchKernelGGL(sw_normalize_kernel, dim3(grid_for((long long)C * V)), dim3(256), 0, (hipStream_t)stream, out, cnt,
+    hipLaunchKernelGGL(sw_normalize_kernel, dim3(stream_grid((long long)C * V, 1024)), dim3(256), 0, (hipStream_t)stream, out, cnt,
                        C, V);
     MSSEG_CHECK_LAUNCH("sw_normalize");
     return MSSEG_OK;
@@ -684,13 +674,12 @@ int msseg_sw_gather_batch(const float* vol, long long vol_bstride, void* win, lo
     const long long R = (long long)RD * RH * RW;
     long long gx = ceil_div_ll(R, 256LL * 2);
     if (gx > 65535) gx = 65535;
-    if (dtype == MSSEG_F32)
-        hipLaunchKernelGGL(sw_gather_batch_kernel<float>, dim3((unsigned)gx, nwin), dim3(256), 0, (hipStream_t)stream, vol,
-                           vol_bstride, (float*)win, ldw, table, nwin, C, VD, VH, VW, RD, RH, RW, cval);
-    else if (dtype == MSSEG_BF16)
-        hipLaunchKernelGGL(sw_gather_batch_kernel<bf16_t>, dim3((unsigned)gx, nwin), dim3(256), 0, (hipStream_t)stream,
-                           vol, vol_bstride, (bf16_t*)win, ldw, table, nwin, C, VD, VH, VW, RD, RH, RW, cval);
-    else MSSEG_FAIL(MSSEG_EINVAL, "sw_gather_batch: bad dtype");
+    const bool known = for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(sw_gather_batch_kernel<T>, dim3((unsigned)gx, nwin), dim3(256), 0, (hipStream_t)stream, vol,
+                           vol_bstride, (T*)win, ldw, table, nwin, C, VD, VH, VW, RD, RH, RW, cval);
+    });
+    if (!known) MSSEG_FAIL(MSSEG_EINVAL, "sw_gather_batch: bad dtype");
     MSSEG_CHECK_LAUNCH("sw_gather_batch");
     return MSSEG_OK;
 }

@@ -82,20 +82,13 @@ __global__ __launch_bounds__(256) void majority_vote_u8_kernel(const unsigned ch
     }
 }
 
-inline int pp_grid(long long total, int per_thread) {
-    long long b = ceil_div_ll(total, 256LL * per_thread);
-    const long long cap = (long long)msseg_num_cus() * 16;
-    if (b > cap) b = cap;
-    return (int)(b < 1 ? 1 : b);
-}
-
 }  // namespace
 
 extern "C" {
 
 int msseg_argmax_u8(const float* logits, int C, long long V, uint8_t* out, msseg_stream_t stream) {
     if (!logits || !out || C < 1 || C > 255 || V < 1) MSSEG_FAIL(MSSEG_EINVAL, "argmax_u8: bad args");
-    hipLaunchKernelGGL(argmax_u8_kernel, dim3(pp_grid(V, 4)), dim3(256), 0, (hipStream_t)stream, logits, C, V, out);
+    hipLaunchKernelGGL(argmax_u8_kernel, dim3(stream_grid(V, 1024)), dim3(256), 0, (hipStream_t)stream, logits, C, V, out);
     MSSEG_CHECK_LAUNCH("argmax_u8");
     return MSSEG_OK;
 }
@@ -107,7 +100,7 @@ int msseg_resample_nearest_u8(const uint8_t* src, int SD, int SH, int SW, uint8_
     const double rd = TD > 1 ? (double)(SD - 1) / (double)(TD - 1) : 0.0;
     const double rh = TH > 1 ? (double)(SH - 1) / (double)(TH - 1) : 0.0;
     const double rw = TW > 1 ? (double)(SW - 1) / (double)(TW - 1) : 0.0;
-    hipLaunchKernelGGL(resample_nearest_u8_kernel, dim3(pp_grid((long long)TD * TH * TW, 1)), dim3(256), 0,
+    hipLaunchKernelGGL(resample_nearest_u8_kernel, dim3(stream_grid((long long)TD * TH * TW)), dim3(256), 0,
                        (hipStream_t)stream, src, SD, SH, SW, dst, TD, TH, TW, rd, rh, rw);
     MSSEG_CHECK_LAUNCH("resample_nearest_u8");
     return MSSEG_OK;
@@ -116,7 +109,7 @@ int msseg_resample_nearest_u8(const uint8_t* src, int SD, int SH, int SW, uint8_
 int msseg_majority_vote_u8(const uint8_t* labels, int F, long long V, int C, uint8_t* out, msseg_stream_t stream) {
     if (!labels || !out || F < 1 || F > 254 || V < 1 || C < 1 || C > 16)
         MSSEG_FAIL(MSSEG_EINVAL, "majority_vote_u8: 1 <= folds <= 254, 1 <= classes <= 16");
-    const int g = pp_grid(V, 1);
+    const int g = stream_grid(V);
     if (C <= 4) hipLaunchKernelGGL(majority_vote_u8_kernel<4>, dim3(g), dim3(256), 0, (hipStream_t)stream, labels, F, V, C, out);
     else if (C <= 8) hipLaunchKernelGGL(majority_vote_u8_kernel<8>, dim3(g), dim3(256), 0, (hipStream_t)stream, labels, F, V, C, out);
     else hipLaunchKernelGGL(majority_vote_u8_kernel<16>, dim3(g), dim3(256), 0, (hipStream_t)stream, labels, F, V, C, out);
@@ -178,13 +171,12 @@ extern "C" int msseg_aug_crop_batch(const float* img, const uint8_t* lab, int C,
     long long gx = ceil_div_ll((long long)R * R * R, 256LL * 4);
     if (gx > 4096) gx = 4096;
     dim3 grid((unsigned)gx, npatch);
-    if (out_dtype == MSSEG_F32)
-        hipLaunchKernelGGL(aug_crop_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, img, lab, C, VD, VH, VW,
-                           (const AugRow*)table, (float*)out_img, out_lab, R);
-    else if (out_dtype == MSSEG_BF16)
-        hipLaunchKernelGGL(aug_crop_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, img, lab, C, VD, VH, VW,
-                           (const AugRow*)table, (bf16_t*)out_img, out_lab, R);
-    else MSSEG_FAIL(MSSEG_EINVAL, "aug_crop_batch: bad dtype");
+    const bool known = for_dtype(out_dtype, [&](auto t) {
+        using TO = typename decltype(t)::type;
+        hipLaunchKernelGGL(aug_crop_kernel<TO>, grid, dim3(256), 0, (hipStream_t)stream, img, lab, C, VD, VH, VW,
+                           (const AugRow*)table, (TO*)out_img, out_lab, R);
+    });
+    if (!known) MSSEG_FAIL(MSSEG_EINVAL, "aug_crop_batch: bad dtype");
     MSSEG_CHECK_LAUNCH("aug_crop_batch");
     return MSSEG_OK;
 }

@@ -14,31 +14,6 @@
 
 namespace {
 
-template <typename T> struct Ch;
-template <> struct Ch<bf16_t> {
-    static constexpr int E = 8;
-    static MSSEG_DEVFN void load(const bf16_t* p, float* f) {
-        const bf16x8_t v = *(const bf16x8_t*)p;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] = (float)v[e];
-    }
-    static MSSEG_DEVFN void store(bf16_t* p, const float* f) {
-        bf16x8_t v;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = (bf16_t)f[e];
-        *(bf16x8_t*)p = v;
-    }
-};
-template <> struct Ch<float> {
-    static constexpr int E = 4;
-    static MSSEG_DEVFN void load(const float* p, float* f) {
-        const f32x4_t v = *(const f32x4_t*)p;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) f[e] = v[e];
-    }
-    static MSSEG_DEVFN void store(float* p, const float* f) { *(f32x4_t*)p = f32x4_t{f[0], f[1], f[2], f[3]}; }
-};
-
 // ---- trilinear ------------------------------------------------------------------------------------------------
 struct Lin { int i0, i1; float l0, l1; };
 // torch's area_pixel_compute_source_index (align_corners = False): src = max(scale * (o + 0.5) - 0.5, 0)
@@ -62,7 +37,7 @@ struct InterpParams {
 
 template <typename T>
 __global__ __launch_bounds__(256) void interp_fwd_kernel(const InterpParams p) {
-    constexpr int E = Ch<T>::E;
+    constexpr int E = Chunk<T>::E;
     const int nch = p.C / E;
     const long long total = (long long)p.N * p.OD * p.OH * p.OW * nch;
     const T* __restrict__ xg = (const T*)p.x;
@@ -86,11 +61,11 @@ __global__ __launch_bounds__(256) void interp_fwd_kernel(const InterpParams p) {
                     const int d = a ? Ld.i1 : Ld.i0, h = b ? Lh.i1 : Lh.i0, w = c ? Lw.i1 : Lw.i0;
                     const float wt = (a ? Ld.l1 : Ld.l0) * (b ? Lh.l1 : Lh.l0) * (c ? Lw.l1 : Lw.l0);
                     float xv[E];
-                    Ch<T>::load(xg + ((((long long)n * p.ID + d) * p.IH + h) * p.IW + w) * p.ldx + ch * E, xv);
+                    Chunk<T>::load(xg + ((((long long)n * p.ID + d) * p.IH + h) * p.IW + w) * p.ldx + ch * E, xv);
 #pragma unroll
                     for (int e = 0; e < E; ++e) acc[e] = fmaf(wt, xv[e], acc[e]);
                 }
-        Ch<T>::store(yg + v * p.ldy + ch * E, acc);
+        Chunk<T>::store(yg + v * p.ldy + ch * E, acc);
     }
 }
 
@@ -119,21 +94,6 @@ struct Interp1Params {
     float scale;                       // Li / Lo
 };
 
-template <typename T> MSSEG_DEVFN void ld4(const T* p, float* f);
-template <> MSSEG_DEVFN void ld4<float>(const float* p, float* f) {
-    const f32x4_t v = *(const f32x4_t*)p;
-    f[0] = v[0]; f[1] = v[1]; f[2] = v[2]; f[3] = v[3];
-}
-template <> MSSEG_DEVFN void ld4<bf16_t>(const bf16_t* p, float* f) {
-    const bf16x4_t v = *(const bf16x4_t*)p;
-    f[0] = (float)v[0]; f[1] = (float)v[1]; f[2] = (float)v[2]; f[3] = (float)v[3];
-}
-template <typename T> MSSEG_DEVFN void st4(T* p, const float* f);
-template <> MSSEG_DEVFN void st4<float>(float* p, const float* f) { *(f32x4_t*)p = f32x4_t{f[0], f[1], f[2], f[3]}; }
-template <> MSSEG_DEVFN void st4<bf16_t>(bf16_t* p, const float* f) {
-    *(bf16x4_t*)p = bf16x4_t{(bf16_t)f[0], (bf16_t)f[1], (bf16_t)f[2], (bf16_t)f[3]};
-}
-
 template <typename TI, typename TO>
 __global__ __launch_bounds__(256) void interp1_bwd_kernel(const Interp1Params p) {
     const int nch = p.C / 4;
@@ -153,11 +113,11 @@ __global__ __launch_bounds__(256) void interp1_bwd_kernel(const Interp1Params p)
             const float wt = wt_of(o, i, p.scale, p.Li);
             if (wt == 0.f) continue;
             float g[4];
-            ld4<TI>(gy + ((ou * p.Lo + o) * p.inner + in) * p.lddy + ch * 4, g);
+            load4<TI>(gy + ((ou * p.Lo + o) * p.inner + in) * p.lddy + ch * 4, g);
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc[e] = fmaf(wt, g[e], acc[e]);
         }
-        st4<TO>(gx + ((ou * p.Li + i) * p.inner + in) * p.lddx + ch * 4, acc);
+        store4<TO>(gx + ((ou * p.Li + i) * p.inner + in) * p.lddx + ch * 4, acc);
     }
 }
 
@@ -334,32 +294,25 @@ __global__ void kv_attn_bwd_kv_finalize_kernel(const KvParams p, const float* pa
 
 template <typename T>
 __global__ __launch_bounds__(256) void scale_channels_kernel(const T* x, const float* s, T* y, long long S, int C, long long total) {
-    constexpr int E = Ch<T>::E;
+    constexpr int E = Chunk<T>::E;
     const int nch = C / E;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int ch = (int)(i % nch);
         const long long v = i / nch;
         const long long n = v / S;
         float f[E];
-        Ch<T>::load(x + v * C + ch * E, f);
+        Chunk<T>::load(x + v * C + ch * E, f);
 #pragma unroll
         for (int e = 0; e < E; ++e) f[e] *= s[n * C + ch * E + e];
-        Ch<T>::store(y + v * C + ch * E, f);
+        Chunk<T>::store(y + v * C + ch * E, f);
     }
-}
-
-int grid_of(long long total) {
-    long long gx = (total + 255) / 256;
-    const long long cap = (long long)msseg_num_cus() * 16;
-    if (gx > cap) gx = cap;
-    return (int)(gx < 1 ? 1 : gx);
 }
 
 int interp_check(const void* lo, long long ldlo, const void* hi, long long ldhi, int N, int ID, int IH, int IW, int OD, int OH,
                  int OW, int C, int dtype, const char* what) {
     if (!lo || !hi) MSSEG_FAIL(MSSEG_EINVAL, "%s: null pointer", what);
     if (dtype != MSSEG_F32 && dtype != MSSEG_BF16) MSSEG_FAIL(MSSEG_EINVAL, "%s: bad dtype", what);
-    const int epc = dtype == MSSEG_F32 ? 4 : 8;
+    const int epc = epc_of(dtype);
     if (N < 1 || ID < 1 || IH < 1 || IW < 1 || OD < 1 || OH < 1 || OW < 1 || C < 1 || C % epc)
         MSSEG_FAIL(MSSEG_EINVAL, "%s: bad shape (channels must be a multiple of %d)", what, epc);
     if (ldlo < C || ldhi < C || ldlo % epc || ldhi % epc || ((uintptr_t)lo & 15) || ((uintptr_t)hi & 15))
@@ -371,7 +324,7 @@ template <typename TI, typename TO>
 int interp1_launch(const void* dy, long long lddy, void* dx, long long lddx, long long outer, int Lo, int Li, long long inner,
                           int C, hipStream_t stream) {
     Interp1Params p{dy, lddy, dx, lddx, outer, inner, Lo, Li, C, (float)Li / Lo};
-    hipLaunchKernelGGL((interp1_bwd_kernel<TI, TO>), dim3(grid_of(outer * Li * inner * (C / 4))), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((interp1_bwd_kernel<TI, TO>), dim3(stream_grid(outer * Li * inner * (C / 4))), dim3(256), 0, stream, p);
     MSSEG_CHECK_LAUNCH("interp_trilinear_bwd");
     return MSSEG_OK;
 }
@@ -385,9 +338,11 @@ int msseg_interp_trilinear_fwd(const void* x, long long ldx, void* y, long long 
     int rc = interp_check(x, ldx, y, ldy, N, ID, IH, IW, OD, OH, OW, C, dtype, "interp_trilinear_fwd");
     if (rc) return rc;
     InterpParams p{x, ldx, y, ldy, N, ID, IH, IW, OD, OH, OW, C, (float)ID / OD, (float)IH / OH, (float)IW / OW};
-    const long long total = (long long)N * OD * OH * OW * (C / (dtype == MSSEG_F32 ? 4 : 8));
-    if (dtype == MSSEG_F32) hipLaunchKernelGGL(interp_fwd_kernel<float>, dim3(grid_of(total)), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(interp_fwd_kernel<bf16_t>, dim3(grid_of(total)), dim3(256), 0, (hipStream_t)stream, p);
+    const long long total = (long long)N * OD * OH * OW * (C / epc_of(dtype));
+    for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(interp_fwd_kernel<T>, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, p);
+    });
     MSSEG_CHECK_LAUNCH("interp_trilinear_fwd");
     return MSSEG_OK;
 }
@@ -407,15 +362,12 @@ int msseg_interp_trilinear_bwd(const void* dy, long long lddy, void* dx, long lo
     float* t1 = (float*)workspace;                               // [N, OD, OH, IW, C]
     float* t2 = t1 + (size_t)N * OD * OH * IW * C;               // [N, OD, IH, IW, C]
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MSSEG_F32) {
-        rc = interp1_launch<float, float>(dy, lddy, t1, C, (long long)N * OD * OH, OW, IW, 1, C, st);
+    for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        rc = interp1_launch<T, float>(dy, lddy, t1, C, (long long)N * OD * OH, OW, IW, 1, C, st);
         if (!rc) rc = interp1_launch<float, float>(t1, C, t2, C, (long long)N * OD, OH, IH, IW, C, st);
-        if (!rc) rc = interp1_launch<float, float>(t2, C, dx, lddx, N, OD, ID, (long long)IH * IW, C, st);
-    } else {
-        rc = interp1_launch<bf16_t, float>(dy, lddy, t1, C, (long long)N * OD * OH, OW, IW, 1, C, st);
-        if (!rc) rc = interp1_launch<float, float>(t1, C, t2, C, (long long)N * OD, OH, IH, IW, C, st);
-        if (!rc) rc = interp1_launch<float, bf16_t>(t2, C, dx, lddx, N, OD, ID, (long long)IH * IW, C, st);
-    }
+        if (!rc) rc = interp1_launch<float, T>(t2, C, dx, lddx, N, OD, ID, (long long)IH * IW, C, st);
+    });
     return rc;
 }
 
@@ -428,24 +380,16 @@ static int kv_check(const KvParams& p, int dtype, const char* what) {
 }
 
 #define KV_DISPATCH(BWDFLAG)                                                                                            \
-    do {                                                                                                                \
+    for_dtype(dtype, [&](auto t) {                                                                                      \
+        using T = typename decltype(t)::type;                                                                           \
         const dim3 g((p.N + 255) / 256, p.heads, p.B);                                                                  \
-        if (dtype == MSSEG_F32) {                                                                                       \
-            switch (p.hd) {                                                                                             \
-                case 16: hipLaunchKernelGGL((kv_attn_kernel<float, 16, BWDFLAG>), g, dim3(256), 0, (hipStream_t)stream, p); break; \
-                case 32: hipLaunchKernelGGL((kv_attn_kernel<float, 32, BWDFLAG>), g, dim3(256), 0, (hipStream_t)stream, p); break; \
-                case 48: hipLaunchKernelGGL((kv_attn_kernel<float, 48, BWDFLAG>), g, dim3(256), 0, (hipStream_t)stream, p); break; \
-                default: hipLaunchKernelGGL((kv_attn_kernel<float, 64, BWDFLAG>), g, dim3(256), 0, (hipStream_t)stream, p); break; \
-            }                                                                                                           \
-        } else {                                                                                                        \
-            switch (p.hd) {                                                                                             \
-                case 16: hipLaunchKernelGGL((kv_attn_kernel<bf16_t, 16, BWDFLAG>), g, dim3(256), 0, (hipStream_t)stream, p); break; \
-                case 32: hipLaunchKernelGGL((kv_attn_kernel<bf16_t, 32, BWDFLAG>), g, dim3(256), 0, (hipStream_t)stream, p); break; \
-                case 48: hipLaunchKernelGGL((kv_attn_kernel<bf16_t, 48, BWDFLAG>), g, dim3(256), 0, (hipStream_t)stream, p); break; \
-                default: hipLaunchKernelGGL((kv_attn_kernel<bf16_t, 64, BWDFLAG>), g, dim3(256), 0, (hipStream_t)stream, p); break; \
-            }                                                                                                           \
+        switch (p.hd) {                                                                                                 \
+            case 16: hipLaunchKernelGGL((kv_attn_kernel<T, 16, BWDFLAG>), g, dim3(256), 0, (hipStream_t)stream, p); break; \
+            case 32: hipLaunchKernelGGL((kv_attn_kernel<T, 32, BWDFLAG>), g, dim3(256), 0, (hipStream_t)stream, p); break; \
+            case 48: hipLaunchKernelGGL((kv_attn_kernel<T, 48, BWDFLAG>), g, dim3(256), 0, (hipStream_t)stream, p); break; \
+            default: hipLaunchKernelGGL((kv_attn_kernel<T, 64, BWDFLAG>), g, dim3(256), 0, (hipStream_t)stream, p); break; \
         }                                                                                                               \
-    } while (0)
+    })
 
 int msseg_kv_attention_fwd(const void* q, const void* kv, void* o, float* lse, int B, int N, int M, int heads, int head_dim,
                            float scale, int dtype, msseg_stream_t stream) {
@@ -483,13 +427,11 @@ int msseg_kv_attention_bwd(const void* q, const void* kv, const void* o, const f
     const int nqc = (N + QCH - 1) / QCH;
     float* part = p.dS + (size_t)B * heads * N * M;
     const dim3 g2(nqc, heads, B), g3(M, heads, B);
-    if (dtype == MSSEG_F32) {
-        hipLaunchKernelGGL(kv_attn_bwd_kv_kernel<float>, g2, dim3(256), 0, (hipStream_t)stream, p, part);
-        hipLaunchKernelGGL(kv_attn_bwd_kv_finalize_kernel<float>, g3, dim3(64), 0, (hipStream_t)stream, p, (const float*)part, nqc);
-    } else {
-        hipLaunchKernelGGL(kv_attn_bwd_kv_kernel<bf16_t>, g2, dim3(256), 0, (hipStream_t)stream, p, part);
-        hipLaunchKernelGGL(kv_attn_bwd_kv_finalize_kernel<bf16_t>, g3, dim3(64), 0, (hipStream_t)stream, p, (const float*)part, nqc);
-    }
+    for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(kv_attn_bwd_kv_kernel<T>, g2, dim3(256), 0, (hipStream_t)stream, p, part);
+        hipLaunchKernelGGL(kv_attn_bwd_kv_finalize_kernel<T>, g3, dim3(64), 0, (hipStream_t)stream, p, (const float*)part, nqc);
+    });
     MSSEG_CHECK_LAUNCH("kv_attention_bwd (keys)");
     return MSSEG_OK;
 }
@@ -497,14 +439,15 @@ int msseg_kv_attention_bwd(const void* q, const void* kv, const void* o, const f
 int msseg_scale_channels(const void* x, const float* scale, void* y, int N, long long S, int C, int dtype, msseg_stream_t stream) {
     if (!x || !scale || !y) MSSEG_FAIL(MSSEG_EINVAL, "scale_channels: null pointer");
     if (dtype != MSSEG_F32 && dtype != MSSEG_BF16) MSSEG_FAIL(MSSEG_EINVAL, "scale_channels: bad dtype");
-    const int epc = dtype == MSSEG_F32 ? 4 : 8;
+    const int epc = epc_of(dtype);
     if (N < 1 || S < 1 || C < 1 || C % epc || ((uintptr_t)x & 15) || ((uintptr_t)y & 15))
         MSSEG_FAIL(MSSEG_EINVAL, "scale_channels: dense 16-byte aligned tensors with C %% %d == 0", epc);
     const long long total = (long long)N * S * (C / epc);
-    if (dtype == MSSEG_F32)
-        hipLaunchKernelGGL(scale_channels_kernel<float>, dim3(grid_of(total)), dim3(256), 0, (hipStream_t)stream, (const float*)x, scale, (float*)y, S, C, total);
-    else
-        hipLaunchKernelGGL(scale_channels_kernel<bf16_t>, dim3(grid_of(total)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, scale, (bf16_t*)y, S, C, total);
+    for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(scale_channels_kernel<T>, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, (const T*)x, scale,
+                           (T*)y, S, C, total);
+    });
     MSSEG_CHECK_LAUNCH("scale_channels");
     return MSSEG_OK;
 }
