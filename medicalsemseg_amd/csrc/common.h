@@ -125,6 +125,11 @@ template <> struct Chunk<bf16_t> {
 #pragma unroll
         for (int e = 0; e < 8; ++e) f[e] = (float)v[e];
     }
+    static MSSEG_DEVFN void unpack(const u32x4_t& raw, float* f) {   // a chunk fetched with ldg16 and kept as loaded
+        const bf16x8_t v = __builtin_bit_cast(bf16x8_t, raw);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = (float)v[e];
+    }
     static MSSEG_DEVFN void store(bf16_t* p, const float* f) {
         bf16x8_t v;
 #pragma unroll
@@ -136,6 +141,11 @@ template <> struct Chunk<float> {
     static constexpr int E = 4;
     static MSSEG_DEVFN void load(const float* p, float* f) {
         const f32x4_t v = *(const f32x4_t*)p;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) f[e] = v[e];
+    }
+    static MSSEG_DEVFN void unpack(const u32x4_t& raw, float* f) {
+        const f32x4_t v = __builtin_bit_cast(f32x4_t, raw);
 #pragma unroll
         for (int e = 0; e < 4; ++e) f[e] = v[e];
     }

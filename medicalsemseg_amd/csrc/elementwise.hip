@@ -6,6 +6,8 @@
 #include <stdarg.h>
 #include <string.h>
 
+#include <initializer_list>
+
 // ---------------------------------------------------------------------------------------------------------
 // error plumbing / device info
 // ---------------------------------------------------------------------------------------------------------
@@ -371,6 +373,7 @@ MSSEG_DEVFN void mean_rstd(const float* stats, int n, int C, int c, long long S,
 }
 
 // MODE 0: forward   MODE 1: backward reduce   MODE 2: backward apply
+// (launched for MODE 1, and for the scalar fallback of MODE 0 / 2; on 16-byte chunks those two run instnorm_stream_kernel)
 template <typename T, bool VEC, int MODE>
 __global__ __launch_bounds__(MODE == 1 ? RED_THREADS : 256) void instnorm_kernel(const NormParams p) {
     constexpr int W = VEC ? DT<T>::EPC : 1;
@@ -517,6 +520,142 @@ __global__ __launch_bounds__(MODE == 1 ? RED_THREADS : 256) void instnorm_kernel
                 }
             }
         }
+    }
+}
+
+// MODE 0 and MODE 2 on 16-byte chunks are pure streaming passes, elementwise in the rows.  A thread takes NORM_U rows per
+// trip: it issues every load of the batch (x, dy, and the residual or the stored activation where the launch has one)
+// into registers, then computes, then stores -- no branch stands between the loads, so NORM_U x (1..3) 16-byte loads per
+// thread are outstanding at the first wait.  Which optional streams exist is a template parameter (OPT: residual in
+// MODE 0, stored activation in MODE 2; DRES: MODE 2 also writes dz).  A tail of fewer than NORM_U rows stays batched: the
+// missing rows re-load the trip's first row and their stores are masked.  Rows are addressed by 32-bit byte offsets from
+// the block's first row (launch_norm_stream keeps a block's extent below 2^30 bytes in every operand).
+// Measured at the UNet's 96^3 x 32 and 48^3 x 64 levels (bf16, batch 2; profiles/README.md): 2 and 4 rows per trip stream
+// alike and 8 is slower (backward apply 94-105 against 76 us per call); filling every resident slot (4 to 8 blocks per
+// CU) is no faster at 96^3 than 2 blocks per CU and ~5 % slower at 48^3, so the grid stops at NORM_BLOCKS_PER_CU.
+constexpr int NORM_U = 4;
+constexpr int NORM_BLOCKS_PER_CU = 2;
+
+// one trip: rows rb + u * rows_par, u < NORM_U, of the block's nrows.  TAIL: some of them are past the end (the full trips
+// carry no test at all, so that nothing tempts the compiler to move a load behind one)
+template <typename T, int MODE, bool OPT, bool DRES, bool TAIL>
+MSSEG_DEVFN void norm_stream_batch(const char* __restrict__ xb, unsigned ldx, const char* __restrict__ ob, unsigned ldo,
+                                   const char* __restrict__ dyb, unsigned lddy, char* __restrict__ outb, unsigned ldout,
+                                   char* __restrict__ drb, unsigned lddr, int rb, int rows_par, int nrows, unsigned cg,
+                                   const float* mean, const float* rstd, const float* sc, const float* sh,
+                                   const float* k0, const float* k1, float slope) {
+    constexpr int W = DT<T>::EPC, U = NORM_U;
+    constexpr unsigned ES = sizeof(T);
+    unsigned row[U];
+    bool ok[U];
+    u32x4_t xr[U], dr[U], orw[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int r = rb + u * rows_par;
+        ok[u] = !TAIL || r < nrows;
+        row[u] = (unsigned)(ok[u] ? r : rb);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) xr[u] = ldg16(xb + (row[u] * ldx + cg) * ES);
+    if constexpr (MODE == 2) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) dr[u] = ldg16(dyb + (row[u] * lddy + cg) * ES);
+    }
+    if constexpr (OPT) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) orw[u] = ldg16(ob + (row[u] * ldo + cg) * ES);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        float xv[W], o[W], dv[W], yv[W];
+        Chunk<T>::unpack(xr[u], xv);
+        if constexpr (MODE == 0) {
+            float rv[W];
+            if constexpr (OPT) {
+                Chunk<T>::unpack(orw[u], rv);
+            } else {
+#pragma unroll
+                for (int e = 0; e < W; ++e) rv[e] = 0.f;
+            }
+#pragma unroll
+            for (int e = 0; e < W; ++e) {
+                const float z = xv[e] * sc[e] + sh[e] + rv[e];
+                o[e] = z > 0.f ? z : z * slope;
+            }
+        } else {
+            Chunk<T>::unpack(dr[u], dv);
+            if constexpr (OPT) {
+                Chunk<T>::unpack(orw[u], yv);
+            } else {   // sign of the pre-activation, recomputed exactly as the forward formed it
+#pragma unroll
+                for (int e = 0; e < W; ++e) yv[e] = xv[e] * sc[e] + sh[e];
+            }
+#pragma unroll
+            for (int e = 0; e < W; ++e) {
+                const float dz = yv[e] > 0.f ? dv[e] : dv[e] * slope;
+                const float xh = (xv[e] - mean[e]) * rstd[e];
+                o[e] = sc[e] * (dz - k0[e] - xh * k1[e]);
+                dv[e] = dz;
+            }
+        }
+        if (ok[u]) {
+            Chunk<T>::store((T*)(outb + (row[u] * ldout + cg) * ES), o);
+            if constexpr (DRES) Chunk<T>::store((T*)(drb + (row[u] * lddr + cg) * ES), dv);
+        }
+    }
+}
+
+template <typename T, int MODE, bool OPT, bool DRES>
+__global__ __launch_bounds__(256, 4) void instnorm_stream_kernel(const NormParams p) {
+    static_assert(MODE == 0 || MODE == 2, "streaming modes only");
+    constexpr int W = DT<T>::EPC;
+    const int n = blockIdx.y;
+    const int g = threadIdx.x % p.groups, rl = threadIdx.x / p.groups;
+    const long long r0 = (long long)blockIdx.x * p.rows_per_block;
+    const long long r1 = r0 + p.rows_per_block > p.S ? p.S : r0 + p.rows_per_block;
+    const int nrows = (int)(r1 - r0);
+    if (rl >= p.rows_par || rl >= nrows) return;   // no barriers below
+    const long long v0 = ((long long)n * p.S + r0) * (long long)sizeof(T);   // the block's first row, in bytes per unit of ld
+    const char* xb = (const char*)p.x + v0 * p.ldx;
+    const char* ob = nullptr;
+    const char* dyb = nullptr;
+    char* outb;
+    char* drb = nullptr;
+    unsigned ldo = 0, lddy = 0, ldout, lddr = 0;
+    if constexpr (MODE == 0) {
+        if constexpr (OPT) { ob = (const char*)p.res + v0 * p.ldr; ldo = (unsigned)p.ldr; }
+        outb = (char*)p.y + v0 * p.ldy; ldout = (unsigned)p.ldy;
+    } else {
+        if constexpr (OPT) { ob = (const char*)p.y + v0 * p.ldy; ldo = (unsigned)p.ldy; }
+        dyb = (const char*)p.dy + v0 * p.lddy; lddy = (unsigned)p.lddy;
+        outb = (char*)p.dx + v0 * p.lddx; ldout = (unsigned)p.lddx;
+        if constexpr (DRES) { drb = (char*)p.dres + v0 * p.lddres; lddr = (unsigned)p.lddres; }
+    }
+    const float invS = 1.0f / (float)p.S;
+    for (int gg = g; gg * W < p.C; gg += p.groups) {
+        float mean[W], rstd[W], sc[W], sh[W], k0[W], k1[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            const int c = gg * W + e;
+            mean_rstd(p.stats, n, p.C, c, p.S, p.eps, mean[e], rstd[e]);
+            const float ga = p.gamma ? p.gamma[c] : 1.f;
+            sc[e] = rstd[e] * ga;
+            sh[e] = (p.beta ? p.beta[c] : 0.f) - mean[e] * sc[e];
+            if constexpr (MODE == 2) {
+                k0[e] = p.red[((long long)n * p.C + c) * 2 + 0] * invS;
+                k1[e] = p.red[((long long)n * p.C + c) * 2 + 1] * invS;
+            } else {
+                k0[e] = k1[e] = 0.f;
+            }
+        }
+        const unsigned cg = (unsigned)(gg * W);
+        int rb = rl;
+        for (; rb + (NORM_U - 1) * p.rows_par < nrows; rb += NORM_U * p.rows_par)
+            norm_stream_batch<T, MODE, OPT, DRES, false>(xb, (unsigned)p.ldx, ob, ldo, dyb, lddy, outb, ldout, drb, lddr, rb,
+                                                         p.rows_par, nrows, cg, mean, rstd, sc, sh, k0, k1, p.slope);
+        if (rb < nrows)
+            norm_stream_batch<T, MODE, OPT, DRES, true>(xb, (unsigned)p.ldx, ob, ldo, dyb, lddy, outb, ldout, drb, lddr, rb,
+                                                        p.rows_par, nrows, cg, mean, rstd, sc, sh, k0, k1, p.slope);
     }
 }
 
@@ -831,7 +970,49 @@ __global__ __launch_bounds__(RED_THREADS) void head_dgrad_inbwd_kernel(const Hea
     }
 }
 
+// MODE 0 / 2 on 16-byte chunks: one resident set of blocks, sized from what the instantiation really gets per CU
+template <typename T, int MODE, bool OPT, bool DRES> int launch_norm_stream(NormParams& p, int N, hipStream_t st) {
+    static std::atomic<int> resident{0};   // blocks per CU, asked once per instantiation
+    int per_cu = resident.load(std::memory_order_relaxed);
+    if (per_cu == 0) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)instnorm_stream_kernel<T, MODE, OPT, DRES>,
+                                                         256, 0) != hipSuccess || per_cu < 1)
+            MSSEG_FAIL(MSSEG_ELAUNCH, "instnorm: no occupancy for the streaming kernel");
+        resident.store(per_cu, std::memory_order_relaxed);
+    }
+    if (per_cu > NORM_BLOCKS_PER_CU) per_cu = NORM_BLOCKS_PER_CU;
+    const RowMap m = row_map(p.C, DT<T>::EPC, 256);
+    p.groups = m.groups; p.rows_par = m.rows_par;
+    // the output is elementwise, so the mapping of rows to blocks is free: every resident block gets one contiguous run of
+    // rows, a thread NORM_U rows of it per trip; a run stays below 2^30 bytes in the widest operand (32-bit row offsets)
+    long long ldmax = p.ldx > 1 ? p.ldx : 1;
+    for (long long ld : {p.ldr, p.ldy, p.lddy, p.lddx, p.lddres}) ldmax = ld > ldmax ? ld : ldmax;
+    long long blocks = ceil_div_ll(p.S, (long long)m.rows_par * NORM_U);
+    const long long cap = (long long)msseg_num_cus() * per_cu / (N > 0 ? N : 1);
+    if (blocks > cap) blocks = cap;
+    long long max_run = ((long long)1 << 30) / (ldmax * (long long)sizeof(T)) - 1;   // rows; the chunk offset adds < 1 row
+    if (max_run < 1) max_run = 1;
+    if (blocks < ceil_div_ll(p.S, max_run)) blocks = ceil_div_ll(p.S, max_run);
+    if (blocks < 1) blocks = 1;
+    p.rows_per_block = ceil_div_ll(p.S, blocks);
+    const long long trip = (long long)m.rows_par * NORM_U;   // whole trips, where the run limit allows: one tail per sample
+    if (ceil_div_ll(p.rows_per_block, trip) * trip <= max_run) p.rows_per_block = ceil_div_ll(p.rows_per_block, trip) * trip;
+    blocks = ceil_div_ll(p.S, p.rows_per_block);
+    hipLaunchKernelGGL((instnorm_stream_kernel<T, MODE, OPT, DRES>), dim3((unsigned)blocks, N), dim3(256), 0, st, p);
+    MSSEG_CHECK_LAUNCH("instnorm");
+    return MSSEG_OK;
+}
+
 template <typename T, int MODE> int launch_norm(NormParams& p, int N, bool vec, hipStream_t st) {
+    if constexpr (MODE != 1) {
+        if (vec) {
+            const bool opt = MODE == 0 ? p.res != nullptr : p.y != nullptr;
+            if constexpr (MODE == 2) {
+                if (p.dres) return opt ? launch_norm_stream<T, 2, true, true>(p, N, st) : launch_norm_stream<T, 2, false, true>(p, N, st);
+            }
+            return opt ? launch_norm_stream<T, MODE, true, false>(p, N, st) : launch_norm_stream<T, MODE, false, false>(p, N, st);
+        }
+    }
     constexpr int NTHR = MODE == 1 ? RED_THREADS : 256;
     const RowMap m = row_map(p.C, vec ? DT<T>::EPC : 1, NTHR);
     p.groups = m.groups; p.rows_par = m.rows_par;
@@ -839,7 +1020,7 @@ template <typename T, int MODE> int launch_norm(NormParams& p, int N, bool vec, 
     if (MODE == 1) {
         blocks = reduce_blocks(p.S, m.rows_par, N, p.C, 2);
     } else {
-        // pure streaming passes: 8 blocks of 4 waves per CU, each thread with 4+ independent 16-byte loads in flight
+        // scalar fallback of the streaming modes (channel count or alignment rules out 16-byte chunks)
         blocks = ceil_div_ll(p.S, (long long)m.rows_par * 4);
         const long long cap = (long long)msseg_num_cus() * 8 / (N > 0 ? N : 1);
         if (blocks > cap) blocks = cap;
@@ -848,8 +1029,12 @@ template <typename T, int MODE> int launch_norm(NormParams& p, int N, bool vec, 
     p.rows_per_block = ceil_div_ll(p.S, blocks);
     blocks = ceil_div_ll(p.S, p.rows_per_block);
     dim3 grid((unsigned)blocks, N);
-    if (vec) hipLaunchKernelGGL((instnorm_kernel<T, true, MODE>), grid, dim3(NTHR), 0, st, p);
-    else hipLaunchKernelGGL((instnorm_kernel<T, false, MODE>), grid, dim3(NTHR), 0, st, p);
+    if constexpr (MODE == 1) {
+        if (vec) hipLaunchKernelGGL((instnorm_kernel<T, true, 1>), grid, dim3(NTHR), 0, st, p);
+        else hipLaunchKernelGGL((instnorm_kernel<T, false, 1>), grid, dim3(NTHR), 0, st, p);
+    } else {
+        hipLaunchKernelGGL((instnorm_kernel<T, false, MODE>), grid, dim3(NTHR), 0, st, p);
+    }
     MSSEG_CHECK_LAUNCH("instnorm");
     if (MODE == 1) {
         // red[n][c] = (sum dz, sum dz*xhat); dbeta = sum_n red0, dgamma = sum_n red1
