@@ -1,0 +1,6 @@
+// igemm_fwd_kernel instantiations: conv k3 s1 p1 on 4x4x8 tiles (k3_plan cfg 1); cout blocks 16 / 32 / 48, both dtypes.
+#include "igemm_fwd_kernel.h"
+
+int msseg_igemm_k3_mid(IgemmParams& p, int dtype, hipStream_t stream) {
+    return launch_dtype<27, SRC_DIRECT, EPI_STORE, 4, 4, 8, 4>(p, dtype, stream);
+}

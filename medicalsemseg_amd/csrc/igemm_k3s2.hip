@@ -1,0 +1,6 @@
+// igemm_fwd_kernel instantiations: conv k3 s2 p1 on 2x4x8 output tiles; cout blocks 16 / 32 / 48, both dtypes.
+#include "igemm_fwd_kernel.h"
+
+int msseg_igemm_k3s2(IgemmParams& p, int dtype, hipStream_t stream) {
+    return launch_dtype<27, SRC_DIRECT, EPI_STORE, 2, 4, 8, 4, 2>(p, dtype, stream);
+}

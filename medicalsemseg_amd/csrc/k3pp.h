@@ -37,6 +37,22 @@ static inline long long msseg_k3_tiles(int N, int D, int H, int W) {
     return (long long)N * ceil_div(D, 4) * ceil_div(H, 4) * ceil_div(W, 16);
 }
 
+// ---- generic implicit-GEMM forward kernel (igemm_fwd_kernel.h): one launcher per family, defined in the igemm_*.hip file
+// that holds the family's instantiations; p.cout_block == 0 means msseg_cout_block(p.M).  Hidden: the split adds nothing
+// to the library's exported symbols ----
+struct IgemmParams;
+#pragma GCC visibility push(hidden)
+int msseg_igemm_k3_big_f32(IgemmParams& p, hipStream_t stream);            // 27 taps, 4x8x16 tiles; p.cout_block 16 or 32
+int msseg_igemm_k3_big_bf16(IgemmParams& p, hipStream_t stream);
+int msseg_igemm_k3_mid(IgemmParams& p, int dtype, hipStream_t stream);     // 27 taps, 4x4x8 tiles
+int msseg_igemm_k3_small(IgemmParams& p, int dtype, hipStream_t stream);   // 27 taps, 2x4x8 tiles
+int msseg_igemm_k3s2(IgemmParams& p, int dtype, hipStream_t stream);       // 27 taps, stride 2
+int msseg_igemm_flat(IgemmParams& p, int dtype, hipStream_t stream);       // 1 tap: direct source, plain store
+int msseg_igemm_gather(IgemmParams& p, int dtype, hipStream_t stream);     // 1 tap: im2col gather source
+int msseg_igemm_deconv(IgemmParams& p, int dtype, hipStream_t stream);     // 1 tap: ConvTranspose k2 s2 scatter epilogue; cout block 32
+int msseg_igemm_deconv_bwd(IgemmParams& p, int dtype, hipStream_t stream); // 1 tap: ConvTranspose k2 s2 children as source
+#pragma GCC visibility pop
+
 struct K3ppParams {
     const void* x;
     long long ldx;

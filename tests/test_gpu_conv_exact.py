@@ -6,7 +6,21 @@ and a kernel must EQUAL the float64 CPU reference whatever its tiling, split-K o
 voxel fails `torch.equal`, where the relative gates of tests/test_gpu_kernels.py (6e-3 of the output's maximum in bf16) let it
 pass (tests/test_conv_exact_method.py shows both on the CPU).  DESIGN.md, "Exact integer-input tests", lists kernel -> case.
 
-Every case prints the kernel or path that took it and asserts it wherever the library has a query for it."""
+Every case prints the kernel or path that took it and asserts it wherever the library has a query for it.
+
+Instantiations of the generic kernel (csrc/igemm_fwd_kernel.h) and the case that runs each, in fp32 and in bf16 unless noted;
+"cout block" is the kernel's NT * 16, dgrad the input gradient of a case (cout -> cin channels):
+  igemm_k3_small.hip (2x4x8)   16: test_conv3d_k3_exact 8->24 @5x7x9, 128->256 @6^3, 160->32 @8^3;  32: dgrad of 64->144 @7x9x11;
+                               48: 64->144 @7x9x11
+  igemm_k3_mid.hip (4x4x8)     16: 24->16 @13x15x17;  32: 72->32 @13x12x14, dgrad of 24->16;  48: 48->48 @12x12x24
+  igemm_k3_big_*.hip (4x8x16)  16: dgrad of 16->48 @32x33x34;  32: 16->48 @32x33x34 (Cout = 48 on two 32-wide blocks), fp32 32->32
+                               @32x33x34, bf16 64->32 @34x33x50;  no 48-wide instantiation (IGEMM_K3)
+  igemm_k3s2.hip               16: test_conv3d_k3s2_exact 16->16 @5x6x7;  32: the four S2_CASES;  48: 16->48 @5x6x7
+  igemm_flat.hip, direct       fp32: test_linear_exact 1152->16 (16), 3072->768 and every dgrad but the last (32), 1536->48, 48->144
+                               (48);  bf16: the 301-token cases 32->16 (16), 128->32 (32), 32->48 (48)
+  igemm_flat.hip, gather       test_conv3d_gather_exact 4->16 (16), 4->32 and 1->32 k7 (32), 1->48 k2 (48)
+  igemm_flat.hip, deconv       32 only: test_deconv_k2s2_exact, fp32 every case, bf16 the Cout = 8 cases
+  igemm_flat.hip, deconv_bwd   cout block of Cin: fp32 16->8 (16), 48->48 (48), the others (32);  bf16 16->8, 32->8, 48->8"""
 import functools
 import os
 
@@ -159,7 +173,26 @@ K3_CASES = [
     (32, 64, (30, 29, 70), 2, BF16, 3, 3),
     # 48-channel kernel (forward and input gradient: 48 gradient channels in)
     (48, 48, (30, 33, 36), 3, BF16, 4, 3),
+    # generic igemm, the (tile, cout block) pairs the generic cases above leave out (IGEMM_K3 below): 2x4x8 with 48- (forward) and 32-wide
+    # (input gradient) blocks; 4x4x8 with 16-wide blocks; 4x8x16 with Cout = 48 on 32-wide blocks, the second half empty (forward),
+    # and with 16-wide blocks (input gradient).  Odd extents: partial tiles on every axis of the two smaller tiles.
+    (64, 144, (7, 9, 11), 4, F32, 2, 0), (64, 144, (7, 9, 11), 4, BF16, 2, None),
+    (24, 16, (13, 15, 17), 2, F32, 1, 0), (24, 16, (13, 15, 17), 2, BF16, 1, None),
+    (16, 48, (32, 33, 34), 2, F32, 0, 0), (16, 48, (32, 33, 34), 2, BF16, 0, None),
 ]
+
+
+# What the generic cases run of igemm_fwd_kernel<27 taps, stride 1> on a card with 256 CUs (k3_plan counts workgroups against
+# 3/4 of them): (cin, cout, grid) -> (forward cout block, input-gradient kernel, input-gradient cout block), the same for both
+# dtypes unless a bf16 row says otherwise.  Every reachable (tile, cout block) pair of csrc/igemm_k3_{small,mid,big}.hip is here
+# in fp32 and bf16; the 4x8x16 tile has no 48-wide block (k3_plan answers 32).
+IGEMM_K3 = {
+    (8, 24, (5, 7, 9)): (16, 2, 16), (128, 256, (6, 6, 6)): (16, 2, 16), (160, 32, (8, 8, 8)): (16, 2, 16),
+    (64, 144, (7, 9, 11)): (48, 2, 32),
+    (48, 48, (12, 12, 24)): (48, 1, 48), (72, 32, (13, 12, 14)): (32, 1, 32), (24, 16, (13, 15, 17)): (16, 1, 32),
+    (32, 32, (32, 33, 34)): (32, 0, 32), (16, 48, (32, 33, 34)): (32, 0, 16),
+    (64, 32, (34, 33, 50), BF16): (32, 3, 32),      # input gradient 32 -> 64 on the ping-pong kernel
+}
 
 
 @pytest.mark.parametrize("cin,cout,sp,n0,dtype,kern,wgk", K3_CASES)
@@ -174,6 +207,10 @@ def test_conv3d_k3_exact(cin, cout, sp, n0, dtype, kern, wgk):
         assert L.msseg_conv3d_k3_variant(N, *sp, cout) == kern
     dgk = L.msseg_conv3d_k3_kernel(N, *sp, cout, cin, code)
     wg = L.msseg_conv3d_k3_wgrad_kernel(N, *sp, cin, cout, code)
+    blocks = IGEMM_K3.get((cin, cout, sp, dtype), IGEMM_K3.get((cin, cout, sp)))
+    assert (blocks is not None) == (kern <= 2)
+    if blocks is not None and L.msseg_num_cus() == 256:
+        assert (L.msseg_conv3d_k3_cout_block(N, *sp, cout), dgk, L.msseg_conv3d_k3_cout_block(N, *sp, cin)) == blocks
     if kern in (3, 4) and cin == cout:
         assert dgk == kern
     if wgk is not None:
@@ -353,6 +390,8 @@ def test_conv3d_k3_channel_slices_exact(sp, N, kern):
 # ------------------------------------------------------------------------------------------------------------------
 S2_CASES = [(48, 96, (12, 12, 12)), (32, 64, (9, 10, 11)), (96, 192, (5, 6, 7)), (16, 32, (3, 3, 3))]
 S2_PARAMS = [(*c, d) for c in S2_CASES for d in (F32, BF16)]
+# the cases above have Cout % 32 == 0 (32-wide cout blocks of csrc/igemm_k3s2.hip): 16- and 48-wide blocks, odd extents
+S2_EXACT_PARAMS = S2_PARAMS + [(*c, d) for c in [(16, 16, (5, 6, 7)), (16, 48, (5, 6, 7))] for d in (F32, BF16)]
 
 
 def _s2_run(x, w, b, dy, dtype, dev):
@@ -372,9 +411,11 @@ def _s2_run(x, w, b, dy, dtype, dev):
     return y, dyz, ya.detach(), xa.grad, wp.grad, bp.grad
 
 
-@pytest.mark.parametrize("cin,cout,sp,dtype", S2_PARAMS)
+@pytest.mark.parametrize("cin,cout,sp,dtype", S2_EXACT_PARAMS)
 def test_conv3d_k3s2_exact(cin, cout, sp, dtype):
+    from medicalsemseg_amd import hip
     dev = _dev()
+    assert hip.lib().msseg_cout_block(cout) == {16: 16, 32: 32, 48: 48, 64: 32, 96: 32, 192: 32}[cout]
     r = _k3_ref(cin, cout, sp, 2, 2)
     assert tuple(r["y"].shape[2:]) == tuple((v - 1) // 2 + 1 for v in sp)
     with launched() as k:
@@ -436,7 +477,10 @@ def _deconv_ref(cin, cout, sp, N, k):
 # <3, 3, 2> on a ragged W (a second 16-voxel group holding one voxel); the remaining forward instantiations <6, 2, 2> and <12, 1, 2>.
 # Maximum |reference| of the last two (y, dx, dw): 67, 124, 56 and 92, 121, 21
 DC2_CASES = [(32, 32, (8, 8, 8), 2), (256, 128, (3, 3, 3), 2), (48, 48, (4, 6, 10), 2), (128, 64, (4, 5, 7), 3),
-             (768, 384, (2, 3, 3), 2), (96, 48, (2, 3, 17), 2), (192, 96, (2, 3, 17), 2), (384, 192, (2, 3, 3), 2)]
+             (768, 384, (2, 3, 3), 2), (96, 48, (2, 3, 17), 2), (192, 96, (2, 3, 17), 2), (384, 192, (2, 3, 3), 2),
+             # Cout = 8: no register or sliced kernel takes it in either dtype, so forward and input gradient run on the generic
+             # igemm kernel (csrc/igemm_flat.hip: deconv epilogue on 32-wide blocks, deconv_bwd source on the 16- / 32- / 48-wide block of Cin)
+             (16, 8, (2, 3, 5), 2), (32, 8, (2, 3, 5), 2), (48, 8, (2, 3, 5), 2)]
 
 
 @pytest.mark.parametrize("cin,cout,sp,N,dtype", [(*c, d) for c in DC2_CASES for d in (F32, BF16)])
@@ -457,6 +501,8 @@ def test_deconv_k2s2_exact(cin, cout, sp, N, dtype):
     print(f"deconv_k2s2 {cin}->{cout} @ {sp} N={N} {dtype}: launched {sorted(k.names)}; partial-block input gradient: {part_ok}")
     assert part_ok == (dtype == BF16 and (cin, cout) in ((256, 128), (128, 64), (768, 384), (96, 48), (192, 96), (384, 192)))
     assert "lwg_kernel<deconv>" not in k.names and "igemm_wgrad_kernel<flat>" in k.names   # below 100 k coarse voxels: flat kernel
+    if cout == 8:
+        assert k.names == {"igemm_fwd_kernel<flat>", "igemm_wgrad_kernel<flat>"} and hip.lib().msseg_cout_block(cin) == cin
     assert_exact(vol(y), r["y"], "deconv_k2s2 fwd")
     assert_exact(vol(dx), r["dx"], "deconv_k2s2 bwd data")
     assert_exact(dw, r["dw"], "deconv_k2s2 wgrad")
@@ -533,7 +579,10 @@ def test_deconv_k4s4_exact(cin, cout, sp, dtype, dc4):
 # (msseg_linear_wgrad_ok): cout / 16 a multiple of 3 and cin / 16 a multiple of 3 (the instantiated slice shapes), and not a few
 # tokens (< 1024) against a large weight (cin * cout > 200000).
 LIN_CASES = [(17, 1152, 16, False), (433, 1536, 48, True), (54, 3072, 768, False),   # few tokens, deep K: the waves split K (bf16)
-             (4099, 48, 144, True)]                                                   # many tokens: weights in registers (bf16)
+             (4099, 48, 144, True),                                                   # many tokens: weights in registers (bf16)
+             # Cin of one or four 32-channel k-steps: no register kernel, bf16 too runs csrc/igemm_flat.hip, forward on 48- / 16- /
+             # 32-wide cout blocks (the input gradient of the first two has three and two k-steps: register kernel in bf16)
+             (301, 32, 48, False), (301, 32, 16, False), (301, 128, 32, False)]
 
 
 @pytest.mark.parametrize("tokens,cin,cout,lwg,dtype", [(*c, d) for c in LIN_CASES for d in (F32, BF16)])
@@ -552,6 +601,8 @@ def test_linear_exact(tokens, cin, cout, lwg, dtype):
         hip.conv3d_k1_wgrad(xg, dyg, dw, cin, cout)
     print(f"linear {cin}->{cout}, {tokens} tokens, {dtype}: launched {sorted(k.names)}; one-pass wgrad ok: {one_pass}")
     assert one_pass == (lwg and dtype == BF16)
+    if tokens == 301:
+        assert "igemm_fwd_kernel<flat>" in k.names and hip.lib().msseg_cout_block(cout) == cout
     assert_exact(y, x @ w.t() + b, "conv3d_k1 fwd")
     assert_exact(dx, dy @ w, "conv3d_k1 dgrad")
     assert_exact(dw, dy.t() @ x, "conv3d_k1_wgrad")
@@ -627,7 +678,8 @@ def test_conv3d_stem_exact(cout, sp, N):
     assert_exact(dw, 2 * w.grad, "stem wgrad accumulate")
 
 
-GATHER_CASES = [(1, 48, 2, 2, 0, (12, 12, 12)), (4, 32, 3, 1, 1, (5, 7, 9)), (1, 32, 7, 4, 3, (16, 20, 24))]
+# cout blocks of the gather source (csrc/igemm_flat.hip): 48, 32, 32 and 16 wide
+GATHER_CASES = [(1, 48, 2, 2, 0, (12, 12, 12)), (4, 32, 3, 1, 1, (5, 7, 9)), (1, 32, 7, 4, 3, (16, 20, 24)), (4, 16, 3, 1, 1, (5, 7, 9))]
 
 
 @pytest.mark.parametrize("cin,cout,k,s,p,sp,dtype", [(*c, d) for c in GATHER_CASES for d in (F32, BF16)])
