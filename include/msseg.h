@@ -257,6 +257,15 @@ int msseg_linear_wgrad(const void* x, long long ldx, const void* dy, long long l
 int msseg_conv3d_gather_wgrad(const void* x, long long ldx, const void* dy, long long lddy, float* dw,
                               int N, int ID, int IH, int IW, int Cin, int Cout, int k, int s, int p, int accumulate,
                               void* workspace, size_t workspace_bytes, int dtype, msseg_stream_t stream);
+/* Weight gradient of the one-input-channel stem conv (k 3 p 1, or k 1) whose output feeds InstanceNorm + LeakyReLU, with
+ * that unit's backward apply folded into the operand load: dy = apply(yraw, da; stats, red, gamma, beta) as
+ * msseg_instnorm_act_bwd_apply (y = NULL) would store it is formed tile by tile and never written; dw has the bits of that
+ * call followed by msseg_conv3d_gather_wgrad.  bf16, Cout a multiple of 32 or 48 (<= 256), N <= 8; anything else is an
+ * error.  workspace as for msseg_conv3d_gather_wgrad. */
+int msseg_conv3d_stem_wgrad_inbwd(const void* x, long long ldx, const void* yraw, long long ldyraw, const void* da,
+                                  long long ldda, const float* stats, const float* red, const float* gamma, const float* beta,
+                                  float eps, float slope, float* dw, int N, int D, int H, int W, int Cout, int k,
+                                  int accumulate, void* workspace, size_t workspace_bytes, int dtype, msseg_stream_t stream);
 int msseg_deconv_k2s2_wgrad(const void* x, long long ldx, const void* dy, long long lddy, float* dw,
                             int N, int D, int H, int W, int Cin, int Cout, int accumulate,
                             void* workspace, size_t workspace_bytes, int dtype, msseg_stream_t stream);
@@ -422,6 +431,14 @@ int msseg_instnorm_act_bwd_apply(const void* x, long long ldx, const float* stat
                                  const float* beta, const void* y, long long ldy, const void* dy, long long lddy, const float* red, void* dx,
                                  long long lddx, void* dres, long long lddres, int N, long long S, int C, float eps,
                                  float slope, int dtype, msseg_stream_t stream);
+/* msseg_instnorm_act_bwd_apply (y = NULL, no dres) for the unit in front of a <= 4-class 1x1x1 head whose input gradient was
+ * not stored (msseg_conv3d_k1_head_bwd_fused with da = NULL): the gradient of the unit's activation is formed again from the
+ * class gradient rows dl (16 bytes per voxel, pitch lddl) and the head's weight w[Cout][C], rounded as that kernel stores
+ * it; dx has the bits of the plain apply fed with the stored da.  C <= 64 in 16-byte chunks; anything else is an error. */
+int msseg_instnorm_act_bwd_apply_head(const void* x, long long ldx, const float* stats, const float* gamma,
+                                      const float* beta, const void* dl, long long lddl, const float* w, int Cout,
+                                      const float* red, void* dx, long long lddx, int N, long long S, int C, float eps,
+                                      float slope, int dtype, msseg_stream_t stream);
 /* MaxPool3d(2) forward / backward (first maximum in scan order receives the gradient, as ATen). */
 int msseg_maxpool2_fwd(const void* x, long long ldx, void* y, long long ldy, int N, int D, int H, int W, int C,
                        int dtype, msseg_stream_t stream);

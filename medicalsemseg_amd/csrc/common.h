@@ -152,6 +152,52 @@ template <> struct Chunk<float> {
     static MSSEG_DEVFN void store(float* p, const float* f) { *(f32x4_t*)p = f32x4_t{f[0], f[1], f[2], f[3]}; }
 };
 
+// the 16 bytes Chunk<bf16_t>::store writes, in registers (for a kernel that keeps the chunk in LDS)
+MSSEG_DEVFN u32x4_t chunk_pack_bf16(const float* f) {
+    bf16x8_t v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (bf16_t)f[e];
+    return __builtin_bit_cast(u32x4_t, v);
+}
+
+// ---- InstanceNorm + LeakyReLU backward, per element -------------------------------------------------------------------
+// Shared by the backward apply pass (elementwise.hip) and by the kernels that apply it to an operand as they load it
+// (stem_conv.hip), which must give the apply pass's bits.  The expressions are written as the apply pass has always had them
+// and the contraction is the compiler's: in both places it makes one fma of the pre-activation, one of dz - k0 - xh * k1,
+// fma(-mean, mean, s2 / S) of the variance and fma(-mean, sc, beta) of the shift (read from the device assembly; writing the
+// fmas out changes nothing in the arithmetic but reschedules the apply pass).  tests/test_gpu_inbwd_fused.py compares the bits.
+MSSEG_DEVFN void mean_rstd(const float* stats, int n, int C, int c, long long S, float eps, float& mean, float& rstd) {
+    const float inv = 1.0f / (float)S;
+    const float s = stats[((long long)n * C + c) * 2 + 0], s2 = stats[((long long)n * C + c) * 2 + 1];
+    mean = s * inv;
+    float var = s2 * inv - mean * mean;
+    var = var > 0.f ? var : 0.f;
+    rstd = rsqrtf(var + eps);
+}
+// scale and shift of the normalisation: y = x * sc + sh
+MSSEG_DEVFN void norm_scale_shift(const float* gamma, const float* beta, int c, float mean, float rstd, float& sc, float& sh) {
+    sc = rstd * (gamma ? gamma[c] : 1.f);
+    sh = (beta ? beta[c] : 0.f) - mean * sc;
+}
+// sign source of the activation where it was not stored: the pre-activation as the forward formed it
+MSSEG_DEVFN float norm_preact(float x, float sc, float sh) { return x * sc + sh; }
+// the gradient of the pre-activation from the gradient dv of the activation (yv: the activation, or the pre-activation)
+MSSEG_DEVFN float norm_bwd_dz(float yv, float dv, float slope) { return yv > 0.f ? dv : dv * slope; }
+// the gradient of the raw element x; k0 / k1 = the sample's channel sums of dz and dz * xhat over the voxels, divided by S
+MSSEG_DEVFN float norm_bwd_dx(float x, float dz, float mean, float rstd, float sc, float k0, float k1) {
+    const float xh = (x - mean) * rstd;
+    return sc * (dz - k0 - xh * k1);
+}
+
+// input gradient of the <= 4-class 1x1x1 head for channel e of a chunk, rounded to T as the head's backward stores it:
+// dl = the voxel's class gradients, wv[k][e] = the weight of class k as T (0 past the last class)
+template <typename T, int W> MSSEG_DEVFN float head_da(const float* dl, const float (*wv)[W], int e) {
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc += dl[k] * wv[k][e];
+    return (float)(T)acc;
+}
+
 // 4 consecutive channels at p (aligned to 4 elements) <-> 4 floats
 template <typename T> MSSEG_DEVFN void load4(const T* p, float* f);
 template <> MSSEG_DEVFN void load4<float>(const float* p, float* f) { Chunk<float>::load(p, f); }

@@ -361,17 +361,10 @@ struct NormParams {
     long long S; int C; float eps, slope;
     long long rows_per_block; int groups, rows_par;
     float* ws; unsigned int* counter; float* dgamma; float* dbeta; int accumulate;
+    const float* hw; int hcout;          // MODE 2 with the HEAD source: dy holds the class gradient rows, hw the head's weight
 };
 
-MSSEG_DEVFN void mean_rstd(const float* stats, int n, int C, int c, long long S, float eps, float& mean, float& rstd) {
-    const float inv = 1.0f / (float)S;
-    const float s = stats[((long long)n * C + c) * 2 + 0], s2 = stats[((long long)n * C + c) * 2 + 1];
-    mean = s * inv;
-    float var = s2 * inv - mean * mean;
-    var = var > 0.f ? var : 0.f;
-    rstd = rsqrtf(var + eps);
-}
-
+// mean_rstd, norm_scale_shift, norm_preact, norm_bwd_dz, norm_bwd_dx: common.h
 // MODE 0: forward   MODE 1: backward reduce   MODE 2: backward apply
 // (launched for MODE 1, and for the scalar fallback of MODE 0 / 2; on 16-byte chunks those two run instnorm_stream_kernel)
 template <typename T, bool VEC, int MODE>
@@ -538,12 +531,16 @@ constexpr int NORM_BLOCKS_PER_CU = 2;
 
 // one trip: rows rb + u * rows_par, u < NORM_U, of the block's nrows.  TAIL: some of them are past the end (the full trips
 // carry no test at all, so that nothing tempts the compiler to move a load behind one)
-template <typename T, int MODE, bool OPT, bool DRES, bool TAIL>
+// HEAD (MODE 2 without OPT / DRES): the incoming gradient is not a tensor.  dyb holds the class gradient rows of the <= 4-class
+// head behind this unit (16 bytes per voxel, the same row for every channel chunk) and hwv the head's weights for this chunk:
+// dv = head_da(), the value head_dgrad_inbwd_kernel would have stored and this pass read back
+template <typename T, int MODE, bool OPT, bool DRES, bool TAIL, bool HEAD = false>
 MSSEG_DEVFN void norm_stream_batch(const char* __restrict__ xb, unsigned ldx, const char* __restrict__ ob, unsigned ldo,
                                    const char* __restrict__ dyb, unsigned lddy, char* __restrict__ outb, unsigned ldout,
                                    char* __restrict__ drb, unsigned lddr, int rb, int rows_par, int nrows, unsigned cg,
                                    const float* mean, const float* rstd, const float* sc, const float* sh,
-                                   const float* k0, const float* k1, float slope) {
+                                   const float* k0, const float* k1, float slope,
+                                   const float (*hwv)[DT<T>::EPC] = nullptr) {
     constexpr int W = DT<T>::EPC, U = NORM_U;
     constexpr unsigned ES = sizeof(T);
     unsigned row[U];
@@ -559,7 +556,7 @@ MSSEG_DEVFN void norm_stream_batch(const char* __restrict__ xb, unsigned ldx, co
     for (int u = 0; u < U; ++u) xr[u] = ldg16(xb + (row[u] * ldx + cg) * ES);
     if constexpr (MODE == 2) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) dr[u] = ldg16(dyb + (row[u] * lddy + cg) * ES);
+        for (int u = 0; u < U; ++u) dr[u] = ldg16(dyb + (row[u] * lddy + (HEAD ? 0u : cg)) * ES);
     }
     if constexpr (OPT) {
 #pragma unroll
@@ -584,17 +581,23 @@ MSSEG_DEVFN void norm_stream_batch(const char* __restrict__ xb, unsigned ldx, co
             }
         } else {
             Chunk<T>::unpack(dr[u], dv);
+            if constexpr (HEAD) {
+                float dl[W];
+#pragma unroll
+                for (int e = 0; e < W; ++e) dl[e] = dv[e];
+#pragma unroll
+                for (int e = 0; e < W; ++e) dv[e] = head_da<T, W>(dl, hwv, e);
+            }
             if constexpr (OPT) {
                 Chunk<T>::unpack(orw[u], yv);
             } else {   // sign of the pre-activation, recomputed exactly as the forward formed it
 #pragma unroll
-                for (int e = 0; e < W; ++e) yv[e] = xv[e] * sc[e] + sh[e];
+                for (int e = 0; e < W; ++e) yv[e] = norm_preact(xv[e], sc[e], sh[e]);
             }
 #pragma unroll
             for (int e = 0; e < W; ++e) {
-                const float dz = yv[e] > 0.f ? dv[e] : dv[e] * slope;
-                const float xh = (xv[e] - mean[e]) * rstd[e];
-                o[e] = sc[e] * (dz - k0[e] - xh * k1[e]);
+                const float dz = norm_bwd_dz(yv[e], dv[e], slope);
+                o[e] = norm_bwd_dx(xv[e], dz, mean[e], rstd[e], sc[e], k0[e], k1[e]);
                 dv[e] = dz;
             }
         }
@@ -605,9 +608,10 @@ MSSEG_DEVFN void norm_stream_batch(const char* __restrict__ xb, unsigned ldx, co
     }
 }
 
-template <typename T, int MODE, bool OPT, bool DRES>
-__global__ __launch_bounds__(256, 4) void instnorm_stream_kernel(const NormParams p) {
+template <typename T, int MODE, bool OPT, bool DRES, bool HEAD = false>
+__global__ __launch_bounds__(256, HEAD ? NORM_BLOCKS_PER_CU : 4) void instnorm_stream_kernel(const NormParams p) {
     static_assert(MODE == 0 || MODE == 2, "streaming modes only");
+    static_assert(!HEAD || (MODE == 2 && !OPT && !DRES), "the head source replaces the gradient tensor of the plain apply");
     constexpr int W = DT<T>::EPC;
     const int n = blockIdx.y;
     const int g = threadIdx.x % p.groups, rl = threadIdx.x / p.groups;
@@ -638,9 +642,7 @@ __global__ __launch_bounds__(256, 4) void instnorm_stream_kernel(const NormParam
         for (int e = 0; e < W; ++e) {
             const int c = gg * W + e;
             mean_rstd(p.stats, n, p.C, c, p.S, p.eps, mean[e], rstd[e]);
-            const float ga = p.gamma ? p.gamma[c] : 1.f;
-            sc[e] = rstd[e] * ga;
-            sh[e] = (p.beta ? p.beta[c] : 0.f) - mean[e] * sc[e];
+            norm_scale_shift(p.gamma, p.beta, c, mean[e], rstd[e], sc[e], sh[e]);
             if constexpr (MODE == 2) {
                 k0[e] = p.red[((long long)n * p.C + c) * 2 + 0] * invS;
                 k1[e] = p.red[((long long)n * p.C + c) * 2 + 1] * invS;
@@ -648,14 +650,21 @@ __global__ __launch_bounds__(256, 4) void instnorm_stream_kernel(const NormParam
                 k0[e] = k1[e] = 0.f;
             }
         }
+        float hwv[HEAD ? 4 : 1][W];
+        if constexpr (HEAD) {   // as head_dgrad_inbwd_kernel sets them up
+#pragma unroll
+            for (int e = 0; e < W; ++e)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) hwv[k][e] = k < p.hcout ? (float)(T)p.hw[k * p.C + gg * W + e] : 0.f;
+        }
         const unsigned cg = (unsigned)(gg * W);
         int rb = rl;
         for (; rb + (NORM_U - 1) * p.rows_par < nrows; rb += NORM_U * p.rows_par)
-            norm_stream_batch<T, MODE, OPT, DRES, false>(xb, (unsigned)p.ldx, ob, ldo, dyb, lddy, outb, ldout, drb, lddr, rb,
-                                                         p.rows_par, nrows, cg, mean, rstd, sc, sh, k0, k1, p.slope);
+            norm_stream_batch<T, MODE, OPT, DRES, false, HEAD>(xb, (unsigned)p.ldx, ob, ldo, dyb, lddy, outb, ldout, drb, lddr, rb,
+                                                               p.rows_par, nrows, cg, mean, rstd, sc, sh, k0, k1, p.slope, hwv);
         if (rb < nrows)
-            norm_stream_batch<T, MODE, OPT, DRES, true>(xb, (unsigned)p.ldx, ob, ldo, dyb, lddy, outb, ldout, drb, lddr, rb,
-                                                        p.rows_par, nrows, cg, mean, rstd, sc, sh, k0, k1, p.slope);
+            norm_stream_batch<T, MODE, OPT, DRES, true, HEAD>(xb, (unsigned)p.ldx, ob, ldo, dyb, lddy, outb, ldout, drb, lddr, rb,
+                                                              p.rows_par, nrows, cg, mean, rstd, sc, sh, k0, k1, p.slope, hwv);
     }
 }
 
@@ -920,10 +929,7 @@ __global__ __launch_bounds__(RED_THREADS) void head_dgrad_inbwd_kernel(const Hea
                 dc.load(dyn + r * p.lddy);            // the first EPC (>= 4) channels of the class gradient
 #pragma unroll
                 for (int e = 0; e < WD; ++e) {
-                    float acc = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) acc += dc.v[k] * wv[k][e];
-                    const float da = (float)(T)acc;
+                    const float da = head_da<T, WD>(dc.v, wv, e);
                     o.v[e] = da;
                     const float z = xc.v[e] * sc[e] + sh[e];
                     const float dz = z > 0.f ? da : da * p.slope;
@@ -935,7 +941,9 @@ __global__ __launch_bounds__(RED_THREADS) void head_dgrad_inbwd_kernel(const Hea
                         for (int k = 0; k < 4; ++k) gw[k][e] += dc.v[k] * av;
                     }
                 }
-                o.store(dan + r * p.ldda + gg * WD);
+                // da absent (weight-gradient form only): the apply pass forms it again from dy and w (its HEAD source).  A
+                // runtime test, wave-uniform; the form without dW keeps its one code path, and with it its contraction
+                if (!DW || p.da != nullptr) o.store(dan + r * p.ldda + gg * WD);
             }
         }
         constexpr int NPER = DW ? 6 : 2;
@@ -971,11 +979,11 @@ __global__ __launch_bounds__(RED_THREADS) void head_dgrad_inbwd_kernel(const Hea
 }
 
 // MODE 0 / 2 on 16-byte chunks: one resident set of blocks, sized from what the instantiation really gets per CU
-template <typename T, int MODE, bool OPT, bool DRES> int launch_norm_stream(NormParams& p, int N, hipStream_t st) {
+template <typename T, int MODE, bool OPT, bool DRES, bool HEAD = false> int launch_norm_stream(NormParams& p, int N, hipStream_t st) {
     static std::atomic<int> resident{0};   // blocks per CU, asked once per instantiation
     int per_cu = resident.load(std::memory_order_relaxed);
     if (per_cu == 0) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)instnorm_stream_kernel<T, MODE, OPT, DRES>,
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)instnorm_stream_kernel<T, MODE, OPT, DRES, HEAD>,
                                                          256, 0) != hipSuccess || per_cu < 1)
             MSSEG_FAIL(MSSEG_ELAUNCH, "instnorm: no occupancy for the streaming kernel");
         resident.store(per_cu, std::memory_order_relaxed);
@@ -998,7 +1006,7 @@ template <typename T, int MODE, bool OPT, bool DRES> int launch_norm_stream(Norm
     const long long trip = (long long)m.rows_par * NORM_U;   // whole trips, where the run limit allows: one tail per sample
     if (ceil_div_ll(p.rows_per_block, trip) * trip <= max_run) p.rows_per_block = ceil_div_ll(p.rows_per_block, trip) * trip;
     blocks = ceil_div_ll(p.S, p.rows_per_block);
-    hipLaunchKernelGGL((instnorm_stream_kernel<T, MODE, OPT, DRES>), dim3((unsigned)blocks, N), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((instnorm_stream_kernel<T, MODE, OPT, DRES, HEAD>), dim3((unsigned)blocks, N), dim3(256), 0, st, p);
     MSSEG_CHECK_LAUNCH("instnorm");
     return MSSEG_OK;
 }
@@ -1622,12 +1630,12 @@ static int head_bwd_impl(const void* dy, long long lddy, const float* w, void* d
                          const float* beta, float slope, float eps, float* red, float* dgamma, float* dbeta, int accumulate,
                          float* dw, int dw_accumulate, void* scratch, size_t scratch_bytes, int dtype,
                          msseg_stream_t stream) {
-    if (!dy || !w || !da || !yraw || !fwd_stats || !red || N < 1 || S < 1)
+    if (!dy || !w || (!da && !dw) || !yraw || !fwd_stats || !red || N < 1 || S < 1)   // da == NULL (with dw): da is not stored
         MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k1_head_dgrad_inbwd: bad args");
     if (dtype != MSSEG_F32 && dtype != MSSEG_BF16) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k1_head_dgrad_inbwd: bad dtype");
     if (int rc = scratch_ok(scratch, scratch_bytes, "conv3d_k1_head_dgrad_inbwd")) return rc;
     const int esz = dtype == MSSEG_F32 ? 4 : 2, epc = 16 / esz;
-    if (Cout < 1 || Cout > 4 || C < 1 || C > 64 || !vec_ok(yraw, ldyraw, C, esz) || !vec_ok(da, ldda, C, esz) ||
+    if (Cout < 1 || Cout > 4 || C < 1 || C > 64 || !vec_ok(yraw, ldyraw, C, esz) || (da && !vec_ok(da, ldda, C, esz)) ||
         (lddy % epc) || ((uintptr_t)dy & 15))
         MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k1_head_dgrad_inbwd: needs <= 4 classes in 16-byte aligned gradient rows and "
                                  "16-byte channel chunks (C=%d, Cout=%d, lddy=%lld)", C, Cout, lddy);
@@ -1792,6 +1800,26 @@ int msseg_instnorm_act_bwd_apply(const void* x, long long ldx, const float* stat
     int rc = MSSEG_OK;
     const bool known = for_dtype(dtype, [&](auto t) { rc = launch_norm<typename decltype(t)::type, 2>(p, N, vec, (hipStream_t)stream); });
     return known ? rc : bad_dtype(dtype);
+}
+
+int msseg_instnorm_act_bwd_apply_head(const void* x, long long ldx, const float* stats, const float* gamma,
+                                      const float* beta, const void* dl, long long lddl, const float* w, int Cout,
+                                      const float* red, void* dx, long long lddx, int N, long long S, int C, float eps,
+                                      float slope, int dtype, msseg_stream_t stream) {
+    if (!x || !stats || !dl || !w || !red || !dx || N < 1 || S < 1) MSSEG_FAIL(MSSEG_EINVAL, "instnorm_act_bwd_apply_head: bad args");
+    if (dtype != MSSEG_F32 && dtype != MSSEG_BF16) return bad_dtype(dtype);
+    const int esz = dtype == MSSEG_F32 ? 4 : 2, epc = 16 / esz;
+    if (Cout < 1 || Cout > 4 || C < 1 || C > 64 || !vec_ok(x, ldx, C, esz) || !vec_ok(dx, lddx, C, esz) || (lddl % epc) ||
+        ((uintptr_t)dl & 15))
+        MSSEG_FAIL(MSSEG_EINVAL, "instnorm_act_bwd_apply_head: needs <= 4 classes in 16-byte aligned gradient rows and "
+                                 "16-byte channel chunks (C=%d, Cout=%d, lddl=%lld)", C, Cout, lddl);
+    NormParams p{};
+    p.x = x; p.ldx = ldx; p.stats = stats; p.gamma = gamma; p.beta = beta; p.dy = dl; p.lddy = lddl;
+    p.red = (float*)red; p.dx = dx; p.lddx = lddx; p.hw = w; p.hcout = Cout;
+    p.S = S; p.C = C; p.eps = eps; p.slope = slope;
+    int rc = MSSEG_OK;
+    for_dtype(dtype, [&](auto t) { rc = launch_norm_stream<typename decltype(t)::type, 2, false, false, true>(p, N, (hipStream_t)stream); });
+    return rc;
 }
 
 int msseg_maxpool2_fwd(const void* x, long long ldx, void* y, long long ldy, int N, int D, int H, int W, int C,

@@ -672,6 +672,38 @@ int msseg_conv3d_gather_wgrad(const void* x, long long ldx, const void* dy, long
                : launch_wg<bf16_t, 1, Q_GATHER, 1, 1, 256>(p, rp, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+int msseg_conv3d_stem_wgrad_inbwd(const void* x, long long ldx, const void* yraw, long long ldyraw, const void* da,
+                                  long long ldda, const float* stats, const float* red, const float* gamma, const float* beta,
+                                  float eps, float slope, float* dw, int N, int D, int H, int W, int Cout, int k,
+                                  int accumulate, void* workspace, size_t workspace_bytes, int dtype, msseg_stream_t stream) {
+    if (!x || !yraw || !da || !stats || !red || !dw || !workspace || N < 1 || D < 1 || H < 1 || W < 1)
+        MSSEG_FAIL(MSSEG_EINVAL, "conv3d_stem_wgrad_inbwd: bad args");
+    if ((gamma == nullptr) != (beta == nullptr)) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_stem_wgrad_inbwd: gamma/beta go together");
+    const int pd = k == 3 ? 1 : 0;
+    const int mblks = ceil_div(Cout, 32);
+    if ((k != 3 && k != 1) || N > 8 || (long long)N * D * H * W > 0x7fffffffLL ||
+        !msseg_stem_eligible(dtype, 1, Cout, k, 1, pd, ldx, ldyraw, yraw) ||
+        !msseg_aligned_bf16(dtype, yraw, ldyraw, Cout, da, ldda, Cout) ||
+        workspace_bytes < (size_t)8 * 4096 * mblks)
+        MSSEG_FAIL(MSSEG_EINVAL, "conv3d_stem_wgrad_inbwd: one input channel, bf16, k 3 or 1, Cout a multiple of 32 or 48 (<= 256) "
+                                 "in 16-byte aligned rows, N <= 8 only (Cout=%d, k=%d, N=%d)", Cout, k, N);
+    StemWgParams sp{};
+    sp.x = x; sp.ldx = ldx; sp.N = N; sp.D = D; sp.H = H; sp.W = W; sp.M = Cout;
+    sp.yraw = yraw; sp.ldyraw = ldyraw; sp.da = da; sp.ldda = ldda;
+    sp.stats = stats; sp.red = red; sp.gamma = gamma; sp.beta = beta; sp.eps = eps; sp.slope = slope;
+    int gx = msseg_stem_wgrad_grid(sp);
+    const long long fit = (long long)(workspace_bytes / ((size_t)4096 * mblks));
+    if (gx > fit) gx = (int)(fit & ~7LL);
+    sp.slabs = (float*)workspace;
+    if (int rc = msseg_stem_wgrad_launch(sp, gx, (hipStream_t)stream)) return rc;
+    const int KT = k * k * k;
+    ReduceParams rq{};   // as the stem route of msseg_conv3d_gather_wgrad: the same slabs, the same order
+    rq.dw = dw; rq.M = Cout; rq.M0 = Cout; rq.T = 1; rq.K = KT; rq.K0 = 1;
+    rq.s_m0 = KT; rq.s_k1 = 1; rq.s_k0 = KT; rq.accumulate = accumulate;
+    rq.slabs = sp.slabs + (k == 1 ? 13 : 0); rq.mblks = mblks; rq.kblks = 1; rq.nslots = gx; rq.cbw = 32;
+    return launch_reduce(rq, (hipStream_t)stream);
+}
+
 int msseg_deconv_k2s2_wgrad(const void* x, long long ldx, const void* dy, long long lddy, float* dw, int N, int D, int H,
                             int W, int Cin, int Cout, int accumulate, void* workspace, size_t workspace_bytes,
                             int dtype, msseg_stream_t stream) {

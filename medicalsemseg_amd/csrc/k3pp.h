@@ -103,6 +103,11 @@ struct StemWgParams {
     const void* dy; long long lddy;
     float* slabs;                     // [cout block][workgroup][32][32] fp32
     int N, D, H, W, M;
+    // yraw != nullptr (dy unused): dy = the InstanceNorm + LeakyReLU backward apply of (yraw, da) with the forward statistics
+    // stats[N][M][2] and the backward sums red[N][M][2], formed tile by tile and never stored; N <= 8
+    const void* yraw; long long ldyraw;
+    const void* da; long long ldda;
+    const float* stats; const float* red; const float* gamma; const float* beta; float eps, slope;
 };
 bool msseg_stem_eligible(int dtype, int Cin, int Cout, int k, int s, int pd, long long ldx, long long ldy, const void* y);
 int msseg_stem_fwd_launch(const StemParams& p, hipStream_t stream);

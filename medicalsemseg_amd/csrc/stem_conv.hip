@@ -179,10 +179,21 @@ constexpr int XP = 24;                              // row pitch (elements) of t
 constexpr int XS_ELEMS = PD * PH * XP;              // one shifted copy
 constexpr int P_BYTES = TD * TH * TW * 64;          // dy tile, 32 channels
 
+constexpr int WG_BUF_BYTES = P_BYTES + 3 * XS_ELEMS * 2 + 64;
+constexpr int WG_NMAX = 8;                          // samples of the INBWD constants table
+constexpr int WG_TAB_BYTES = WG_NMAX * 32 * 6 * 4;
+
+// INBWD: dy does not exist.  It is the InstanceNorm + LeakyReLU backward apply (elementwise.hip, instnorm_stream_kernel MODE 2
+// without the stored activation) of the unit's raw output yraw and the gradient da of its activation; the only consumer of the
+// stem's dy is this weight gradient (no input gradient, and the bias gradient of a conv in front of InstanceNorm is zero), so
+// the tile is formed while it is staged: each thread loads the yraw and da chunks of the LDS slots the DMA would have filled
+// for it, applies common.h's norm_bwd_dz / norm_bwd_dx with the apply pass's per-channel constants, rounds to bf16 as that
+// pass stores and writes the 16 bytes to the slot.  The MFMA loop sees the same tile, so dW has the two-kernel path's bits.
+template <bool INBWD>
 __global__ __launch_bounds__(W_THREADS) void stem_wgrad_kernel(const StemWgParams p) {
     extern __shared__ __attribute__((aligned(256))) unsigned char smem[];
-    // [2 buffers] x { dy tile 16 KB | 3 shifted x copies }
-    constexpr int BUF_BYTES = P_BYTES + 3 * XS_ELEMS * 2 + 64;
+    // [2 buffers] x { dy tile 16 KB | 3 shifted x copies } (+ INBWD: constants [n][channel of the block][mean, rstd, sc, sh, k0, k1])
+    constexpr int BUF_BYTES = WG_BUF_BYTES;
     lds_u8* smem3 = (lds_u8*)smem;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -198,9 +209,39 @@ __global__ __launch_bounds__(W_THREADS) void stem_wgrad_kernel(const StemWgParam
     for (int j = 0; j < 4; ++j) {
         const int tv = (wave + 4 * j) * 16 + (lane >> 2);
         const int td = tv / (TH * TW), th = (tv / TW) % TH, tw = tv % TW;
-        p_off[j] = (unsigned)((((long long)td * p.H + th) * p.W + tw) * p.lddy * 2 + (lane & 3) * 16);
+        if constexpr (INBWD) p_off[j] = (unsigned)(((long long)td * p.H + th) * p.W + tw);   // voxels: yraw and da have their own pitch
+        else p_off[j] = (unsigned)((((long long)td * p.H + th) * p.W + tw) * p.lddy * 2 + (lane & 3) * 16);
+    }
+    // INBWD: the two operand chunks of the thread's four slots, loaded one tile ahead; the constants of its 8 channels
+    u32x4_t yr[INBWD ? 4 : 1], dr[INBWD ? 4 : 1];
+    float cst[INBWD ? 8 : 1][6];
+    int n_cst = -1;
+    const bool ch_ok_t = mblk * 32 + (lane & 3) * 8 < p.M;
+    if constexpr (INBWD) {
+        // the table: instnorm_stream_kernel's per-channel constants, once per workgroup
+        float* tab = (float*)(smem + 2 * BUF_BYTES);
+        const float invS = 1.0f / (float)((long long)p.D * p.H * p.W);
+        for (int i = tid; i < p.N * 32; i += W_THREADS) {
+            const int n = i >> 5, c = mblk * 32 + (i & 31);
+            float mean = 0.f, rstd = 0.f, nsc = 0.f, nsh = 0.f, k0 = 0.f, k1 = 0.f;
+            if (c < p.M) {
+                mean_rstd(p.stats, n, p.M, c, (long long)p.D * p.H * p.W, p.eps, mean, rstd);
+                norm_scale_shift(p.gamma, p.beta, c, mean, rstd, nsc, nsh);
+                k0 = p.red[((long long)n * p.M + c) * 2 + 0] * invS;
+                k1 = p.red[((long long)n * p.M + c) * 2 + 1] * invS;
+            }
+            float* t = tab + i * 6;
+            t[0] = mean; t[1] = rstd; t[2] = nsc; t[3] = nsh; t[4] = k0; t[5] = k1;
+        }
+        __syncthreads();
     }
     unsigned short st[3];
+    auto slot_ok = [&](const TileCo& tc, int j, bool full) {   // is the voxel of the thread's slot j inside the volume?
+        if (full) return true;
+        const int tv = (wave + 4 * j) * 16 + (lane >> 2);
+        const int td = tv / (TH * TW), th = (tv / TW) % TH, tw = tv % TW;
+        return tc.d0 + td < p.D && tc.h0 + th < p.H && tc.w0 + tw < p.W;
+    };
     auto load_tile = [&](const TileCo& tc, int buf) {
         unsigned char* base = smem + buf * BUF_BYTES;
         const long long pvox = (((long long)tc.n * p.D + tc.d0) * p.H + tc.h0) * p.W + tc.w0;
@@ -208,8 +249,21 @@ __global__ __launch_bounds__(W_THREADS) void stem_wgrad_kernel(const StemWgParam
         const bool full = tc.d0 + TD <= p.D && tc.h0 + TH <= p.H && tc.w0 + TW <= p.W;
         const unsigned char* zsrc = (const unsigned char*)&g_zero_chunk;
         const bool ch_ok = mblk * 32 + (lane & 3) * 8 < p.M;   // 48 couts: the second block's upper half is padding
+        if constexpr (INBWD) {
+            // a slot that will hold zeros (outside the volume, padding channels) loads the tile's first voxel, first chunk
+            const unsigned char* yb = (const unsigned char*)p.yraw + mblk * 64 + pvox * p.ldyraw * 2;
+            const unsigned char* db = (const unsigned char*)p.da + mblk * 64 + pvox * p.ldda * 2;
+            unsigned vo[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
+            for (int j = 0; j < 4; ++j) vo[j] = slot_ok(tc, j, full) ? p_off[j] : 0u;
+            const unsigned co = ch_ok ? (lane & 3) * 16 : 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) yr[j] = ldg16(yb + (size_t)vo[j] * (unsigned)(p.ldyraw * 2) + co);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dr[j] = ldg16(db + (size_t)vo[j] * (unsigned)(p.ldda * 2) + co);
+        }
+#pragma unroll
+        for (int j = 0; j < (INBWD ? 0 : 4); ++j) {
             const unsigned char* src = pb + p_off[j];
             if (!ch_ok) src = zsrc;
             if (!full) {
@@ -245,6 +299,37 @@ __global__ __launch_bounds__(W_THREADS) void stem_wgrad_kernel(const StemWgParam
         }
     };
 
+    // INBWD: the staged chunks -> the dy tile of buffer buf, where the DMA would have put them
+    auto commit_dy = [&](const TileCo& tc, int buf) {
+        if constexpr (INBWD) {
+            if (tc.n != n_cst) {
+                const f32x4_t* t = (const f32x4_t*)(smem + 2 * BUF_BYTES + ((tc.n * 32 + (lane & 3) * 8) * 6) * 4);
+#pragma unroll
+                for (int i = 0; i < 12; ++i) {
+                    const f32x4_t v = t[i];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) cst[(i * 4 + e) / 6][(i * 4 + e) % 6] = v[e];
+                }
+                n_cst = tc.n;
+            }
+            const bool full = tc.d0 + TD <= p.D && tc.h0 + TH <= p.H && tc.w0 + TW <= p.W;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float xv[8], dv[8], o[8];
+                Chunk<bf16_t>::unpack(yr[j], xv);
+                Chunk<bf16_t>::unpack(dr[j], dv);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float dz = norm_bwd_dz(norm_preact(xv[e], cst[e][2], cst[e][3]), dv[e], p.slope);
+                    o[e] = norm_bwd_dx(xv[e], dz, cst[e][0], cst[e][1], cst[e][2], cst[e][4], cst[e][5]);
+                }
+                u32x4_t pk = chunk_pack_bf16(o);
+                if (!(ch_ok_t && slot_ok(tc, j, full))) pk = u32x4_t{0u, 0u, 0u, 0u};
+                *(u32x4_t*)(smem + buf * BUF_BYTES + (wave + 4 * j) * 1024 + lane * 16) = pk;
+            }
+        }
+    };
+
     // MFMA operands (v_mfma_f32_32x32x16_bf16): A = dy^T: lane l holds voxels 8*(l>>5).. of cout l & 31 (transposing
     // reads as in conv3d_k3_wgrad_pp.hip); B: lane l holds voxels 8*(l>>5).. of tap l & 31 = one 16-byte read.
     const int G = lane >> 4, qr = (lane >> 2) & 3, pc = lane & 3;
@@ -263,6 +348,7 @@ __global__ __launch_bounds__(W_THREADS) void stem_wgrad_kernel(const StemWgParam
     if (sc.n_my > 0) {
         load_tile(sc.tile(0), 0);
         commit_x(0);
+        commit_dy(sc.tile(0), 0);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -280,7 +366,10 @@ __global__ __launch_bounds__(W_THREADS) void stem_wgrad_kernel(const StemWgParam
             if (!tap_ok) bfr = u32x4_t{0u, 0u, 0u, 0u};
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, af), __builtin_bit_cast(bf16x8_t, bfr), acc, 0, 0, 0);
         }
-        if (k + 1 < sc.n_my) commit_x(buf ^ 1);
+        if (k + 1 < sc.n_my) {
+            commit_x(buf ^ 1);
+            commit_dy(sc.tile(k + 1), buf ^ 1);
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
@@ -331,10 +420,19 @@ int msseg_stem_wgrad_grid(const StemWgParams& p) {
 }
 
 int msseg_stem_wgrad_launch(const StemWgParams& p, int gx, hipStream_t stream) {
-    const int lds = 2 * (P_BYTES + 3 * XS_ELEMS * 2 + 64);
+    if (p.yraw != nullptr) {   // the tile is formed from (yraw, da) as it is staged
+        if (p.N > WG_NMAX) MSSEG_FAIL(MSSEG_EINVAL, "stem_wgrad: the fused backward apply needs N <= %d", WG_NMAX);
+        const int lds = 2 * WG_BUF_BYTES + WG_TAB_BYTES;
+        static msseg_lds_attr_once attr_in;
+        if (!attr_in.ensure((const void*)stem_wgrad_kernel<true>, lds)) MSSEG_FAIL(MSSEG_ELAUNCH, "stem_wgrad: cannot set dynamic LDS size %d", lds);
+        hipLaunchKernelGGL(stem_wgrad_kernel<true>, dim3(gx, ceil_div(p.M, 32)), dim3(W_THREADS), lds, stream, p);
+        MSSEG_CHECK_LAUNCH("stem_wgrad_inbwd");
+        return MSSEG_OK;
+    }
+    const int lds = 2 * WG_BUF_BYTES;
     static msseg_lds_attr_once attr;
-    if (!attr.ensure((const void*)stem_wgrad_kernel, lds)) MSSEG_FAIL(MSSEG_ELAUNCH, "stem_wgrad: cannot set dynamic LDS size %d", lds);
-    hipLaunchKernelGGL(stem_wgrad_kernel, dim3(gx, ceil_div(p.M, 32)), dim3(W_THREADS), lds, stream, p);
+    if (!attr.ensure((const void*)stem_wgrad_kernel<false>, lds)) MSSEG_FAIL(MSSEG_ELAUNCH, "stem_wgrad: cannot set dynamic LDS size %d", lds);
+    hipLaunchKernelGGL(stem_wgrad_kernel<false>, dim3(gx, ceil_div(p.M, 32)), dim3(W_THREADS), lds, stream, p);
     MSSEG_CHECK_LAUNCH("stem_wgrad");
     return MSSEG_OK;
 }

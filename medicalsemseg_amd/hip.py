@@ -101,6 +101,7 @@ SIGNATURES = {
     "msseg_conv3d_k3_wgrad_kernel": ([_i, _i, _i, _i, _i, _i, _i], _i),
     "msseg_conv3d_k3_wgrad": ([_vp, _ll, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp], _i),
     "msseg_conv3d_k1_wgrad": ([_vp, _ll, _vp, _ll, _vp, _ll, _i, _i, _i, _vp, _sz, _i, _vp], _i),
+    "msseg_conv3d_stem_wgrad_inbwd": ([_vp, _ll, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _f, _f, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp], _i),
     "msseg_conv3d_gather_wgrad": ([_vp, _ll, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp], _i),
     "msseg_deconv_k2s2_wgrad": ([_vp, _ll, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp], _i),
     "msseg_deconv_k4s4_wgrad": ([_vp, _ll, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp], _i),
@@ -110,6 +111,7 @@ SIGNATURES = {
                                            _i, _i, _i, _i, _i, _f, _f, _vp, _sz, _i, _vp], _i),
     "msseg_instnorm_act_pool_fwd": ([_vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _i, _i, _i, _i, _i, _f, _f, _i, _vp], _i),
     "msseg_instnorm_act_bwd_reduce": ([_vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _i, _i, _ll, _i, _f, _f, _vp, _sz, _i, _vp], _i),
+    "msseg_instnorm_act_bwd_apply_head": ([_vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _i, _vp, _vp, _ll, _i, _ll, _i, _f, _f, _i, _vp], _i),
     "msseg_instnorm_act_bwd_apply": ([_vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _ll, _vp, _ll, _i, _ll, _i, _f, _f, _i, _vp], _i),
     "msseg_maxpool2_fwd": ([_vp, _ll, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp], _i),
     "msseg_maxpool2_bwd": ([_vp, _ll, _vp, _ll, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
@@ -667,13 +669,14 @@ def conv3d_k1_head_norm(yraw, stats, gamma, beta, slope, eps, w, bias, y, cin, c
 
 def conv3d_k1_head_bwd_fused(dy, w, da, cin, cout, yraw, fwd_stats, gamma, beta, slope, eps, dw, dw_accumulate,
                              dgamma=None, dbeta=None, accumulate=False):
-    """conv3d_k1_head_dgrad_inbwd + the head's weight gradient dw[cout][cin] from the recomputed activation"""
+    """conv3d_k1_head_dgrad_inbwd + the head's weight gradient dw[cout][cin] from the recomputed activation.
+    da None: the input gradient is not stored (the sums and dw are the same bits); instnorm_act_bwd_apply_head forms it again"""
     _need_gpu(dy, w, da, yraw, fwd_stats, dw)
     N = dy.shape[0]
     S = dy.numel() // dy.shape[-1] // N
     red = torch.empty(N, cin, 2, dtype=torch.float32, device=dy.device)
     sc = scratch(dy.device)
-    _ck(lib().msseg_conv3d_k1_head_bwd_fused(_p(dy), ld(dy), _p(w), _p(da), ld(da), N, S, cin, cout, _p(yraw), ld(yraw),
+    _ck(lib().msseg_conv3d_k1_head_bwd_fused(_p(dy), ld(dy), _p(w), _p(da), ld(da) if da is not None else 0, N, S, cin, cout, _p(yraw), ld(yraw),
                                              _p(fwd_stats), _p(gamma), _p(beta), slope, eps, _p(red), _p(dgamma),
                                              _p(dbeta), int(accumulate), _p(dw), int(dw_accumulate), _p(sc), sc.numel(),
                                              dt(dy), _stream()), "conv3d_k1_head_bwd_fused")
@@ -867,6 +870,28 @@ def conv3d_gather_wgrad(x, dy, dw, cin, cout, k, s, p, accumulate=False):
     ws = _wg_ws(cout, 1, cin * k ** 3, x.device)
     _ck(lib().msseg_conv3d_gather_wgrad(_p(x), ld(x), _p(dy), ld(dy), _p(dw), N, D, H, W, cin, cout, k, s, p,
                                         int(accumulate), _p(ws), ws.numel(), dt(x), _stream()), "conv3d_gather_wgrad")
+
+
+def conv3d_stem_wgrad_inbwd_ok(x, y_raw, da, cout) -> bool:
+    """can conv3d_stem_wgrad_inbwd take these operands (the one-channel stem kernels, 16-byte channel chunks, N <= 8)?"""
+    return bool(x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] == 1 and x.shape[0] <= 8
+                and (cout % 32 == 0 or cout % 48 == 0) and cout <= 256
+                and all(ld(t) % 8 == 0 and t.data_ptr() % 16 == 0 for t in (y_raw, da)))
+
+
+def conv3d_stem_wgrad_inbwd(x, y_raw, da, stats, red, gamma, beta, slope, eps, dw, cout, k=3, accumulate=False):
+    """dw (+)= weight gradient of the one-input-channel conv (k 3 p 1, or k 1) from dy = the InstanceNorm + LeakyReLU backward
+    apply of (y_raw, da, red), which is formed inside the kernel and never stored: the bits of instnorm_act_bwd_apply into a
+    tensor followed by conv3d_gather_wgrad"""
+    _need_gpu(x, y_raw, da, stats, red, dw)
+    N, D, H, W = x.shape[:4]
+    ws = _wg_ws(cout, 1, k ** 3, x.device)
+    nv = N * D * H * W
+    TIMER.launch("conv3d_stem_wgrad_inbwd", 2.0 * nv * cout * 27, nv * (2 * cout + 1) * 2 + cout * k ** 3 * 4,
+                 lambda: _ck(lib().msseg_conv3d_stem_wgrad_inbwd(_p(x), ld(x), _p(y_raw), ld(y_raw), _p(da), ld(da), _p(stats),
+                                                                 _p(red), _p(gamma), _p(beta), eps, slope, _p(dw), N, D, H, W,
+                                                                 cout, k, int(accumulate), _p(ws), ws.numel(), dt(x),
+                                                                 _stream()), "conv3d_stem_wgrad_inbwd"))
 
 
 def deconv_k2s2_wgrad(x, dy, dw, cin, cout, accumulate=False):
@@ -1134,6 +1159,19 @@ def instnorm_act_bwd_apply(x, stats, gamma, y, dy, red, dx, slope, eps=1e-5, dre
                                            _p(dx), ld(dx), _p(dres), ld(dres) if dres is not None else 0, N, S, Cc, eps,
                                            slope, dt(x), _stream()), "instnorm_act_bwd_apply"))
     return red
+
+
+def instnorm_act_bwd_apply_head(x, stats, gamma, beta, dl, w, cout, red, dx, slope, eps=1e-5):
+    """instnorm_act_bwd_apply (y None, no dres) with the gradient of the activation formed from the class gradient rows dl
+    ([..., 16 bytes]) and the head's weight w (fp32 [cout, C]) instead of read from a tensor: the bits of the plain apply fed
+    with the da that conv3d_k1_head_bwd_fused stores"""
+    _need_gpu(x, stats, dl, w, red, dx)
+    N, S, Cc = _nsc(x)
+    TIMER.launch("instnorm_act_bwd_apply_head", 8.0 * N * S * Cc, _nbytes(x, dl, dx),
+                 lambda: _ck(lib().msseg_instnorm_act_bwd_apply_head(_p(x), ld(x), _p(stats), _p(gamma), _p(beta), _p(dl), ld(dl),
+                                                                     _p(w), cout, _p(red), _p(dx), ld(dx), N, S, Cc, eps, slope,
+                                                                     dt(x), _stream()), "instnorm_act_bwd_apply_head"))
+    return dx
 
 
 def maxpool2_fwd(x, y):

@@ -140,6 +140,14 @@ class _Applied:
 APPLIED = _Applied()
 
 
+class HeadGrad:
+    """Stands for the input gradient of the <= 4-class output conv where it was not stored (Conv1.bwd_norm, deferred form):
+    the class gradient rows and the weight it is formed from again inside the receiving unit's backward apply"""
+
+    def __init__(self, dl, w, cout):
+        self.dl, self.w, self.cout = dl, w, cout
+
+
 def _grad_buf(p: torch.nn.Parameter):
     """(tensor to write the gradient into, accumulate?)
 
@@ -296,17 +304,7 @@ class Conv3:
                 hip.conv3d_gather_wgrad(x, dy, g, self.cin, self.cout, 3, 1, 1, acc)
             else:
                 hip.conv3d_k3_wgrad(x, dy, g, self.cin, self.cout, acc)
-        if self.b is not None and self.b.requires_grad:
-            g, acc = _grad_buf(self.b)
-            if bias_grad_is_zero:
-                # a bias feeding InstanceNorm: d loss / d bias == 0 identically (the mean subtraction removes it);
-                # dy sums to zero over every (n, c) by construction of the InstanceNorm backward
-                # (with a lazily zeroed buffer the fill runs once: nothing else ever writes this gradient)
-                if not acc and not getattr(self.b, "_msseg_grad_is_zero", False):
-                    g.zero_()
-                    self.b._msseg_grad_is_zero = getattr(self.b, "_msseg_gowner", None) is not None
-            else:
-                hip.channel_sum(dy, g, acc)
+        self._bwd_bias(dy, bias_grad_is_zero)
         if not need_dx:
             return None
         if self._gather(dtype):
@@ -345,6 +343,34 @@ class Conv3:
             return dx, None
         hip.conv3d_k3(dy, wp, None, dx, self.cout, self.cin)
         return dx
+
+    def _bwd_bias(self, dy, bias_grad_is_zero):
+        if self.b is not None and self.b.requires_grad:
+            g, acc = _grad_buf(self.b)
+            if bias_grad_is_zero:
+                # a bias feeding InstanceNorm: d loss / d bias == 0 identically (the mean subtraction removes it);
+                # dy sums to zero over every (n, c) by construction of the InstanceNorm backward
+                # (with a lazily zeroed buffer the fill runs once: nothing else ever writes this gradient)
+                if not acc and not getattr(self.b, "_msseg_grad_is_zero", False):
+                    g.zero_()
+                    self.b._msseg_grad_is_zero = getattr(self.b, "_msseg_gowner", None) is not None
+            else:
+                hip.channel_sum(dy, g, acc)
+
+    def stem_inbwd_ok(self, x, y_raw, da) -> bool:
+        """the one-input-channel conv on the stem kernels: can its weight gradient apply the InstanceNorm backward of the unit
+        it heads while it loads its operand (conv3d_stem_wgrad_inbwd), so that the conv's output gradient is never written?"""
+        return (self.cin == 1 and y_raw is not None and isinstance(da, torch.Tensor) and not os.environ.get("MSSEG_NO_STEM_INBWD")
+                and hip.conv3d_stem_wgrad_inbwd_ok(x, y_raw, da, self.cout))
+
+    def bwd_stem_inbwd(self, x, y_raw, stats, da, red, norm):
+        """backward of the stem conv of a conv + InstanceNorm + LeakyReLU unit whose input gradient is not needed, from the
+        gradient da of the unit's activation and its backward sums red: the unit's dy exists only inside the kernel"""
+        if self.w.requires_grad:
+            g, acc = _grad_buf(self.w)
+            hip.conv3d_stem_wgrad_inbwd(x, y_raw, da, stats, red, norm.gamma, norm.beta, norm.slope, norm.eps, g, self.cout,
+                                        3, acc)
+        self._bwd_bias(None, True)
 
 
 class Conv1:
@@ -396,7 +422,10 @@ class Conv1:
     def bwd_norm(self, dy, dy_channels, nrm, yraw, stats):
         """backward of fwd_norm: returns (da, red) for the unit's `bwd(..., red=red)`; weight / bias gradients land in .grad"""
         dyk = dy[..., :dy_channels]
-        dx = torch.empty(yraw.shape, dtype=yraw.dtype, device=yraw.device)
+        # deferred form: the input gradient (three multiply-adds per element from a 16-byte row) is not written here and
+        # read back by the unit's backward apply, which forms it again (InstNormAct.bwd takes the HeadGrad in its place)
+        defer = self.w.requires_grad and not os.environ.get("MSSEG_NO_HEAD_DEFER")
+        dx = None if defer else torch.empty(yraw.shape, dtype=yraw.dtype, device=yraw.device)
         dg, db, acc = _norm_grad_bufs(nrm)
         if self.b is not None and self.b.requires_grad:
             g, bacc = _grad_buf(self.b)
@@ -408,7 +437,7 @@ class Conv1:
         else:
             red = hip.conv3d_k1_head_dgrad_inbwd(dyk, self.w.detach(), dx, self.cin, self.cout, yraw, stats, nrm.gamma,
                                                  nrm.beta, nrm.slope, nrm.eps, dg, db, acc)
-        return dx, red
+        return (HeadGrad(dyk, self.w.detach(), self.cout) if defer else dx), red
 
     def bwd(self, x, dy, need_dx=True, dy_channels=None, next_norm=None):
         """dy may carry zero-padded channels (dy_channels = padded count, multiple of 8).
@@ -586,6 +615,11 @@ class InstNormAct:
                 raise RuntimeError("a residual unit cannot take an already-applied gradient")
             return da
         dy = torch.empty(y_raw.shape, dtype=y_raw.dtype, device=y_raw.device)
+        if isinstance(da, HeadGrad):
+            if want_dres or not isinstance(red, torch.Tensor):
+                raise RuntimeError("a deferred head gradient needs the backward sums and a unit without residual")
+            return hip.instnorm_act_bwd_apply_head(y_raw, stats, self.gamma, self.beta, da.dl, da.w, da.cout, red, dy,
+                                                   self.slope, self.eps)
         dres = torch.empty(y_raw.shape, dtype=y_raw.dtype, device=y_raw.device) if want_dres else None
         # without a residual the sign of the pre-activation is recomputed from y_raw: one tensor read less
         a_in = a if want_dres else None
@@ -641,6 +675,10 @@ class ConvNormAct:
         next_cna/next_saved: the ConvNormAct (and its saved tuple) whose activation is this conv's input; when given
         the result is (dx, red_for_that_layer)."""
         x, y, stats, a = saved
+        if not need_dx and isinstance(red, torch.Tensor) and self.conv.stem_inbwd_ok(x, y, da):
+            # the stem unit: dy is consumed by the weight gradient alone, which forms it from (y, da, red) as it loads
+            self.conv.bwd_stem_inbwd(x, y, stats, da, red, self.norm)
+            return None
         dy = self.norm.bwd(y, stats, a, da, red=red)
         if next_cna is not None and need_dx:
             nx, ny, nstats, na = next_saved
@@ -702,8 +740,12 @@ class ResBlock:
         x, y1, s1, a1, y2, s2, y3, s3, r, o = saved
         dy2, dres = self.n2.bwd(y2, s2, o, do, want_dres=True)
         da1, red1 = self.c2.bwd(a1, dy2, True, next_norm=(self.n1, y1, s1, a1))
-        dy1 = self.n1.bwd(y1, s1, a1, da1, red=red1)
-        if need_dx and self.c1.dgrad_accumulate_ok(dy1):
+        if not need_dx and isinstance(red1, torch.Tensor) and self.c1.stem_inbwd_ok(x, y1, da1):
+            dy1 = None   # the one-channel first conv: its weight gradient forms dy1 from (y1, da1, red1) as it loads
+            self.c1.bwd_stem_inbwd(x, y1, s1, da1, red1, self.n1)
+        else:
+            dy1 = self.n1.bwd(y1, s1, a1, da1, red=red1)
+        if dy1 is not None and need_dx and self.c1.dgrad_accumulate_ok(dy1):
             # large grids (Swin-UNETR's 96^3 / 48^3 UnetResBlocks): the gradient of the shortcut first, then the first conv's
             # input gradient is added onto it by that kernel's epilogue -- no separate add pass over the (up to 96-channel)
             # input gradient (3 x 340 MB at 96^3, batch 2)
@@ -713,7 +755,7 @@ class ResBlock:
             else:
                 dx3 = dres
             return self.c1.bwd(x, dy1, True, dx_out=dx3, accumulate_dx=True)
-        dx = self.c1.bwd(x, dy1, need_dx)
+        dx = self.c1.bwd(x, dy1, need_dx) if dy1 is not None else None
         if self.c3 is not None:
             dy3 = self.n3.bwd(y3, s3, r, dres)
             dx3 = self.c3.bwd(x, dy3, need_dx)
