@@ -631,6 +631,23 @@ int msseg_sw_gather_batch(const float* vol, long long vol_bstride, void* win, lo
 int msseg_sw_blend_batch(const void* win, long long ldw, int dtype, const float* imp, float* out, long long out_bstride,
                          float* cnt, long long cnt_bstride, const int* table, int nwin, int C, int VD, int VH, int VW,
                          int RD, int RH, int RW, msseg_stream_t stream);
+/* The same two launches with a mirror mask per table row (mirror test-time augmentation: a (window, mask) pair is one
+ * more row).  flips: device int32 [nwin], bit 0 / 1 / 2 set = row j is mirrored along D / H / W; null = no row is
+ * mirrored, which is exactly the two calls above (they forward here).  With f(r) = R - 1 - r on a mirrored axis of
+ * extent R and f(r) = r otherwise:
+ * gather: win[j][rz][ry][rx] = vol[b][z0 + fz(rz)][y0 + fy(ry)][x0 + fx(rx)], `cval` outside -- the window as above,
+ *         flipped along the mirrored axes.
+ * blend : out[b][c][z0+dz][y0+dy][x0+dx] += imp[dz][dy][dx] * win[j][c][fz(dz)][fy(dy)][fx(dx)], cnt += imp[dz][dy][dx]:
+ *         the logits are un-mirrored on the way in, the weight is NOT mirrored (it is indexed in volume orientation;
+ *         the Gaussian map of an even extent peaks at R / 2 and is not symmetric).  Order and roundings as above;
+ *         rows of one start under several masks overlap completely.  RD, RH, RW are independent, even or odd. */
+int msseg_sw_gather_batch_mirror(const float* vol, long long vol_bstride, void* win, long long ldw, int dtype,
+                                 const int* table, const int* flips, int nwin, int C, int VD, int VH, int VW, int RD,
+                                 int RH, int RW, float cval, msseg_stream_t stream);
+int msseg_sw_blend_batch_mirror(const void* win, long long ldw, int dtype, const float* imp, float* out,
+                                long long out_bstride, float* cnt, long long cnt_bstride, const int* table,
+                                const int* flips, int nwin, int C, int VD, int VH, int VW, int RD, int RH, int RW,
+                                msseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Layout passes of the vendored MONAI Swin-UNETR encoder (csrc/layout.hip; /root/reference/models/segmentors/

@@ -397,19 +397,24 @@ __global__ void sw_normalize_kernel(float* out, const float* cnt, int C, long lo
 
 // ---- batched forms: one launch per window batch, window starts in a device-resident table ----------------
 // table[j] = (b, z0, y0, x0); b < 0 marks an unused slot (short last batch).
+// flips[j] (nullable = 0): bit 0 / 1 / 2 mirrors window j along D / H / W -- window voxel r is volume voxel
+// start + (R - 1 - r) on a mirrored axis.  Only the voxel index changes: the window is written in its own order, the
+// volume row of a W-mirrored window is read as a descending contiguous run.
 template <typename T>
 __global__ void sw_gather_batch_kernel(const float* __restrict__ vol, long long vol_bstride, T* __restrict__ win,
-                                       long long ldw, const int* __restrict__ table, int nwin, int C, int VD, int VH,
-                                       int VW, int RD, int RH, int RW, float cval) {
+                                       long long ldw, const int* __restrict__ table, const int* __restrict__ flips,
+                                       int nwin, int C, int VD, int VH, int VW, int RD, int RH, int RW, float cval) {
     const long long R = (long long)RD * RH * RW, V = (long long)VD * VH * VW;
     const int j = blockIdx.y;
     const int b = table[j * 4 + 0];
     if (b < 0) return;
     const int z0 = table[j * 4 + 1], y0 = table[j * 4 + 2], x0 = table[j * 4 + 3];
+    const int m = flips ? flips[j] : 0;
     const float* vb = vol + (long long)b * vol_bstride;
     for (long long ri = blockIdx.x * 256LL + threadIdx.x; ri < R; ri += (long long)gridDim.x * 256) {
         const int rx = (int)(ri % RW), ry = (int)((ri / RW) % RH), rz = (int)(ri / ((long long)RW * RH));
-        const int z = z0 + rz, y = y0 + ry, x = x0 + rx;
+        const int z = z0 + ((m & 1) ? RD - 1 - rz : rz), y = y0 + ((m & 2) ? RH - 1 - ry : ry),
+                  x = x0 + ((m & 4) ? RW - 1 - rx : rx);
         const bool in = (unsigned)z < (unsigned)VD && (unsigned)y < (unsigned)VH && (unsigned)x < (unsigned)VW;
         const long long v = ((long long)z * VH + y) * VW + x;
         for (int c = 0; c < C; ++c) {
@@ -424,16 +429,21 @@ __global__ void sw_gather_batch_kernel(const float* __restrict__ vol, long long 
 // order) that covers it -- which then adds the contributions of all windows of the batch covering that voxel, in
 // table order, with the reference's two roundings per window (mul, then add): the same fp32 sequence as
 // `out[idx] += imp * seg` executed window after window (/root/reference/engine/utils.py:146-148).
+// flips[k] (nullable = 0; bits as in the gather): the logits of window k are read at the mirrored window index, the
+// weight at the un-mirrored one -- `imp` lives in volume orientation (an even ROI's Gaussian peaks at R / 2 and is not
+// symmetric).  Rows of one start under several masks cover the same voxels; the owner rule needs nothing new for them.
 template <typename T, int CMAX>
 __global__ __launch_bounds__(256) void sw_blend_batch_kernel(const T* __restrict__ win, long long ldw,
                                                              const float* __restrict__ imp, float* __restrict__ out,
                                                              long long out_bstride, float* __restrict__ cnt,
                                                              long long cnt_bstride, const int* __restrict__ table,
-                                                             int nwin, int C, int VD, int VH, int VW, int RD, int RH,
-                                                             int RW) {
+                                                             const int* __restrict__ flips, int nwin, int C, int VD,
+                                                             int VH, int VW, int RD, int RH, int RW) {
 #pragma clang fp contract(off)
     __shared__ int tab[256 * 4];
+    __shared__ int flp[256];
     for (int i = threadIdx.x; i < nwin * 4; i += 256) tab[i] = table[i];
+    if ((int)threadIdx.x < nwin) flp[threadIdx.x] = flips ? flips[threadIdx.x] : 0;
     __syncthreads();
     const long long R = (long long)RD * RH * RW, V = (long long)VD * VH * VW;
     const bool vecw = ldw > 0 && ldw * (long long)sizeof(T) == 16 && C <= DT<T>::EPC && (((uintptr_t)win) & 15) == 0;
@@ -466,14 +476,18 @@ __global__ __launch_bounds__(256) void sw_blend_batch_kernel(const T* __restrict
             if (dz >= (unsigned)RD || dy >= (unsigned)RH || dx >= (unsigned)RW) continue;
             const long long pi = ((long long)dz * RH + dy) * RW + dx;
             const float w = imp[pi];
+            const int m = flp[k];
+            const unsigned sz = (m & 1) ? RD - 1 - dz : dz, sy = (m & 2) ? RH - 1 - dy : dy,
+                           sx = (m & 4) ? RW - 1 - dx : dx;
+            const long long si = ((long long)sz * RH + sy) * RW + sx;    // the logits' voxel; == pi without a mask
             float vals[CMAX];
             if (vecw) {   // 16-byte logits rows (the networks' channels-last logits): one load per (voxel, window)
-                unpack_row<T, CMAX>(*(const u32x4_t*)(win + ((long long)k * R + pi) * ldw), C, vals);
+                unpack_row<T, CMAX>(*(const u32x4_t*)(win + ((long long)k * R + si) * ldw), C, vals);
             } else {
 #pragma unroll
                 for (int c = 0; c < CMAX; ++c)
-                    vals[c] = c < C ? (ldw > 0 ? DT<T>::ld(win + ((long long)k * R + pi) * ldw + c)
-                                               : DT<T>::ld(win + ((long long)k * C + c) * R + pi)) : 0.f;
+                    vals[c] = c < C ? (ldw > 0 ? DT<T>::ld(win + ((long long)k * R + si) * ldw + c)
+                                               : DT<T>::ld(win + ((long long)k * C + c) * R + si)) : 0.f;
             }
 #pragma unroll
             for (int c = 0; c < CMAX; ++c) {
@@ -493,13 +507,13 @@ __global__ __launch_bounds__(256) void sw_blend_batch_kernel(const T* __restrict
 
 template <typename T, int CMAX>
 int launch_blend_batch(const void* win, long long ldw, const float* imp, float* out, long long obs, float* cnt,
-                              long long cbs, const int* table, int nwin, int C, int VD, int VH, int VW, int RD, int RH,
-                              int RW, hipStream_t st) {
+                              long long cbs, const int* table, const int* flips, int nwin, int C, int VD, int VH, int VW,
+                              int RD, int RH, int RW, hipStream_t st) {
     const long long R = (long long)RD * RH * RW;
     long long gx = ceil_div_ll(R, 256);
     if (gx > 65535) gx = 65535;
     hipLaunchKernelGGL((sw_blend_batch_kernel<T, CMAX>), dim3((unsigned)gx, nwin), dim3(256), 0, st, (const T*)win, ldw,
-                       imp, out, obs, cnt, cbs, table, nwin, C, VD, VH, VW, RD, RH, RW);
+                       imp, out, obs, cnt, cbs, table, flips, nwin, C, VD, VH, VW, RD, RH, RW);
     MSSEG_CHECK_LAUNCH("sw_blend_batch");
     return MSSEG_OK;
 }
@@ -653,21 +667,29 @@ int msseg_sw_normalize(float* out, const float* cnt, int C, long long V, msseg_s
     return MSSEG_OK;
 }
 
-int msseg_sw_blend_batch(const void* win, long long ldw, int dtype, const float* imp, float* out, long long out_bstride,
-                         float* cnt, long long cnt_bstride, const int* table, int nwin, int C, int VD, int VH, int VW,
-                         int RD, int RH, int RW, msseg_stream_t stream) {
+int msseg_sw_blend_batch_mirror(const void* win, long long ldw, int dtype, const float* imp, float* out,
+                                long long out_bstride, float* cnt, long long cnt_bstride, const int* table,
+                                const int* flips, int nwin, int C, int VD, int VH, int VW, int RD, int RH, int RW,
+                                msseg_stream_t stream) {
     if (!win || !imp || !out || !cnt || !table) MSSEG_FAIL(MSSEG_EINVAL, "sw_blend_batch: null pointer");
     if (nwin < 1 || nwin > 256) MSSEG_FAIL(MSSEG_EINVAL, "sw_blend_batch: 1 <= nwin <= 256 windows per launch (got %d)", nwin);
     if (C < 1 || C > 16) MSSEG_FAIL(MSSEG_EINVAL, "sw_blend_batch: 1 <= C <= 16 classes");
     if (RD < 1 || RH < 1 || RW < 1 || RD > VD || RH > VH || RW > VW)
         MSSEG_FAIL(MSSEG_EINVAL, "sw_blend_batch: roi (%d,%d,%d) does not fit the volume (%d,%d,%d)", RD, RH, RW, VD, VH, VW);
-    DISPATCH_TC(dtype, C, launch_blend_batch, win, ldw, imp, out, out_bstride, cnt, cnt_bstride, table, nwin, C, VD, VH,
-                VW, RD, RH, RW, (hipStream_t)stream);
+    DISPATCH_TC(dtype, C, launch_blend_batch, win, ldw, imp, out, out_bstride, cnt, cnt_bstride, table, flips, nwin, C,
+                VD, VH, VW, RD, RH, RW, (hipStream_t)stream);
 }
 
-int msseg_sw_gather_batch(const float* vol, long long vol_bstride, void* win, long long ldw, int dtype, const int* table,
-                          int nwin, int C, int VD, int VH, int VW, int RD, int RH, int RW, float cval,
-                          msseg_stream_t stream) {
+int msseg_sw_blend_batch(const void* win, long long ldw, int dtype, const float* imp, float* out, long long out_bstride,
+                         float* cnt, long long cnt_bstride, const int* table, int nwin, int C, int VD, int VH, int VW,
+                         int RD, int RH, int RW, msseg_stream_t stream) {
+    return msseg_sw_blend_batch_mirror(win, ldw, dtype, imp, out, out_bstride, cnt, cnt_bstride, table, nullptr, nwin, C,
+                                       VD, VH, VW, RD, RH, RW, stream);
+}
+
+int msseg_sw_gather_batch_mirror(const float* vol, long long vol_bstride, void* win, long long ldw, int dtype,
+                                 const int* table, const int* flips, int nwin, int C, int VD, int VH, int VW, int RD,
+                                 int RH, int RW, float cval, msseg_stream_t stream) {
     if (!vol || !win || !table) MSSEG_FAIL(MSSEG_EINVAL, "sw_gather_batch: null pointer");
     if (nwin < 1 || nwin > 65535 || C < 1) MSSEG_FAIL(MSSEG_EINVAL, "sw_gather_batch: bad window / channel count");
     if (ldw != 0 && ldw < C) MSSEG_FAIL(MSSEG_EINVAL, "sw_gather_batch: ldw smaller than the channel count");
@@ -677,11 +699,18 @@ int msseg_sw_gather_batch(const float* vol, long long vol_bstride, void* win, lo
     const bool known = for_dtype(dtype, [&](auto t) {
         using T = typename decltype(t)::type;
         hipLaunchKernelGGL(sw_gather_batch_kernel<T>, dim3((unsigned)gx, nwin), dim3(256), 0, (hipStream_t)stream, vol,
-                           vol_bstride, (T*)win, ldw, table, nwin, C, VD, VH, VW, RD, RH, RW, cval);
+                           vol_bstride, (T*)win, ldw, table, flips, nwin, C, VD, VH, VW, RD, RH, RW, cval);
     });
     if (!known) MSSEG_FAIL(MSSEG_EINVAL, "sw_gather_batch: bad dtype");
     MSSEG_CHECK_LAUNCH("sw_gather_batch");
     return MSSEG_OK;
+}
+
+int msseg_sw_gather_batch(const float* vol, long long vol_bstride, void* win, long long ldw, int dtype, const int* table,
+                          int nwin, int C, int VD, int VH, int VW, int RD, int RH, int RW, float cval,
+                          msseg_stream_t stream) {
+    return msseg_sw_gather_batch_mirror(vol, vol_bstride, win, ldw, dtype, table, nullptr, nwin, C, VD, VH, VW, RD, RH,
+                                        RW, cval, stream);
 }
 
 }  // extern "C"

@@ -91,7 +91,8 @@ def eval_model(inferer, model, data_loader, criterion, device, cfg, log_writer=N
         with torch.no_grad():
             if inferer is None:
                 outputs = sliding_window_inference(inputs, aff_xyz, cfg.vol_size, cfg.batch_size_val, model,
-                                                   overlap=cfg.val_infer_overlap, mode="gaussian")
+                                                   overlap=cfg.val_infer_overlap, mode="gaussian",
+                                                   mirror_axes=getattr(cfg, "infer_mirror_axes", ()))
             else:
                 # the reference hands the bare module to MONAI's inferer, which feeds it a bare window tensor (the models
                 # want the (window, centers, affine) tuple: SURVEY.md M4); an inferer that already builds the tuple passes
@@ -126,7 +127,8 @@ def test_model(model, data_loader, device, cfg, log_writer=None):
         img_name = os.path.split(str(batch["image_meta_dict"]["filename_or_obj"][0]))[-1].split("img")[-1]
         with torch.no_grad():
             outputs = sliding_window_inference(inputs, aff_xyz, cfg.vol_size, cfg.batch_size_val, model,
-                                               overlap=cfg.val_infer_overlap, mode="gaussian", cval=air_cval)
+                                               overlap=cfg.val_infer_overlap, mode="gaussian", cval=air_cval,
+                                               mirror_axes=getattr(cfg, "infer_mirror_axes", ()))
         seg = label_map(outputs)
         if post_enabled(cfg):
             only_largest = not (int(getattr(cfg, "post_min_size", 0)) > 1 or getattr(cfg, "post_fill_holes", False))

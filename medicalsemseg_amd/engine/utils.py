@@ -9,7 +9,9 @@ normalise are HIP kernels (``msseg_sw_gather_batch/_blend_batch/_normalize``); t
 ``classes`` identical ones; under ``torch.distributed`` the accumulators are updated batch by batch (memory O(volume), like the reference); with
 ``shard_ranks=True`` window batches are dealt round-robin to the ranks and each step's logits are exchanged with one
 all-gather, after which every rank blends the step's windows in the reference order (bit-identical to the single-GPU
-result).
+result).  An addition of this build: ``mirror_axes`` (``--infer_mirror_axes``) predicts every window under each flip
+combination of the given axes and blends the un-mirrored logits of all of them -- the flips are index changes inside the
+gather and blend kernels (``msseg_sw_gather_batch_mirror/_blend_batch_mirror``), nothing else in the loop changes.
 """
 from __future__ import annotations
 
@@ -101,6 +103,31 @@ def importance_map(patch_size: Sequence[int], mode="constant", sigma_scale=0.125
     return imp.to(device) if device is not None else imp
 
 
+def mirror_axes_tuple(axes) -> Tuple[int, ...]:
+    """`--infer_mirror_axes` as a tuple of distinct volume axes: accepts (), an int or a sequence of ints out of
+    0 = D, 1 = H, 2 = W (the three forms the flag takes after `collapse_lists`)."""
+    if isinstance(axes, int):
+        axes = (axes,)
+    try:
+        axes = tuple(axes)
+    except TypeError:
+        raise ValueError(f"--infer_mirror_axes: expected axes out of 0, 1, 2, got {axes!r}") from None
+    for a in axes:
+        if isinstance(a, bool) or not isinstance(a, int) or a not in (0, 1, 2):
+            raise ValueError(f"--infer_mirror_axes: axes are 0 (D), 1 (H) or 2 (W), got {a!r}")
+    if len(set(axes)) != len(axes):
+        raise ValueError(f"--infer_mirror_axes: duplicate axis in {axes}")
+    return axes
+
+
+def mirror_masks(axes) -> Tuple[int, ...]:
+    """the flip masks of mirror test-time augmentation over `axes`: every subset as an integer with bit a set when
+    axis a is flipped, in increasing order (the identity 0 first); 1, 2, 4 or 8 masks."""
+    axes = mirror_axes_tuple(axes)
+    return tuple(sorted(sum(1 << a for a in sub) for n in range(len(axes) + 1)
+                        for sub in itertools.combinations(axes, n)))
+
+
 class _GraphedInfer:
     """`seg = predictor.infer_cl(win)` on a static batch of channels-last windows, replayed from a captured hipGraph
     (models that declare `graph_safe` -- static shapes, no host synchronisation -- and offer `infer_cl`: channels-last
@@ -143,8 +170,16 @@ class _GraphedInfer:
 def sliding_window_inference(inputs: torch.Tensor, affine, roi_size, sw_batch_size: int, predictor: Callable,
                              overlap: float = 0.25, mode: str = "constant", sigma_scale=0.125,
                              padding_mode: str = "constant", cval: float = 0.0, sw_device=None, device=None,
-                             *args, shard_ranks: bool = False, **kwargs) -> torch.Tensor:
-    """`shard_ranks=True` (opt-in; every rank must pass the SAME `inputs`, in lock-step): window batches are dealt
+                             *args, shard_ranks: bool = False, mirror_axes=(), **kwargs) -> torch.Tensor:
+    """`mirror_axes` (mirror test-time augmentation; (), an int or a sequence out of 0 = D, 1 = H, 2 = W): every window
+    is predicted under each flip combination of these axes (`mirror_masks`, the identity first) and the un-mirrored
+    logits of all of them are blended with the window's weights: the result is the importance-weighted mean over
+    windows and masks.  A (window, mask) pair is one more row of the window table, mask fastest, so batches may start
+    or end in the middle of a window's masks; the gather writes the window mirrored and the blend reads the logits
+    mirrored (index changes inside the two kernels, no extra pass over the windows).  The predictor sees the mirrored
+    window; the `centers` row of the tuple path is the window's own.
+
+    `shard_ranks=True` (opt-in; every rank must pass the SAME `inputs`, in lock-step): window batches are dealt
     round-robin to the ranks, each step's logits are exchanged with one all-gather and blended by every rank in the
     single-rank order, so all ranks return the bit-identical single-rank result.  Default: every rank works on its own
     volume, as the reference does (validation files are partitioned per rank, data/dataset_builder.py:455-464)."""
@@ -167,18 +202,29 @@ def sliding_window_inference(inputs: torch.Tensor, affine, roi_size, sw_batch_si
     interval = get_scan_interval(image_size, roi, 3, overlap)
     starts = window_starts(image_size, roi, interval)
     num_win = len(starts)
-    total = num_win * B
+    masks = mirror_masks(mirror_axes)
+    M = len(masks)
+    total = num_win * B * M
     nb = int(sw_batch_size)
     imp = importance_map(tuple(min(r, i) for r, i in zip(roi, image_size)), mode, sigma_scale, dev)
     vol = inputs.float().contiguous()
     ws, rk = (parallel.world_size(), parallel.rank()) if shard_ranks else (1, 0)
 
-    # all window starts as (b, z0, y0, x0) rows, padded with unused slots to whole steps of ws * nb windows
+    # all window starts as (b, z0, y0, x0) rows, every start once per mirror mask (mask fastest), padded with unused
+    # slots to whole steps of ws * nb windows; flips[row] = the row's mask (None without mirroring: the plain launches)
     nsteps = -(-total // (nb * ws))
     rows_h = torch.full((nsteps * ws * nb, 4), -1, dtype=torch.int32)
     st = torch.tensor(starts, dtype=torch.int32)
-    rows_h[:total, 0] = torch.arange(total, dtype=torch.int32) // num_win
-    rows_h[:total, 1:] = st.repeat(B, 1)
+    rows_h[:total, 0] = torch.arange(total, dtype=torch.int32) // (num_win * M)
+    rows_h[:total, 1:] = st.repeat_interleave(M, dim=0).repeat(B, 1)
+    flips = None
+    if M > 1:
+        flips_h = torch.zeros(nsteps * ws * nb, dtype=torch.int32)
+        flips_h[:total] = torch.tensor(masks, dtype=torch.int32).repeat(num_win * B)
+        flips = flips_h.to(dev)
+
+    def fl(first, n):
+        return None if flips is None else flips[first:first + n]
     rows_gather = rows_h.clone()
     rows_gather[:total, 1:] -= torch.tensor(pad_lo, dtype=torch.int32)    # gather reads the unpadded volume
     rows_blend = rows_h.to(dev)
@@ -210,14 +256,16 @@ def sliding_window_inference(inputs: torch.Tensor, affine, roi_size, sw_batch_si
         def blend_step(item):
             work, buf, step = item
             work.wait()
-            hip.sw_blend_batch(buf, imp, out, cnt, rows_blend[step * ws * nb:(step + 1) * ws * nb], ws * nb)
+            hip.sw_blend_batch(buf, imp, out, cnt, rows_blend[step * ws * nb:(step + 1) * ws * nb], ws * nb,
+                               flips=fl(step * ws * nb, ws * nb))
 
         for i in range(nsteps):
             g0 = (i * ws + rk) * nb                       # this rank's batch of the step (all slots unused: idle replay)
-            hip.sw_gather_batch(vol, g.win, rows_gather[g0:g0 + nb], nb, cval, channels_last_ld=Cin)
+            hip.sw_gather_batch(vol, g.win, rows_gather[g0:g0 + nb], nb, cval, channels_last_ld=Cin, flips=fl(g0, nb))
             seg = g()
             if ws == 1:
-                hip.sw_blend_batch(seg, imp, out, cnt, rows_blend[g0:g0 + nb], nb, channels_last_ld=seg.shape[-1])
+                hip.sw_blend_batch(seg, imp, out, cnt, rows_blend[g0:g0 + nb], nb, channels_last_ld=seg.shape[-1],
+                                   flips=fl(g0, nb))
                 continue
             if comp is None:
                 comp = [torch.empty((nb, ncls) + tuple(seg.shape[1:4]), dtype=seg.dtype, device=dev) for _ in range(2)]
@@ -237,13 +285,13 @@ def sliding_window_inference(inputs: torch.Tensor, affine, roi_size, sw_batch_si
             idxs = [g for g in range(g0, g0 + nb) if g < total]
             seg = None
             if idxs:
-                centers = torch.tensor([[(starts[g % num_win][d] + roi[d] - roi[d] // 2) / image_size[d] for d in range(3)]
+                centers = torch.tensor([[(starts[(g // M) % num_win][d] + roi[d] - roi[d] // 2) / image_size[d] for d in range(3)]
                                         for g in idxs], dtype=torch.float32, device=dev)
                 if sw_batch_size == 1:
                     centers = centers.unsqueeze(0)  # reference quirk (engine/utils.py:131-132)
                 if win is None:
                     win = torch.zeros(nb, Cin, *roi, dtype=torch.float32, device=dev)
-                hip.sw_gather_batch(vol, win, rows_gather[g0:g0 + nb], nb, cval)
+                hip.sw_gather_batch(vol, win, rows_gather[g0:g0 + nb], nb, cval, flips=fl(g0, nb))
                 seg = predictor((win[:len(idxs)], centers, affine), *args, **kwargs)
                 if seg.dtype not in (torch.float32, torch.bfloat16):
                     seg = seg.float()
@@ -255,7 +303,7 @@ def sliding_window_inference(inputs: torch.Tensor, affine, roi_size, sw_batch_si
                     ncls = int(t.item())
                 out, cnt = accumulators(ncls)
             if ws == 1:
-                hip.sw_blend_batch(seg.contiguous(), imp, out, cnt, rows_blend[g0:g0 + nb], len(idxs))
+                hip.sw_blend_batch(seg.contiguous(), imp, out, cnt, rows_blend[g0:g0 + nb], len(idxs), flips=fl(g0, nb))
                 continue
             # sharded: one all-gather per step, then every rank blends the step's ws * nb windows in global order
             mine = torch.zeros(nb, ncls, *roi, dtype=torch.float32, device=dev)
@@ -264,7 +312,8 @@ def sliding_window_inference(inputs: torch.Tensor, affine, roi_size, sw_batch_si
             if gathered is None:
                 gathered = torch.empty(ws * nb, ncls, *roi, dtype=torch.float32, device=dev)
             torch.distributed.all_gather_into_tensor(gathered, mine)
-            hip.sw_blend_batch(gathered, imp, out, cnt, rows_blend[i * ws * nb:(i + 1) * ws * nb], ws * nb)
+            hip.sw_blend_batch(gathered, imp, out, cnt, rows_blend[i * ws * nb:(i + 1) * ws * nb], ws * nb,
+                               flips=fl(i * ws * nb, ws * nb))
     for b in range(B):
         hip.sw_normalize(out[b], cnt[b])
     sl = [slice(None), slice(None)] + [slice(pad_lo[d], pad_lo[d] + image_size_[d]) for d in range(3)]

@@ -10,7 +10,7 @@ import torch
 from ..utils import misc
 from .test import dice_of_maps, label_map, post_enabled, postprocess
 from .train import _metric_update
-from .utils import sliding_window_inference
+from .utils import mirror_axes_tuple, sliding_window_inference
 
 
 def run_validation(model, data_loader, criterion, device, epoch, cfg, log_writer=None, inferer=sliding_window_inference):
@@ -21,6 +21,9 @@ def run_validation(model, data_loader, criterion, device, epoch, cfg, log_writer
         metric_logger.add_meter(name, misc.SmoothedValue(window_size=100, fmt="{value:.6f}"))
     header = "Validation for epoch: [{}]".format(epoch)
     air_cval = (0.0 - cfg.t_norm_mean) / cfg.t_norm_std if cfg.t_normalize else 0.0
+    # mirror test-time augmentation (--infer_mirror_axes); the keyword goes only to an inferer that is asked to mirror
+    mirror = mirror_axes_tuple(getattr(cfg, "infer_mirror_axes", ()))
+    mirror_kw = {"mirror_axes": mirror} if mirror else {}
 
     for data_iter_step, batch in enumerate(metric_logger.log_every(data_loader, 1, header)):
         inputs = batch["image"].to(device, non_blocking=True)
@@ -29,7 +32,7 @@ def run_validation(model, data_loader, criterion, device, epoch, cfg, log_writer
         with torch.no_grad():
             outputs = inferer(inputs=inputs, affine=aff_xyz, predictor=model, roi_size=cfg.vol_size,
                               sw_batch_size=cfg.batch_size_val, overlap=cfg.val_infer_overlap, mode="gaussian",
-                              device=device, sw_device=device, cval=air_cval)
+                              device=device, sw_device=device, cval=air_cval, **mirror_kw)
             loss = criterion(outputs, labels)
         loss_value = loss.item()
         if not math.isfinite(loss_value):

@@ -147,6 +147,8 @@ SIGNATURES = {
     "msseg_aug_crop_affine": ([_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _f, _vp], _i),
     "msseg_sw_gather_batch": ([_vp, _ll, _vp, _ll, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp], _i),
     "msseg_sw_blend_batch": ([_vp, _ll, _i, _vp, _vp, _ll, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "msseg_sw_gather_batch_mirror": ([_vp, _ll, _vp, _ll, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp], _i),
+    "msseg_sw_blend_batch_mirror": ([_vp, _ll, _i, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "msseg_deconv_k2s2_bwd_partials_ok": ([_i, _i, _i], _i),
     "msseg_deconv_k2s2_bwd_partials": ([_vp, _ll, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "msseg_conv3d_k3_small_ok": ([_i, _i, _i, _i, _i, _i, _i], _i),
@@ -1323,30 +1325,56 @@ def sw_normalize(out, cnt):
     return out
 
 
-def sw_gather_batch(vol, win, table, nwin, cval=0.0, channels_last_ld=0):
+def _sw_flips(flips, table, nwin):
+    """the optional per-row mirror masks of the batched sliding-window calls: device int32 [>= nwin] next to `table`"""
+    if flips is None:
+        return None
+    _need_gpu(flips)
+    if flips.dtype != torch.int32 or not flips.is_contiguous() or flips.dim() != 1 or flips.shape[0] < nwin \
+            or flips.device != table.device:
+        raise ValueError("flips: contiguous int32 [>= nwin] on the table's device")
+    return flips
+
+
+def sw_gather_batch(vol, win, table, nwin, cval=0.0, channels_last_ld=0, flips=None):
     """vol: [B, C, *vol] fp32 ; win: [nwin, C, *roi] (ld 0) or channels-last [nwin, *roi, ld] ; table: int32 [>=nwin, 4]
-    device tensor of (b, z0, y0, x0), b < 0 = unused slot."""
+    device tensor of (b, z0, y0, x0), b < 0 = unused slot.  flips: optional int32 [>=nwin] device tensor, bit 0 / 1 / 2 =
+    row j's window is mirrored along D / H / W (torch.flip of the plain window)."""
     _need_gpu(vol, win, table)
+    flips = _sw_flips(flips, table, nwin)
     assert vol.dtype == torch.float32 and vol.is_contiguous() and win.is_contiguous()
     assert table.dtype == torch.int32 and table.is_contiguous() and table.shape[0] >= nwin
     Cc = vol.shape[1]
     VD, VH, VW = vol.shape[2:]
     RD, RH, RW = win.shape[2:] if channels_last_ld == 0 else win.shape[1:4]
-    _ck(lib().msseg_sw_gather_batch(_p(vol), vol.stride(0), _p(win), channels_last_ld, dt(win), _p(table), nwin, Cc, VD, VH,
-                                    VW, RD, RH, RW, float(cval), _stream()), "sw_gather_batch")
+    if flips is None:
+        _ck(lib().msseg_sw_gather_batch(_p(vol), vol.stride(0), _p(win), channels_last_ld, dt(win), _p(table), nwin, Cc, VD,
+                                        VH, VW, RD, RH, RW, float(cval), _stream()), "sw_gather_batch")
+    else:
+        _ck(lib().msseg_sw_gather_batch_mirror(_p(vol), vol.stride(0), _p(win), channels_last_ld, dt(win), _p(table),
+                                               _p(flips), nwin, Cc, VD, VH, VW, RD, RH, RW, float(cval), _stream()),
+            "sw_gather_batch_mirror")
     return win
 
 
-def sw_blend_batch(win, imp, out, cnt, table, nwin, channels_last_ld=0):
-    """out: [B, C, *vol] fp32 ; cnt: [B, *vol] fp32 ; win as in sw_gather_batch (C = out.shape[1] channels used)."""
+def sw_blend_batch(win, imp, out, cnt, table, nwin, channels_last_ld=0, flips=None):
+    """out: [B, C, *vol] fp32 ; cnt: [B, *vol] fp32 ; win as in sw_gather_batch (C = out.shape[1] channels used).
+    flips: as in sw_gather_batch -- row j's logits are un-mirrored on the way in, `imp` stays in volume orientation."""
     _need_gpu(win, imp, out, cnt, table)
+    flips = _sw_flips(flips, table, nwin)
     assert out.is_contiguous() and cnt.is_contiguous() and win.is_contiguous() and imp.is_contiguous()
     assert table.dtype == torch.int32 and table.is_contiguous() and table.shape[0] >= nwin
     Cc = out.shape[1]
     VD, VH, VW = out.shape[2:]
     RD, RH, RW = imp.shape
-    _ck(lib().msseg_sw_blend_batch(_p(win), channels_last_ld, dt(win), _p(imp), _p(out), out.stride(0), _p(cnt),
-                                   cnt.stride(0), _p(table), nwin, Cc, VD, VH, VW, RD, RH, RW, _stream()), "sw_blend_batch")
+    if flips is None:
+        _ck(lib().msseg_sw_blend_batch(_p(win), channels_last_ld, dt(win), _p(imp), _p(out), out.stride(0), _p(cnt),
+                                       cnt.stride(0), _p(table), nwin, Cc, VD, VH, VW, RD, RH, RW, _stream()),
+            "sw_blend_batch")
+    else:
+        _ck(lib().msseg_sw_blend_batch_mirror(_p(win), channels_last_ld, dt(win), _p(imp), _p(out), out.stride(0), _p(cnt),
+                                              cnt.stride(0), _p(table), _p(flips), nwin, Cc, VD, VH, VW, RD, RH, RW,
+                                              _stream()), "sw_blend_batch_mirror")
 
 
 # --------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """CLI of the training / evaluation drivers: every flag of ``/root/reference/utils/arguments.py:29-313`` with
 the same name, type, default and list-collapsing rule (``:19-24``: a list argument of length 1 becomes a scalar,
 longer lists become tuples), declared as a table; plus a few flags of this build (synthetic data, compute
-dtype, hipGraph replay, post-processing, rotation + zoom in the device crop gather).  Flags whose subsystem is out of the hot-path scope (learned class vectors, MONAI
+dtype, hipGraph replay, post-processing, rotation + zoom in the device crop gather, mirror test-time augmentation).  Flags whose subsystem is out of the hot-path scope (learned class vectors, MONAI
 transforms, Neptune) are accepted and ignored so reference command lines keep working."""
 from __future__ import annotations
 
@@ -67,6 +67,9 @@ _SPEC = {
         # random rotation + zoom inside the device crop gather (data_device.py): probability per patch, angle bound(s) in
         # degrees (one for all three tensor axes or one per axis, each angle from U(-A, A)), zoom factor from U(LO, HI)
         ("--t_affine_prob", "v", 0.0, F), ("--t_affine_rotate", "l", [30.0], F), ("--t_affine_zoom", "l", [0.7, 1.4], F),
+        # mirror test-time augmentation of the sliding-window inference (engine/utils.py): the volume axes (0 = D, 1 = H,
+        # 2 = W) to flip; every window is predicted under each of the 2^n flip combinations and the logits are averaged
+        ("--infer_mirror_axes", "l", [], I),
     ],
 }
 

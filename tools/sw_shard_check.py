@@ -41,6 +41,11 @@ def main():
                 sharded = sliding_window_inference(shared, aff, roi, nb, pred, overlap=0.5, mode="gaussian",
                                                    shard_ranks=True)
                 assert torch.equal(single, sharded), (tag, roi, nb, rk, float((single - sharded).abs().max()))
+            # mirror test-time augmentation: 8 rows per window, 3 per batch -> steps straddle windows and ranks
+            kw = dict(overlap=0.5, mode="gaussian", mirror_axes=(0, 1, 2))
+            single = sliding_window_inference(shared, aff, (32, 32, 32), 3, pred, **kw)
+            sharded = sliding_window_inference(shared, aff, (32, 32, 32), 3, pred, shard_ranks=True, **kw)
+            assert torch.equal(single, sharded), (tag, "mirror", rk, float((single - sharded).abs().max()))
         # default mode: each rank its own volume, result == what the same call gives without a process group view
         mine = torch.randn(1, 1, 48, 48, 48, generator=torch.Generator().manual_seed(100 + rk)).to(dev)
         a = sliding_window_inference(mine, aff, (32, 32, 32), 2, net, overlap=0.5, mode="gaussian")
