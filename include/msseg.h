@@ -89,6 +89,11 @@ int msseg_conv3d_k3_variant(int N, int D, int H, int W, int Cout);
  * 73-128).  Variant 4 reads a DIFFERENT weight image -- four msseg_pack_weights images back to back, see
  * medicalsemseg_amd/hip.py pack_conv_k3_c48 and csrc/conv3d_k3_c48.hip -- so the packer must ask this function. */
 int msseg_conv3d_k3_kernel(int N, int D, int H, int W, int Cin, int Cout, int dtype);
+/* Workgroups of that kernel the runtime keeps resident on one CU, at the dynamic LDS size the launcher passes for a batch of N
+ * (the generic kernel's statistics area is sized by N).  Generic variants 0/1/2 only: MSSEG_EINVAL where
+ * msseg_conv3d_k3_kernel answers 3 or 4.  Needs a device; launches nothing.  MSSEG_K3_MID_ONE_PER_CU=1 in the environment
+ * (read once) makes the 4x4x8 tile pass its full-size area again: one workgroup per CU with the same code. */
+int msseg_conv3d_k3_resident_per_cu(int N, int D, int H, int W, int Cin, int Cout, int dtype);
 
 /* ---------------------------------------------------------------------------------------------
  * Implicit-GEMM convolutions (forward-shaped).  y = conv(x, W) + bias.

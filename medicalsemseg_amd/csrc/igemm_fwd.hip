@@ -141,6 +141,20 @@ int msseg_conv3d_k3_kernel(int N, int D, int H, int W, int Cin, int Cout, int dt
     return cfg;
 }
 
+int msseg_conv3d_k3_resident_per_cu(int N, int D, int H, int W, int Cin, int Cout, int dtype) {
+    if (dtype != MSSEG_F32 && dtype != MSSEG_BF16) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_resident_per_cu: bad dtype %d", dtype);
+    if (N < 1 || D < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_resident_per_cu: bad shape");
+    if (msseg_conv3d_k3_kernel(N, D, H, W, Cin, Cout, dtype) > 2)
+        MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_resident_per_cu: the problem runs on a ping-pong kernel, not on the generic one");
+    // the launch path itself up to the launch: same plan, same instantiation, same LDS size
+    int resident = 0;
+    IgemmParams p = igemm_params(nullptr, Cin, nullptr, nullptr, nullptr, Cout, Cin, Cout);
+    p.N = N; p.D = D; p.H = H; p.W = W;
+    p.resident_out = &resident;
+    const int rc = launch_k3(p, dtype, nullptr);
+    return rc ? rc : resident;
+}
+
 // conv k3 p1 with the optional fused reductions f (f.stats == nullptr: none); stats_ws and nb_S are filled in here
 static int k3_fwd_impl(const void* x, long long ldx, const void* wp, const float* bias, void* y, long long ldy, int N,
                        int D, int H, int W, int Cin, int Cout, K3Fused f, void* scratch, size_t scratch_bytes, int dtype,

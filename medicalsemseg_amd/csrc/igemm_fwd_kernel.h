@@ -23,6 +23,7 @@
 #include "common.h"
 #include "k3pp.h"
 
+#include <stdlib.h>
 #include <type_traits>
 
 // outside the anonymous namespace: the msseg_igemm_* launchers pass it between translation units
@@ -45,6 +46,7 @@ struct IgemmParams {
     int rel32_ok;        // halo-relative element offsets fit 32 bits (precomputed-offset staging path)
     int cout_block;      // 0 = msseg_cout_block(M)
     K3Fused fused;       // optional fused reductions of the stored output (k3pp.h)
+    int* resident_out;   // host side only: non-null asks launch_cfg for the resident workgroups per CU instead of a launch
 };
 
 namespace {
@@ -68,9 +70,16 @@ struct IgemmCfg {
     static constexpr int PLANE = ((HV * 16 + 255) / 256) * 256;
     static constexpr int A_BYTES = ((4 * PLANE + 64 + 255) / 256) * 256;
     static constexpr int B_BYTES = NTAPS * 4 * COUTB * 16;
-    static constexpr int STAT_FLOATS = MSSEG_STATS_NMAX * COUTB * 2;
-    static constexpr int STAT_BYTES = (EPI == EPI_STORE) ? (STAT_FLOATS + WAVES * COUTB * 2) * 4 + 256 : 0;
-    static constexpr int LDS_BYTES = A_BYTES + B_BYTES + STAT_BYTES;
+    // Statistics area (EPI_STORE): the per-wave staging of a flush [WAVES][COUTB][2] first, because its size is fixed, then one
+    // (sum, sum of squares) slot [COUTB][2] per sample of the launch.  The launch passes lds_bytes(samples of the launch), so a
+    // training batch does not pay LDS for MSSEG_STATS_NMAX samples: on the 4x4x8 tile with 32-wide cout blocks that is the
+    // difference between one and two resident workgroups per CU (80 640 B at N = 2 against 82 432 B).  Nothing reads or
+    // writes past the last slot, so there is no pad behind it; LEGACY_LDS_BYTES is the size every launch passed before
+    // (NMAX slots + a 256 B pad), kept for the one-workgroup-per-CU switch of launch_cfg and as the registered maximum.
+    static constexpr int WPART_FLOATS = (EPI == EPI_STORE) ? WAVES * COUTB * 2 : 0;
+    static constexpr int SLOT_FLOATS = (EPI == EPI_STORE) ? COUTB * 2 : 0;
+    static constexpr int lds_bytes(int nslots) { return A_BYTES + B_BYTES + (WPART_FLOATS + nslots * SLOT_FLOATS) * 4; }
+    static constexpr int LEGACY_LDS_BYTES = lds_bytes(MSSEG_STATS_NMAX) + ((EPI == EPI_STORE) ? 256 : 0);
     static_assert(TV % (16 * WAVES) == 0, "tile must split into 16-voxel MFMA tiles per wave");
 };
 
@@ -103,11 +112,11 @@ __global__ __launch_bounds__(WAVES * 64, 1) void igemm_fwd_kernel(const IgemmPar
         abase[m] = aoff(q, PLANE) + ((td * STRIDE * PH + th * STRIDE) * PW + tw * STRIDE) * 16;
     }
     const int bbase = (q * COUTB + r) * 16;
-    float* spart = (float*)(smem + C::A_BYTES + C::B_BYTES);
+    float* wpart = (float*)(smem + C::A_BYTES + C::B_BYTES);  // [WAVES][COUTB][2] staging for the per-sample flush
+    float* spart = wpart + C::WPART_FLOATS;                   // [p.N][COUTB][2] sample slots (IgemmCfg::lds_bytes)
     const bool do_stats = (EPI == EPI_STORE) && p.fused.stats != nullptr;
-    float* wpart = spart + C::STAT_FLOATS;  // [WAVES][COUTB][2] staging for the per-sample flush
     if (do_stats) {
-        for (int i = tid; i < C::STAT_FLOATS; i += NTHREADS) spart[i] = 0.f;
+        for (int i = tid; i < p.N * C::SLOT_FLOATS; i += NTHREADS) spart[i] = 0.f;
     }
     float st[NT][4], st2[NT][4];  // this lane's running (sum, sum of squares) of the current sample
 #pragma unroll
@@ -590,17 +599,57 @@ int launch_cfg(IgemmParams& p, hipStream_t stream) {
     }
     auto kern = igemm_fwd_kernel<T, NTAPS, SRC, EPI, TD, TH, TW, WAVES, NT, STRIDE>;
     static msseg_lds_attr_once attr;
-    if (!attr.ensure((const void*)kern, C::LDS_BYTES)) MSSEG_FAIL(MSSEG_ELAUNCH, "igemm: cannot set dynamic LDS size %d", C::LDS_BYTES);
+    if (!attr.ensure((const void*)kern, C::LEGACY_LDS_BYTES))
+        MSSEG_FAIL(MSSEG_ELAUNCH, "igemm: cannot set dynamic LDS size %d", C::LEGACY_LDS_BYTES);
+    // Sample slots of the statistics area: the launch's N (validated against MSSEG_STATS_NMAX wherever statistics are asked
+    // for; a plain launch of a larger batch never touches the area).  MSSEG_K3_MID_ONE_PER_CU=1 makes the 4x4x8 tile pass what
+    // every launch passed before the area was sized by N: the same code at one workgroup per CU, for A/B runs in one build.
+    static const bool legacy_lds = NTAPS == 27 && STRIDE == 1 && TD * TH * TW == 128 && [] {
+        const char* e = getenv("MSSEG_K3_MID_ONE_PER_CU");
+        return e != nullptr && *e != 0 && *e != '0';
+    }();
+    const int nslots = legacy_lds ? MSSEG_STATS_NMAX + 1 : (p.N < MSSEG_STATS_NMAX ? p.N : MSSEG_STATS_NMAX);
+    const int lds = legacy_lds ? C::LEGACY_LDS_BYTES : C::lds_bytes(nslots);
+    // The LDS-only rule every grid was sized by.  The flat and stride-2 families and the 2x4x8 conv tile keep it: their
+    // registers allow another count than it answers (two or three where it says four; three where it says two), so the grid
+    // of a long launch differs from what is resident; the number of partial rows of the fused sums, and with it their
+    // summation order, follows from that grid and stays what it was.
+    int wg_per_cu = (lds > 80 * 1024) ? 1 : ((lds > 40 * 1024) ? 2 : 4);
+    if constexpr (NTAPS == 27 && STRIDE == 1) {
+        // conv k3 tiles (k3_plan): the workgroups of this instantiation a CU holds at that LDS size, asked of the runtime once
+        // per (instantiation, size).  It knows the registers the compiler used and the LDS allocation granule.
+        static std::atomic<int> resident[MSSEG_STATS_NMAX + 2];
+        int res = resident[nslots].load(std::memory_order_relaxed);
+        if (res == 0) {
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&res, (const void*)kern, C::NTHREADS, lds) != hipSuccess || res < 1)
+                MSSEG_FAIL(MSSEG_ELAUNCH, "igemm: no occupancy with %d bytes of LDS", lds);
+            resident[nslots].store(res, std::memory_order_relaxed);
+        }
+        if (p.resident_out != nullptr) {   // msseg_conv3d_k3_resident_per_cu: the plan only, nothing is launched
+            *p.resident_out = res;
+            return MSSEG_OK;
+        }
+        if (TD * TH * TW != 64) wg_per_cu = res;   // the 4x4x8 and 4x8x16 tiles size their grid by it
+    } else {
+        if (p.resident_out != nullptr) MSSEG_FAIL(MSSEG_EINVAL, "igemm: the residency query is for the conv k3 tiles");
+    }
     const int ncb = ceil_div(p.M, C::COUTB);
-    const int wg_per_cu = (C::LDS_BYTES > 80 * 1024) ? 1 : ((C::LDS_BYTES > 40 * 1024) ? 2 : 4);
-    int gx = msseg_num_cus() * wg_per_cu / (ncb > 1 ? 1 : 1);
+    int gx = msseg_num_cus() * wg_per_cu;
     if (gx > p.ntiles) gx = p.ntiles;
+    if (EPI == EPI_STORE && p.fused.stats != nullptr) {
+        // one partial row of N x COUTB x 2 floats per workgroup: no more workgroups than the reduce scratch holds rows of
+        // (a persistent workgroup walks tiles in steps of the grid, so a smaller grid is only slower)
+        const size_t row_bytes = (size_t)ncb * p.N * C::COUTB * 2 * sizeof(float);
+        const size_t fit = (msseg_reduce_scratch_bytes() - MSSEG_SCRATCH_COUNTER_BYTES) / row_bytes;
+        if (fit < 1) MSSEG_FAIL(MSSEG_EWORKSPACE, "igemm: one row of fused sums (%zu bytes) exceeds the reduce scratch", row_bytes);
+        if ((size_t)gx > fit) gx = (int)fit;
+    }
     if (gx < 1) gx = 1;
     dim3 grid(gx, ncb, 1);
     static const char* const kt_name = NTAPS != 27 ? "igemm_fwd_kernel<flat>"
                                        : (TD * TH * TW == 512 ? "igemm_fwd_kernel<27,4x8x16>"
                                           : (TD * TH * TW == 128 ? "igemm_fwd_kernel<27,4x4x8>" : "igemm_fwd_kernel<27,2x4x8>"));
-    MSSEG_KTIMED(kt_name, stream, hipLaunchKernelGGL(kern, grid, dim3(C::NTHREADS), C::LDS_BYTES, stream, p));
+    MSSEG_KTIMED(kt_name, stream, hipLaunchKernelGGL(kern, grid, dim3(C::NTHREADS), lds, stream, p));
     MSSEG_CHECK_LAUNCH("igemm_fwd");
     if (EPI == EPI_STORE && p.fused.stats != nullptr)
         return msseg_k3_fused_finalize(p.fused, gx, p.N, C::COUTB, p.M, p.fused.nb_y != nullptr, ncb, stream);

@@ -34,6 +34,7 @@ SIGNATURES = {
     "msseg_conv3d_k3_cout_block": ([_i, _i, _i, _i, _i], _i),
     "msseg_conv3d_k3_variant": ([_i, _i, _i, _i, _i], _i),
     "msseg_conv3d_k3_kernel": ([_i, _i, _i, _i, _i, _i, _i], _i),
+    "msseg_conv3d_k3_resident_per_cu": ([_i, _i, _i, _i, _i, _i, _i], _i),
     "msseg_conv3d_k3_fwd": ([_vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _i, _vp], _i),
     "msseg_conv3d_k3_fwd_accumulate": ([_vp, _ll, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _i, _vp], _i),
     "msseg_dwconv3d_k3_fwd": ([_vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
@@ -270,6 +271,14 @@ def cout_block(M: int) -> int:
 
 def conv_k3_cout_block(N, D, H, W, cout) -> int:
     return lib().msseg_conv3d_k3_cout_block(N, D, H, W, cout)
+
+
+def conv_k3_resident_per_cu(N, D, H, W, cin, cout, dtype) -> int:
+    """workgroups of the generic conv k3 kernel planned for this problem that one CU holds at the LDS size of a batch of N"""
+    r = lib().msseg_conv3d_k3_resident_per_cu(N, D, H, W, cin, cout, _DT[dtype])
+    if r < 0:
+        _ck(r, "conv3d_k3_resident_per_cu")
+    return r
 
 
 class PackJob(C.Structure):
