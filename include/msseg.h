@@ -810,6 +810,44 @@ int msseg_aug_crop_multi(const void* volumes, int nvol, const void* rows, const 
 int msseg_aug_crop_affine(const void* volumes, int nvol, const void* rows, const int* picks, const double* mats, int npatch,
                           int C, void* out_img, int out_dtype, float* out_lab, int R, float pad_value, msseg_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Intensity augmentation of a gathered batch (csrc/intensity_aug.hip; no reference counterpart: the reference has no
+ * noise / blur / contrast / gamma transform; the recipe and its order are nnU-Net's).  x: fp32 [N][C][D][H][W], the gather's
+ * output; out: the same shape in out_dtype (MSSEG_F32 / MSSEG_BF16), out != x; one msseg_intensity_row per (patch, channel),
+ * row n * C + c.  The table is passed twice: rows_dev is read by the kernels, rows_host (the same N * C rows in host memory,
+ * read before the call returns) is what the entry point validates and plans its launches from.  Stages, in this order, on
+ * each row whose bit is set (semantics: tests/intensity_aug_ref.py, float64):
+ *   NOISE      x += noise_std * z(noise_key, i), i = flat voxel index inside the (patch, channel).  Philox4x32-10, counter
+ *              {i lo, i hi, 0, 0}, key {noise_key lo, hi}; u1, u2 = ((word0, word1 >> 8) + 0.5) * 2^-24 in fp32;
+ *              z = sqrt(-2 ln u1) cos(2 pi u2).
+ *   BLUR       scipy.ndimage.gaussian_filter(x, blur_sigma, mode="reflect", truncate=4) over D, H, W: radius
+ *              int(4 sigma + 0.5), weights exp(-k^2 / (2 sigma^2)) normalised.
+ *   CONTRAST   x = clip((x - m) * contrast + m, lo, hi); m, lo, hi = mean, min, max of the row at this point.
+ *   GAMMA_INV  the GAMMA formula with gamma_inv on -x, negated back.
+ *   GAMMA      m, s = mean, population std; lo = min, R = max - lo; y = ((x - lo) / (R + 1e-7))^gamma * R + lo;
+ *              x = (y - mean(y)) / (std(y) + 1e-8) * s + m.
+ * A row with no bit set is copied (converted).  Deterministic: per-block partials combined in a fixed order, no
+ * floating-point atomics.  MSSEG_EINVAL, with nothing launched, for a patch dimension outside 8..4096, N * C > 65535, a
+ * blur sigma outside (0, 2] (radius above 8), a negative or non-finite noise std, a gamma <= 0, unknown mask bits, a bad
+ * dtype.  workspace: msseg_intensity_aug_workspace_bytes(...) bytes, 16-byte aligned; needed only when a contrast or gamma
+ * bit is set (MSSEG_EWORKSPACE otherwise).  Launches: 1 (noise / blur / copy) + 1 if any row has CONTRAST + 2 per gamma kind
+ * present.  msseg_intensity_noise_bits: the four Philox words of counters first .. first + n - 1 under the key {key_lo, key_hi}, uint32 [n][4]
+ * (test aid for the generator's integer stage).
+ * ------------------------------------------------------------------------------------------- */
+#define MSSEG_INTENSITY_NOISE 1u
+#define MSSEG_INTENSITY_BLUR 2u
+#define MSSEG_INTENSITY_CONTRAST 4u
+#define MSSEG_INTENSITY_GAMMA_INV 8u
+#define MSSEG_INTENSITY_GAMMA 16u
+/* 32 bytes; offsets: mask 0, noise_std 4, noise_key 8, blur_sigma 16, contrast 20, gamma_inv 24, gamma 28 */
+typedef struct msseg_intensity_row {
+    uint32_t mask; float noise_std; uint64_t noise_key; float blur_sigma, contrast, gamma_inv, gamma;
+} msseg_intensity_row;
+size_t msseg_intensity_aug_workspace_bytes(int N, int C, int D, int H, int W);
+int msseg_intensity_aug(const float* x, const msseg_intensity_row* rows_host, const void* rows_dev, int N, int C, int D, int H,
+                        int W, void* out, int out_dtype, void* workspace, size_t workspace_bytes, msseg_stream_t stream);
+int msseg_intensity_noise_bits(unsigned key_lo, unsigned key_hi, long long first, long long n, uint32_t* out, msseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

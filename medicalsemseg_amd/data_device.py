@@ -99,17 +99,118 @@ def draw_affine(rng: np.random.Generator, n, affine):
     return mats
 
 
+class IntensityRow(C.Structure):
+    """mirror of msseg_intensity_row (include/msseg.h): one per (patch, channel)"""
+    _fields_ = [("mask", C.c_uint32), ("noise_std", C.c_float), ("noise_key", C.c_uint64), ("blur_sigma", C.c_float),
+                ("contrast", C.c_float), ("gamma_inv", C.c_float), ("gamma", C.c_float)]
+
+
+INTENSITY_STAGES = ("noise", "blur", "contrast", "gamma_invert", "gamma")
+
+
+def _prob(flag, p):
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"--{flag} takes a probability in [0, 1], got {p!r}")
+    return p
+
+
+def _range(flag, v, lowest, open_low, highest=None):
+    """LO HI with lowest <(=) LO <= HI (<= highest)"""
+    r = tuple(v) if isinstance(v, (tuple, list)) else (v,)
+    ok = len(r) == 2 and all(np.isfinite(float(a)) for a in r) and float(r[0]) <= float(r[1]) and \
+        (float(r[0]) > lowest if open_low else float(r[0]) >= lowest) and (highest is None or float(r[1]) <= highest)
+    if not ok:
+        raise ValueError(f"--{flag} takes LO HI with {lowest:g} {'<' if open_low else '<='} LO <= HI"
+                         f"{'' if highest is None else f' <= {highest:g}'}, got {v!r}")
+    return float(r[0]), float(r[1])
+
+
+def intensity_config(noise_prob=0.0, noise_std=(0.0, 0.1), blur_prob=0.0, blur_sigma=(0.5, 1.0), blur_channel_prob=0.5,
+                     contrast_prob=0.0, contrast_range=(0.75, 1.25), gamma_invert_prob=0.0, gamma_prob=0.0,
+                     gamma_range=(0.7, 1.5)):
+    """--t_noise_* / --t_blur_* / --t_contrast_* / --t_gamma_* as a dict; a ValueError names the flag.  The blur's HI is
+    at most 2: the kernel's radius int(4 sigma + 0.5) stops at 8."""
+    return {"noise_prob": _prob("t_noise_prob", noise_prob), "noise_std": _range("t_noise_std", noise_std, 0.0, False),
+            "blur_prob": _prob("t_blur_prob", blur_prob), "blur_sigma": _range("t_blur_sigma", blur_sigma, 0.0, True, 2.0),
+            "blur_channel_prob": _prob("t_blur_channel_prob", blur_channel_prob),
+            "contrast_prob": _prob("t_contrast_prob", contrast_prob),
+            "contrast_range": _range("t_contrast_range", contrast_range, 0.0, True),
+            "gamma_invert_prob": _prob("t_gamma_invert_prob", gamma_invert_prob),
+            "gamma_prob": _prob("t_gamma_prob", gamma_prob), "gamma_range": _range("t_gamma_range", gamma_range, 0.0, True)}
+
+
+def intensity_config_from_args(cfg):
+    """the flags of a parsed command line -> intensity_config(...)"""
+    return intensity_config(cfg.t_noise_prob, cfg.t_noise_std, cfg.t_blur_prob, cfg.t_blur_sigma, cfg.t_blur_channel_prob,
+                            cfg.t_contrast_prob, cfg.t_contrast_range, cfg.t_gamma_invert_prob, cfg.t_gamma_prob,
+                            cfg.t_gamma_range)
+
+
+def intensity_on(config):
+    return config is not None and any(config[s + "_prob"] > 0.0 for s in INTENSITY_STAGES)
+
+
+def _two_sided(rng, lo, hi):
+    """nnU-Net's rule for a factor range that straddles 1: a coin, then U(lo, 1) (only when lo < 1) or U(max(lo, 1), hi);
+    the ends are kept inside [lo, hi] when the range lies on one side of 1"""
+    if rng.random() < 0.5 and lo < 1.0:
+        return float(rng.uniform(lo, min(1.0, hi)))
+    return float(rng.uniform(min(max(lo, 1.0), hi), hi))
+
+
+def draw_intensity(rng: np.random.Generator, n_patches, n_channels, config):
+    """the IntensityRow list of n_patches x n_channels (row n * C + c).  Per patch, in the kernel's stage order, one uniform
+    number against the stage's probability and, only if the patch is chosen: noise -- one std for the patch, one 64-bit key
+    per channel; blur -- per channel one uniform number against blur_channel_prob and, if it passes, a sigma; contrast,
+    gamma on the inverted image, gamma -- per channel a factor by _two_sided.  A stage of probability 0 draws nothing; with
+    every probability 0 the generator is not touched."""
+    rows = [IntensityRow(0, 0.0, 0, 0.0, 1.0, 1.0, 1.0) for _ in range(n_patches * n_channels)]
+    if not intensity_on(config):
+        return rows
+    for j in range(n_patches):
+        mine = rows[j * n_channels:(j + 1) * n_channels]
+        if config["noise_prob"] > 0.0 and rng.random() < config["noise_prob"]:
+            std = float(rng.uniform(*config["noise_std"]))
+            for r in mine:
+                r.mask |= hip.INTENSITY_NOISE
+                r.noise_std, r.noise_key = std, int(rng.integers(0, 2 ** 64, dtype=np.uint64))
+        if config["blur_prob"] > 0.0 and rng.random() < config["blur_prob"]:
+            for r in mine:
+                if rng.random() < config["blur_channel_prob"]:
+                    r.mask |= hip.INTENSITY_BLUR
+                    r.blur_sigma = float(rng.uniform(*config["blur_sigma"]))
+        for stage, bit, field, rng_key in (("contrast", hip.INTENSITY_CONTRAST, "contrast", "contrast_range"),
+                                           ("gamma_invert", hip.INTENSITY_GAMMA_INV, "gamma_inv", "gamma_range"),
+                                           ("gamma", hip.INTENSITY_GAMMA, "gamma", "gamma_range")):
+            if config[stage + "_prob"] > 0.0 and rng.random() < config[stage + "_prob"]:
+                for r in mine:
+                    r.mask |= bit
+                    setattr(r, field, _two_sided(rng, *config[rng_key]))
+    return rows
+
+
+def _check_intensity(config, roi):
+    config = intensity_config() if config is None else config
+    if intensity_on(config) and roi < 8:
+        raise ValueError(f"the intensity augmentation needs patches of at least 8^3, --vol_size is {roi}")
+    return config
+
+
 class DevicePatchLoader:
     """len() batches of `batch` patches of roi^3 from ONE cached volume; deterministic per seed.  affine_prob > 0 sends the
-    batch through msseg_aug_crop_affine (see DeviceDatasetLoader); the matrices follow the batch's other draws."""
+    batch through msseg_aug_crop_affine (see DeviceDatasetLoader); the matrices follow the batch's other draws.  intensity:
+    an intensity_config(...) (see DeviceDatasetLoader); the batch's intensity rows follow its matrices."""
 
     def __init__(self, image: torch.Tensor, label: torch.Tensor, roi: int, batch: int, n_batches: int, device, seed=13,
                  pos=1.0, neg=1.0, flip_prob=0.0, rot_prob=0.0, shift_os=0.1, shift_prob=0.0, scale_f=0.1, scale_prob=0.0,
                  image_threshold=0.0, out_dtype=torch.float32, affine_prob=0.0, affine_rotate=30.0, affine_zoom=(0.7, 1.4),
-                 affine_pad=0.0):
+                 affine_pad=0.0, intensity=None):
         if image.dim() != 4 or label.dim() != 3:
             raise ValueError("image [C, D, H, W] and label [D, H, W] expected")
         self.affine, self.affine_pad = affine_config(affine_prob, affine_rotate, affine_zoom), float(affine_pad)
+        self.intensity = _check_intensity(intensity, int(roi))
+        self.last_intensity = None
         self.img = image.to(device=device, dtype=torch.float32).contiguous()
         self.lab = label.to(device=device, dtype=torch.uint8).contiguous()
         self.roi, self.batch, self.n, self.dev, self.out_dtype = int(roi), int(batch), int(n_batches), device, out_dtype
@@ -149,7 +250,9 @@ class DevicePatchLoader:
             draws = draw_rows(self.rng, self.batch, int(self.fg.numel()), int(self.bg.numel()), self.cfg)
             rows, centers = self.rows_for(draws)
             self.last_rows = rows
-            img = torch.empty(self.batch, Cc, self.roi, self.roi, self.roi, dtype=self.out_dtype, device=self.dev)
+            aug = intensity_on(self.intensity)                   # then the gather writes an fp32 scratch batch
+            out = torch.empty(self.batch, Cc, self.roi, self.roi, self.roi, dtype=self.out_dtype, device=self.dev)
+            img = torch.empty_like(out, dtype=torch.float32) if aug else out
             lab = torch.empty(self.batch, 1, self.roi, self.roi, self.roi, dtype=torch.float32, device=self.dev)
             if self.affine[0] > 0.0:
                 # the matrices are drawn after the batch's other draws; the rows and starts go to the multi-volume gather's
@@ -165,6 +268,9 @@ class DevicePatchLoader:
                 table = host.to(self.dev, non_blocking=True)
                 hip.aug_crop_batch(self.img, self.lab, table, img, lab, self.roi)
             self.launches += 1
+            if aug:
+                self.last_intensity = draw_intensity(self.rng, self.batch, Cc, self.intensity)
+                img = hip.intensity_aug(img, self.last_intensity, self.out_dtype, out=out)
             aff = torch.eye(4)[None].repeat(self.batch, 1, 1)
             cen = torch.tensor(centers, dtype=torch.float32)
             yield {"image": img, "label": lab,
@@ -315,13 +421,19 @@ class DeviceDatasetLoader:
     affine_prob > 0: each patch is, with that probability, rotated (angles from U(-affine_rotate, affine_rotate) degrees per
     tensor axis) and zoomed (factor from U(*affine_zoom)) about its centre by sampling the cached volume under
     affine_matrix(...) in msseg_aug_crop_affine, still one launch; taps outside the volume read affine_pad.  The matrices
-    of the last batch are in last_mats.  With affine_prob == 0 nothing changes: same kernels, same generator stream."""
+    of the last batch are in last_mats.  With affine_prob == 0 nothing changes: same kernels, same generator stream.
+    intensity: an intensity_config(...).  With any of its stages on, the gather writes an fp32 scratch batch, a patch's
+    intensity rows (draw_intensity) are drawn after its other draws and its matrix, and msseg_intensity_aug (noise, blur,
+    contrast, gamma inverted, gamma) writes the batch in out_dtype; the rows of the last batch are in last_intensity, the
+    labels are untouched.  With every stage off: no draw, no scratch, no launch."""
 
     def __init__(self, volumes, roi, batch, n_batches, patches_per_image=1, device=None, seed=13, crop="fgbg", pos=1.0,
                  neg=1.0, flip_prob=0.0, rot_prob=0.0, shift_os=0.1, shift_prob=0.0, scale_f=0.1, scale_prob=0.0,
                  image_threshold=0.0, out_dtype=torch.float32, affine_prob=0.0, affine_rotate=30.0, affine_zoom=(0.7, 1.4),
-                 affine_pad=0.0):
+                 affine_pad=0.0, intensity=None):
         self.affine, self.affine_pad = affine_config(affine_prob, affine_rotate, affine_zoom), float(affine_pad)
+        self.intensity = _check_intensity(intensity, int(roi))
+        self.last_intensity = None
         if not volumes:
             raise ValueError("DeviceDatasetLoader needs at least one cached volume")
         if crop not in ("fgbg", "spatial"):
@@ -389,13 +501,16 @@ class DeviceDatasetLoader:
         R = self.roi
         for _ in range(self.n):
             vis = [self._next_volume() for _ in range(self.batch)]
-            if self.affine[0] > 0.0:                             # a patch's matrix is drawn right after its other draws
-                made, mats = [], np.empty((self.batch, 3, 3), dtype=np.float64)
-                for j, vi in enumerate(vis):
-                    made.append(self._row(vi))
+            aug = intensity_on(self.intensity)
+            # a patch's matrix is drawn right after its other draws, its intensity rows after the matrix
+            made, irows = [], []
+            mats = np.empty((self.batch, 3, 3), dtype=np.float64) if self.affine[0] > 0.0 else None
+            for j, vi in enumerate(vis):
+                made.append(self._row(vi))
+                if mats is not None:
                     mats[j] = draw_affine(self.rng, 1, self.affine)[0]
-            else:
-                made, mats = [self._row(vi) for vi in vis], None
+                if aug:
+                    irows += draw_intensity(self.rng, 1, self.C, self.intensity)
             rows = [m[0] for m in made]
             table = _upload(rows, self.dev)
             if self.crop == "spatial":
@@ -405,7 +520,8 @@ class DeviceDatasetLoader:
             else:
                 picks = torch.empty(self.batch, 8, dtype=torch.int32, device=self.dev)
                 hip.pick_voxels(self.desc, len(self.vols), table, self.batch, R, self.thr, picks)
-            img = torch.empty(self.batch, self.C, R, R, R, dtype=self.out_dtype, device=self.dev)
+            out = torch.empty(self.batch, self.C, R, R, R, dtype=self.out_dtype, device=self.dev)
+            img = torch.empty_like(out, dtype=torch.float32) if aug else out   # the gather's fp32 scratch batch
             lab = torch.empty(self.batch, 1, R, R, R, dtype=torch.float32, device=self.dev)
             if mats is None:
                 hip.aug_crop_multi(self.desc, len(self.vols), table, picks, img, lab, R)
@@ -413,6 +529,9 @@ class DeviceDatasetLoader:
                 hip.aug_crop_affine(self.desc, len(self.vols), table, picks, torch.from_numpy(mats).to(self.dev), img, lab, R,
                                     self.affine_pad)
             self.launches += 1
+            if aug:
+                img = hip.intensity_aug(img, irows, self.out_dtype, out=out)
+                self.last_intensity = irows
             if self.crop != "spatial":
                 host = picks.cpu()                               # the one small device-to-host copy of the batch
             self.last_rows, self.last_picks, self.last_mats = rows, host, mats

@@ -146,6 +146,9 @@ SIGNATURES = {
     "msseg_pick_voxels": ([_vp, _i, _vp, _i, _i, _f, _vp, _vp], _i),
     "msseg_aug_crop_multi": ([_vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp], _i),
     "msseg_aug_crop_affine": ([_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _f, _vp], _i),
+    "msseg_intensity_aug_workspace_bytes": ([_i, _i, _i, _i, _i], _sz),
+    "msseg_intensity_aug": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp], _i),
+    "msseg_intensity_noise_bits": ([C.c_uint, C.c_uint, _ll, _ll, _vp, _vp], _i),
     "msseg_sw_gather_batch": ([_vp, _ll, _vp, _ll, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp], _i),
     "msseg_sw_blend_batch": ([_vp, _ll, _i, _vp, _vp, _ll, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "msseg_sw_gather_batch_mirror": ([_vp, _ll, _vp, _ll, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp], _i),
@@ -1605,6 +1608,52 @@ def aug_crop_affine(volumes, nvol, rows, picks, mats, out_img, out_lab, roi, pad
     _ck(lib().msseg_aug_crop_affine(_p(volumes), nvol, _p(rows), _p(picks), _p(mats), npatch, out_img.shape[1], _p(out_img),
                                     dt(out_img), _p(out_lab), int(roi), float(pad_value), _stream()), "aug_crop_affine")
     return out_img, out_lab
+
+
+INTENSITY_NOISE, INTENSITY_BLUR, INTENSITY_CONTRAST, INTENSITY_GAMMA_INV, INTENSITY_GAMMA = 1, 2, 4, 8, 16
+INTENSITY_ROW_BYTES = 32
+
+
+def intensity_aug(batch_f32, table, out_dtype=torch.float32, out=None):
+    """noise -> blur -> contrast -> gamma on the inverted image -> gamma on a gathered batch (csrc/intensity_aug.hip).
+    batch_f32: contiguous fp32 [N, C, D, H, W] on the GPU; table: the N * C rows msseg_intensity_row (row n * C + c) as a
+    sequence or array of data_device.IntensityRow on the HOST -- the entry point validates and plans from them; they are
+    uploaded here for the kernels.  -> the batch in out_dtype (fp32 / bf16), written into `out` when given.  Refused with
+    nothing launched: a CPU tensor, another dtype, a non-contiguous batch, a patch dimension below 8, a blur sigma above 2."""
+    _need_gpu(batch_f32, out)
+    if batch_f32.dtype != torch.float32:
+        raise TypeError(f"intensity_aug takes a float32 batch, got {batch_f32.dtype}")
+    if out_dtype not in _DT:
+        raise TypeError(f"unsupported dtype {out_dtype} (float32 / bfloat16 only)")
+    if batch_f32.dim() != 5 or not batch_f32.is_contiguous():
+        raise ValueError("intensity_aug takes a contiguous [N, C, D, H, W] batch")
+    N, Cc, D, H, W = batch_f32.shape
+    raw = bytes(table) if isinstance(table, (C.Array, bytes, bytearray)) else b"".join(bytes(r) for r in table)
+    if len(raw) != N * Cc * INTENSITY_ROW_BYTES:
+        raise ValueError(f"intensity_aug: {N} x {Cc} patches and channels need {N * Cc} rows of {INTENSITY_ROW_BYTES} bytes, "
+                         f"got {len(raw)} bytes")
+    if out is None:
+        out = torch.empty(batch_f32.shape, dtype=out_dtype, device=batch_f32.device)
+    elif out.dtype != out_dtype or out.shape != batch_f32.shape or not out.is_contiguous() or out.device != batch_f32.device:
+        raise ValueError("intensity_aug: out must be a contiguous tensor of the batch's shape and device in out_dtype")
+    host = C.create_string_buffer(raw, len(raw))
+    dev = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(batch_f32.device)   # blocking: the host copy may go
+    ws, ws_bytes = None, 0
+    if any(raw[j] & (INTENSITY_CONTRAST | INTENSITY_GAMMA_INV | INTENSITY_GAMMA) for j in range(0, len(raw), INTENSITY_ROW_BYTES)):
+        ws_bytes = int(lib().msseg_intensity_aug_workspace_bytes(N, Cc, D, H, W))
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=batch_f32.device)
+    _ck(lib().msseg_intensity_aug(_p(batch_f32), C.cast(host, C.c_void_p), _p(dev), N, Cc, D, H, W, _p(out), _DT[out_dtype],
+                                  _p(ws) if ws is not None else None, ws_bytes, _stream()), "intensity_aug")
+    return out
+
+
+def intensity_noise_bits(key, n, first=0, device="cuda"):
+    """the four Philox4x32-10 words of counters first .. first + n - 1 under the 64-bit key, as int32 [n, 4] (bit patterns of
+    the uint32 words): the integer stage of intensity_aug's noise, for comparison with its numpy restatement"""
+    out = torch.empty(int(n), 4, dtype=torch.int32, device=device)
+    _need_gpu(out)
+    _ck(lib().msseg_intensity_noise_bits(int(key) & 0xFFFFFFFF, (int(key) >> 32) & 0xFFFFFFFF, int(first), int(n), _p(out), _stream()), "intensity_noise_bits")
+    return out
 
 
 # --------------------------------------------------------------------------------------------

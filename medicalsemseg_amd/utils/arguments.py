@@ -1,7 +1,7 @@
 """CLI of the training / evaluation drivers: every flag of ``/root/reference/utils/arguments.py:29-313`` with
 the same name, type, default and list-collapsing rule (``:19-24``: a list argument of length 1 becomes a scalar,
 longer lists become tuples), declared as a table; plus a few flags of this build (synthetic data, compute
-dtype, hipGraph replay, post-processing, rotation + zoom in the device crop gather, mirror test-time augmentation).  Flags whose subsystem is out of the hot-path scope (learned class vectors, MONAI
+dtype, hipGraph replay, post-processing, rotation + zoom in the device crop gather, mirror test-time augmentation, intensity augmentation).  Flags whose subsystem is out of the hot-path scope (learned class vectors, MONAI
 transforms, Neptune) are accepted and ignored so reference command lines keep working."""
 from __future__ import annotations
 
@@ -70,6 +70,13 @@ _SPEC = {
         # mirror test-time augmentation of the sliding-window inference (engine/utils.py): the volume axes (0 = D, 1 = H,
         # 2 = W) to flip; every window is predicted under each of the 2^n flip combinations and the logits are averaged
         ("--infer_mirror_axes", "l", [], I),
+        # intensity augmentation of the gathered batch (data_device.py, csrc/intensity_aug.hip), nnU-Net's stages, order and
+        # default ranges: a probability per patch and stage, values from U(LO, HI); --t_blur_channel_prob is the share of
+        # a chosen patch's channels that are blurred; --t_gamma_range serves both gamma stages
+        ("--t_noise_prob", "v", 0.0, F), ("--t_noise_std", "l", [0.0, 0.1], F),
+        ("--t_blur_prob", "v", 0.0, F), ("--t_blur_sigma", "l", [0.5, 1.0], F), ("--t_blur_channel_prob", "v", 0.5, F),
+        ("--t_contrast_prob", "v", 0.0, F), ("--t_contrast_range", "l", [0.75, 1.25], F),
+        ("--t_gamma_invert_prob", "v", 0.0, F), ("--t_gamma_prob", "v", 0.0, F), ("--t_gamma_range", "l", [0.7, 1.5], F),
     ],
 }
 

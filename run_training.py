@@ -35,7 +35,7 @@ def file_loaders(cfg, device, seed, vol):
     """Decathlon data list -> this rank's training / validation volumes, preprocessed once and cached in HBM
     (the reference's ``data/dataset_builder.py:431-491``; transforms :19-306 as device kernels, MONAI parity unpinned)"""
     from medicalsemseg_amd.data_device import (DeviceDatasetLoader, DeviceVolumeLoader, build_cache, crop_mode,
-                                               dataset_file_lists, normalised_zero)
+                                               dataset_file_lists, intensity_config_from_args, normalised_zero)
     crop = crop_mode(cfg)
     rank, world = misc.get_rank(), misc.get_world_size()
     part_train, part_val, train, val = dataset_file_lists(cfg, rank, world)
@@ -65,7 +65,9 @@ def file_loaders(cfg, device, seed, vol):
                                        image_threshold=normalised_zero(cfg),
                                        # rotation + zoom inside the gather; outside the volume lies what the cache pads with
                                        affine_prob=cfg.t_affine_prob, affine_rotate=cfg.t_affine_rotate,
-                                       affine_zoom=cfg.t_affine_zoom, affine_pad=normalised_zero(cfg))
+                                       affine_zoom=cfg.t_affine_zoom, affine_pad=normalised_zero(cfg),
+                                       # noise, blur, contrast and gamma on the gathered batch
+                                       intensity=intensity_config_from_args(cfg))
     return loader_train, DeviceVolumeLoader(rec_val)
 
 
@@ -75,7 +77,7 @@ def synthetic_loaders(cfg, device, seed, vol):
         # device-side data path: one synthetic "CT" of 2x the patch size cached in HBM, patches cropped
         # (fg / bg centres with the reference's pos : neg odds) and augmented by one gather kernel per batch
         from medicalsemseg_amd.data import sphere_labels
-        from medicalsemseg_amd.data_device import DevicePatchLoader
+        from medicalsemseg_amd.data_device import DevicePatchLoader, intensity_config_from_args
         g = torch.Generator().manual_seed(seed)
         lab = sphere_labels(2 * vol, cfg.output_dim)
         img = torch.randn(cfg.in_chans, 2 * vol, 2 * vol, 2 * vol, generator=g) + 0.5 * lab[None]
@@ -85,7 +87,8 @@ def synthetic_loaders(cfg, device, seed, vol):
                                          shift_os=cfg.t_intensity_shift_os, shift_prob=cfg.t_intensity_shift_prob,
                                          scale_f=cfg.t_intensity_scale_factors, scale_prob=cfg.t_intensity_scale_prob,
                                          image_threshold=-1e9, affine_prob=cfg.t_affine_prob,
-                                         affine_rotate=cfg.t_affine_rotate, affine_zoom=cfg.t_affine_zoom, affine_pad=0.0)
+                                         affine_rotate=cfg.t_affine_rotate, affine_zoom=cfg.t_affine_zoom, affine_pad=0.0,
+                                         intensity=intensity_config_from_args(cfg))
     else:
         loader_train = SyntheticLoader(cfg.synthetic_steps, cfg.n_images_per_batch, vol, cfg.in_chans, cfg.output_dim, seed)
     loader_val = SyntheticLoader(1, 1, vval, cfg.in_chans, cfg.output_dim, seed + 7, with_crop_info=False)
