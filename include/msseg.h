@@ -848,6 +848,35 @@ int msseg_intensity_aug(const float* x, const msseg_intensity_row* rows_host, co
                         int W, void* out, int out_dtype, void* workspace, size_t workspace_bytes, msseg_stream_t stream);
 int msseg_intensity_noise_bits(unsigned key_lo, unsigned key_hi, long long first, long long n, uint32_t* out, msseg_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Prediction -> the grid of the file it came from (csrc/restore.hip): the inverse of the dataset path's chain
+ * Orientationd(RAS) -> Spacingd -> CropForegroundd -> SpatialPadd in ONE launch (no reference counterpart: the reference's
+ * test_model zooms the cropped map to the uncropped size).  desc is a HOST pointer to one msseg_restore_desc, read before
+ * the call returns; it travels to the kernel as an argument.  src: uint8 [model] (src_is_logits 0, C ignored) or fp32
+ * [C][model] (src_is_logits 1); dst: uint8 [native], C-contiguous in the file array's order.
+ * Per native voxel n and oriented axis k, in double with one rounding per operation:
+ *   o = n[perm[k]], or native[perm[k]] - 1 - o when flip[k];  s = min(o * scale[k], grid[k] - 1)  (the spacing step rounds
+ *   the length, the last native voxels may land up to half a voxel beyond the grid);  m[k] = s + offset[k];
+ *   q[k] = floor(m[k] + 0.5).  Any q[k] outside [0, model[k]): the voxel was cropped away as air, dst = 0 in both modes.
+ * Nearest (labels): dst = src[q].
+ * Linear (logits): taps i0 = floor(m[k]) and i0 + 1, each clamped into [0, model[k] - 1], f[k] = (float)(m[k] - i0); per
+ *   channel fp32 lerps a + f * (b - a) along model axis 2, then 1, then 0 (msseg_resample_spacing's order); dst = the first
+ *   channel with the strictly greatest value (msseg_argmax_u8's rule).  [C][native] is never formed: the call reads src
+ *   through the cache and writes one byte per native voxel.
+ * MSSEG_EINVAL, with nothing launched: perm is not a permutation, a dimension < 1, a scale that is not finite or not > 0,
+ * C outside 1..255 with logits, native axis 0 or 1 longer than 65535.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct msseg_restore_desc {
+    int32_t native[3];  /* file array shape */
+    int32_t perm[3];    /* oriented axis k is native axis perm[k] */
+    int32_t flip[3];    /* oriented axis k runs backwards */
+    int32_t grid[3];    /* shape after the spacing resample, before crop + pad */
+    int32_t offset[3];  /* pad_before[k] - box_lo[k] */
+    int32_t model[3];   /* shape of src's spatial grid */
+    double  scale[3];   /* old / new spacing per oriented axis; 1.0 without a resample */
+} msseg_restore_desc;
+int msseg_restore_native_u8(const void* src, int src_is_logits, int C, const void* desc, uint8_t* dst, msseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@ including the crop centre record the reference's transform fork adds (``data/tra
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -356,6 +357,8 @@ def preprocess_volume(image, label, affine, cfg, device, filename="volume"):
         torch.zeros(image.shape[1:], dtype=torch.uint8, device=device)
     original_affine = np.array(affine, dtype=np.float64)
     aff = original_affine.copy()
+    native_shape = tuple(int(s) for s in image.shape[1:])
+    perm, flips, spacing_scale = (0, 1, 2), (False, False, False), (1.0, 1.0, 1.0)
     if cfg.in_chans == 1:
         perm, flips = df.ras_orientation(aff)
         aff = df.reorient_affine(aff, tuple(img.shape[1:]), perm, flips)
@@ -369,6 +372,7 @@ def preprocess_volume(image, label, affine, cfg, device, filename="volume"):
         new = voxel_dims(cfg)
         old = df.spacing_of(aff)
         ratio = [float(n) / float(o) for n, o in zip(new, old)]
+        spacing_scale = tuple(float(o) / float(n) for n, o in zip(new, old))
         out = [df.resample_shape(s, o, n) for s, o, n in zip(img.shape[1:], old, new)]
         if img.dtype != torch.float32:
             img, _ = hip.intensity_prep(img)                    # int16 -> fp32, values unchanged
@@ -380,6 +384,7 @@ def preprocess_volume(image, label, affine, cfg, device, filename="volume"):
     img, box = hip.intensity_prep(img, mode, cfg.t_ct_min, cfg.t_ct_max, norm)
     pad = normalised_zero(cfg)
     D, H, W = img.shape[1:]
+    grid_shape = (int(D), int(H), int(W))
     b6 = (0, 0, 0, D, H, W)
     if cfg.t_crop_foreground_img:
         b = box.cpu().tolist()
@@ -392,7 +397,34 @@ def preprocess_volume(image, label, affine, cfg, device, filename="volume"):
         lab = hip.crop_pad_copy(lab[None], b6, min_size, 0)[0][0]
         aff = df.shift_affine(aff, [b6[a] - before[a] for a in range(3)])
     return {"img": img, "lab": lab.contiguous(), "affine": aff, "original_affine": original_affine, "filename": filename,
-            "box": b6, "pad_before": tuple(before)}
+            "box": b6, "pad_before": tuple(before),
+            # the geometry restore_descriptor needs to map a prediction back onto the file's grid
+            "native_shape": native_shape, "orient": (tuple(int(p) for p in perm), tuple(bool(f) for f in flips)),
+            "spacing_scale": spacing_scale, "grid_shape": grid_shape, "model_shape": tuple(int(s) for s in lab.shape)}
+
+
+RESTORE_KEYS = ("native_shape", "orient", "spacing_scale", "grid_shape", "box", "pad_before", "model_shape")
+
+
+def restore_geometry(rec):
+    """the keys of a preprocess_volume record that restore_descriptor reads, without the tensors: what a batch carries as
+    its "restore" entry (with the file's affine in float64, which the native map is saved under)"""
+    return {**{k: rec[k] for k in RESTORE_KEYS}, "original_affine": np.array(rec["original_affine"], dtype=np.float64)}
+
+
+def restore_descriptor(rec):
+    """A preprocess_volume record, or any dict with its keys native_shape, orient, spacing_scale, grid_shape, box,
+    pad_before and model_shape (or lab, whose shape is then the model grid) -> hip.RestoreDesc, the msseg_restore_desc of
+    include/msseg.h: the inverse of the record's chain.  Pure host code."""
+    perm, flips = rec["orient"]
+    model = rec["model_shape"] if "model_shape" in rec else tuple(rec["lab"].shape)
+    d = hip.RestoreDesc()
+    for k in range(3):
+        d.native[k], d.perm[k], d.flip[k] = int(rec["native_shape"][k]), int(perm[k]), int(bool(flips[k]))
+        d.grid[k], d.model[k] = int(rec["grid_shape"][k]), int(model[k])
+        d.offset[k] = int(rec["pad_before"][k]) - int(rec["box"][k])
+        d.scale[k] = float(rec["spacing_scale"][k])
+    return d
 
 
 def build_cache(files, cfg, device):
@@ -563,6 +595,50 @@ class DeviceVolumeLoader:
                                        "filename_or_obj": [r["filename"]]},
                    "label_meta_dict": {"affine": _aff([r], "affine")},
                    "image_transforms": []}
+
+
+def output_name(path):
+    """the name test_model saves a case under: the file's base name behind its last "img" (the reference's rule,
+    engine/test.py:127 there)"""
+    return os.path.split(str(path))[-1].split("img")[-1]
+
+
+def check_output_names(files):
+    """two cases of one output name would overwrite each other's maps: a ValueError names both files"""
+    seen = {}
+    for item in files:
+        name = output_name(item["image"])
+        if name in seen:
+            raise ValueError(f"{item['image']} and {seen[name]} would both be saved as {name!r}")
+        seen[name] = item["image"]
+
+
+class FileCaseLoader:
+    """test-time inference on files: one case per step (batch 1), read and preprocessed when the step asks for it and not
+    kept afterwards (no whole-set cache); labels, if the data list names any, are ignored.  The batch carries the record's
+    geometry as "restore", which engine.test.test_model maps the prediction back onto the file's grid with."""
+
+    def __init__(self, files, cfg, device):
+        self.files, self.cfg, self.dev = list(files), cfg, device
+        check_output_names(self.files)
+
+    def __len__(self):
+        return len(self.files)
+
+    def __iter__(self):
+        from . import data_files as df
+        for item in self.files:
+            image, _, aff = df.load_case({"image": item["image"]})
+            if image.shape[0] != self.cfg.in_chans:
+                raise ValueError(f"{item['image']}: {image.shape[0]} channel(s), --in_chans is {self.cfg.in_chans}")
+            r = preprocess_volume(image, None, aff, self.cfg, self.dev, filename=item["image"])
+            batch = {"image": r["img"][None],
+                     "image_meta_dict": {"original_affine": _aff([r], "original_affine"), "affine": _aff([r], "affine"),
+                                         "filename_or_obj": [r["filename"]]},
+                     "image_transforms": [], "restore": restore_geometry(r)}
+            del r, image
+            yield batch
+            del batch
 
 
 def crop_mode(cfg):

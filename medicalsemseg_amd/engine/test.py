@@ -13,7 +13,17 @@ Post-processing of the arg-max maps (an addition of this build, off by default) 
 class 1, 2, .. (MONAI ``FillHoles``, ``--post_hole_connectivity`` 6 or 26).  Any of the three switches it on:
 ``eval_model`` then reports ``ppDice`` and ``ppHdorffDist`` of the processed maps next to the unchanged meters and saves
 the processed map; ``test_model`` processes on the model grid, before the resample and before saving; ``run_validation``
-(engine/val.py) adds ``ppDice``."""
+(engine/val.py) adds ``ppDice``.
+
+File input (an addition of this build): a batch of ``test_model`` that carries a ``"restore"`` entry (the geometry of its
+``data_device.preprocess_volume`` record, ``data_device.restore_geometry``; one record per batch) also gets a map on the
+grid of the file it came from, written to ``test_output/Fold<k>/native/<name>`` under the file's full affine (translation
+kept; ``pred/``, ``img/`` and ``rs/`` keep the reference's zeroed translation).  ``hip.restore_native_u8`` undoes pad,
+foreground crop, spacing resample and RAS reorientation in one launch.  ``--restore_mode nearest`` (default): arg max on
+the model grid, post-processing if enabled, then the label map is restored.  ``--restore_mode linear``: the blended logits
+are resampled trilinearly and the arg max is taken per native voxel inside the kernel (nnU-Net's order), then
+post-processing runs on the native map; ``pred/`` then holds the unprocessed model-grid arg max.  Batches without the entry
+behave as before."""
 from __future__ import annotations
 
 import os
@@ -22,6 +32,7 @@ import numpy as np
 import torch
 
 from .. import hip, metrics
+from ..data_device import normalised_zero, output_name
 from ..utils import misc
 from .train import _metric_update
 from .utils import sliding_window_inference
@@ -121,20 +132,40 @@ def eval_model(inferer, model, data_loader, criterion, device, cfg, log_writer=N
 def test_model(model, data_loader, device, cfg, log_writer=None):
     model.eval()
     air_cval = (0.0 - cfg.t_norm_mean) / cfg.t_norm_std if cfg.t_normalize else 0.0
+    restore_mode = getattr(cfg, "restore_mode", "nearest")
+    only_largest = not (int(getattr(cfg, "post_min_size", 0)) > 1 or getattr(cfg, "post_fill_holes", False))
     for i, batch in enumerate(data_loader):
         inputs = batch["image"].to(device, non_blocking=True)
         aff_xyz = misc.get_affine_xyz(batch["image_meta_dict"]["original_affine"]).float().to(device)
-        img_name = os.path.split(str(batch["image_meta_dict"]["filename_or_obj"][0]))[-1].split("img")[-1]
+        img_name = output_name(batch["image_meta_dict"]["filename_or_obj"][0])
+        restore = batch.get("restore") if isinstance(batch, dict) else None
         with torch.no_grad():
             outputs = sliding_window_inference(inputs, aff_xyz, cfg.vol_size, cfg.batch_size_val, model,
-                                               overlap=cfg.val_infer_overlap, mode="gaussian", cval=air_cval,
+                                               overlap=cfg.val_infer_overlap, mode="gaussian",
+                                               cval=normalised_zero(cfg) if restore is not None else air_cval,
                                                mirror_axes=getattr(cfg, "infer_mirror_axes", ()))
         seg = label_map(outputs)
-        if post_enabled(cfg):
-            only_largest = not (int(getattr(cfg, "post_min_size", 0)) > 1 or getattr(cfg, "post_fill_holes", False))
+        # with --restore_mode linear the clean-up runs on the native map instead (below); pred/ stays the raw arg max
+        if post_enabled(cfg) and not (restore is not None and restore_mode == "linear"):
             seg, stats = postprocess(seg, cfg, return_stats=True)
             print(("keep largest component, " if only_largest else "post-processing, ") + img_name + ": "
                   + _stats_line(stats, cfg))
+        seg_native = None
+        if restore is not None:
+            # the file's own grid: one launch undoes pad, foreground crop, spacing and orientation (hip.restore_native_u8)
+            if restore_mode == "linear":
+                # the sliding window blends in fp32 and returns its accumulator: no copy is made here (a view of it only when
+                # the case is smaller than the window, which --t_spatial_pad rules out); another dtype would mean a hidden
+                # [C][model] fp32 copy, so it is refused
+                if outputs.dtype != torch.float32:
+                    raise TypeError(f"--restore_mode linear reads fp32 logits, the sliding window returned {outputs.dtype}")
+                seg_native = hip.restore_native_u8(outputs[0].contiguous(), restore, "linear")
+                if post_enabled(cfg):
+                    seg_native, stats = postprocess(seg_native, cfg, return_stats=True)
+                    print(("keep largest component, " if only_largest else "post-processing, ") + img_name + " (native grid): "
+                          + _stats_line(stats, cfg))
+            else:
+                seg_native = hip.restore_native_u8(seg, restore, "nearest")
         seg_rs = None
         if getattr(cfg, "t_voxel_spacings", None):
             target = None
@@ -152,6 +183,14 @@ def test_model(model, data_loader, device, cfg, log_writer=None):
                 _save_volume(os.path.join(out_dir, "img"), img_name, inputs.squeeze().float().cpu().numpy(), aff)
             if seg_rs is not None:
                 _save_volume(os.path.join(out_dir, "rs"), img_name, seg_rs.cpu().numpy(), _affine0(meta.get("original_affine")))
+            if seg_native is not None:
+                # the file's full affine, translation kept: the map overlays the input in a viewer
+                full = restore["original_affine"] if "original_affine" in restore else meta["original_affine"]
+                full = np.array(torch.as_tensor(full).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 4, 4)[0]
+                _save_volume(os.path.join(out_dir, "native"), img_name, seg_native.cpu().numpy(), full)
+        if restore is not None:
+            # a file case is as large as its scan: let go of its tensors before the loader preprocesses the next one
+            del batch, inputs, outputs, seg, seg_native, seg_rs
     return None
 
 

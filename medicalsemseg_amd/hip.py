@@ -169,6 +169,7 @@ SIGNATURES = {
     "msseg_hd_directed_hist": ([_vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _i, _vp], _i),
     "msseg_keep_largest_u8": ([_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "msseg_postprocess_u8": ([_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "msseg_restore_native_u8": ([_vp, _i, _i, _vp, _vp, _vp], _i),
     "msseg_ktimer_enable": ([_i], _i),
     "msseg_ktimer_reset": ([], _i),
     "msseg_ktimer_count": ([], _i),
@@ -1419,6 +1420,39 @@ def majority_vote_u8(labels: torch.Tensor, n_classes: int) -> torch.Tensor:
     out = torch.empty(labels.shape[1:], dtype=torch.uint8, device=labels.device)
     _ck(lib().msseg_majority_vote_u8(_p(labels), labels.shape[0], out.numel(), n_classes, _p(out), _stream()),
         "majority_vote_u8")
+    return out
+
+
+class RestoreDesc(C.Structure):
+    """mirror of msseg_restore_desc (include/msseg.h); data_device.restore_descriptor builds it from a record"""
+    _fields_ = [("native", C.c_int32 * 3), ("perm", C.c_int32 * 3), ("flip", C.c_int32 * 3), ("grid", C.c_int32 * 3),
+                ("offset", C.c_int32 * 3), ("model", C.c_int32 * 3), ("scale", C.c_double * 3)]
+
+
+def restore_native_u8(src: torch.Tensor, desc_or_record, mode: str = "nearest") -> torch.Tensor:
+    """A prediction on the model grid -> uint8 [native], the grid of the file array: the inverse of
+    data_device.preprocess_volume (pad, foreground crop, spacing resample, RAS reorientation) in one launch.
+    mode "nearest": src uint8 [D, H, W], a label map.  mode "linear": src fp32 [C, D, H, W], logits; they are resampled
+    trilinearly and the first arg max is taken per native voxel, without forming [C, native].  Voxels the foreground crop
+    removed are class 0.  desc_or_record: a RestoreDesc or anything data_device.restore_descriptor accepts.  Allocates the
+    output only."""
+    if mode not in ("nearest", "linear"):
+        raise ValueError(f"restore_native_u8: mode {mode!r}: 'nearest' or 'linear'")
+    _need_gpu(src)
+    if isinstance(desc_or_record, RestoreDesc):
+        desc = desc_or_record
+    else:
+        from .data_device import restore_descriptor
+        desc = restore_descriptor(desc_or_record)
+    logits = mode == "linear"
+    assert src.is_contiguous() and src.dtype == (torch.float32 if logits else torch.uint8) and src.dim() == (4 if logits else 3), \
+        "restore_native_u8: src must be a contiguous uint8 [D, H, W] (nearest) or fp32 [C, D, H, W] (linear) tensor"
+    if tuple(src.shape[-3:]) != tuple(desc.model):
+        raise ValueError(f"restore_native_u8: src's grid {tuple(src.shape[-3:])} is not the descriptor's {tuple(desc.model)}")
+    # the entry point validates the descriptor and names what is wrong with it; a negative length only has to get that far
+    out = torch.empty([max(int(v), 0) for v in desc.native], dtype=torch.uint8, device=src.device)
+    _ck(lib().msseg_restore_native_u8(_p(src), int(logits), int(src.shape[0]) if logits else 0, C.addressof(desc), _p(out),
+                                      _stream()), "restore_native_u8")
     return out
 
 

@@ -1,7 +1,7 @@
 """CLI of the training / evaluation drivers: every flag of ``/root/reference/utils/arguments.py:29-313`` with
 the same name, type, default and list-collapsing rule (``:19-24``: a list argument of length 1 becomes a scalar,
 longer lists become tuples), declared as a table; plus a few flags of this build (synthetic data, compute
-dtype, hipGraph replay, post-processing, rotation + zoom in the device crop gather, mirror test-time augmentation, intensity augmentation).  Flags whose subsystem is out of the hot-path scope (learned class vectors, MONAI
+dtype, hipGraph replay, post-processing, rotation + zoom in the device crop gather, mirror test-time augmentation, intensity augmentation, file inference).  Flags whose subsystem is out of the hot-path scope (learned class vectors, MONAI
 transforms, Neptune) are accepted and ignored so reference command lines keep working."""
 from __future__ import annotations
 
@@ -77,6 +77,13 @@ _SPEC = {
         ("--t_blur_prob", "v", 0.0, F), ("--t_blur_sigma", "l", [0.5, 1.0], F), ("--t_blur_channel_prob", "v", 0.5, F),
         ("--t_contrast_prob", "v", 0.0, F), ("--t_contrast_range", "l", [0.75, 1.25], F),
         ("--t_gamma_invert_prob", "v", 0.0, F), ("--t_gamma_prob", "v", 0.0, F), ("--t_gamma_range", "l", [0.7, 1.5], F),
+    ],
+    "file inference": [  # run_predict.py: the files of a data list (engine/test.py, csrc/restore.hip)
+        # the section of the data list to predict (labels of "validation" / "training" are ignored)
+        ("--test_section", "v", "test", S),
+        # how a prediction reaches the file's grid: nearest = the label map is restored; linear = the logits are resampled
+        # trilinearly and the arg max is taken per native voxel
+        ("--restore_mode", "c", "nearest", S, ("nearest", "linear")),
     ],
 }
 
