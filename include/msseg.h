@@ -705,6 +705,31 @@ int msseg_hd_directed_hist(const uint8_t* edges_src, const uint8_t* edges_tgt, i
                            msseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Surface distances in millimetres (metrics.surface_metrics: HD percentile, average symmetric surface distance, normalised
+ * surface Dice of one pair of label maps on an anisotropic grid).  Edge maps, box and surface sizes are hd_edges'.
+ * sd_directed_mm: d2map[bz][by][bx] (box-local, dense, double) = the exact squared Euclidean distance in physical units from
+ *            every class-`cls` surface voxel of `edges_tgt` to the nearest class-`cls` surface voxel of `edges_src` inside
+ *            box6 (as hd_directed_hist's); -1 at every other voxel of the box; +inf at the surface voxels when `edges_src`
+ *            has no class-`cls` voxel in the box.  spacing3 = {sz, sy, sx}: HOST doubles, one per tensor axis, finite and
+ *            positive.  A term is (s k)^2 with k the integer voxel offset, the sum is (x term + y term) + z term, every
+ *            operation rounds once (no contraction).  Workspace: 10 bytes per box voxel (sd_directed_workspace_bytes).
+ * sd_summary: reduces such a map of n entries on the device into out16 (DEVICE, 16 slots of 8 bytes):
+ *            [0] number of entries >= 0 (surface voxels), [1] number of +inf entries, [2] sum of sqrt(d2) over the finite
+ *            entries (double; fixed-shape two-level reduction: same bits on every run), [3 + j] number of entries with
+ *            sqrt(d2) <= tolerances[j] (compared in double on the square root), [11 + r] the order statistic of d2 at the
+ *            zero-based rank ranks[r] (double; NaN when the rank is past the last entry), [15] 0.  tolerances (ntol <= 8) and
+ *            ranks (nrank <= 4, >= 0) are HOST arrays.  Order statistics by radix select over the doubles' bit patterns;
+ *            counts by integer atomics.  scratch: DEVICE, 8-byte aligned, sd_summary_scratch_bytes(), no initialisation.
+ * ------------------------------------------------------------------------------------------- */
+size_t msseg_sd_directed_workspace_bytes(int bz, int by, int bx);
+int msseg_sd_directed_mm(const uint8_t* edges_src, const uint8_t* edges_tgt, int cls, int D, int H, int W, const int* box6,
+                         const double* spacing3, void* workspace, size_t workspace_bytes, double* d2map,
+                         msseg_stream_t stream);
+size_t msseg_sd_summary_scratch_bytes(void);
+int msseg_sd_summary(const double* d2map, long long n, const double* tolerances, int ntol, const long long* ranks, int nrank,
+                     void* scratch, size_t scratch_bytes, void* out16, msseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Keep the largest connected component per class (csrc/components.hip): MONAI KeepLargestConnectedComponent(
  * applied_labels=1..n_classes-1, is_onehot=False, independent=True) on a uint8 label map [D][H][W].
  * For each class c in 1..n_classes-1 independently: the connected components of lab == c (connectivity 6: face

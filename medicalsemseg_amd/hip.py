@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -167,6 +167,10 @@ SIGNATURES = {
     "msseg_hd_edges": ([_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "msseg_hd_directed_workspace_bytes": ([_i, _i, _i], _sz),
     "msseg_hd_directed_hist": ([_vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _i, _vp], _i),
+    "msseg_sd_directed_workspace_bytes": ([_i, _i, _i], _sz),
+    "msseg_sd_directed_mm": ([_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp], _i),
+    "msseg_sd_summary_scratch_bytes": ([], _sz),
+    "msseg_sd_summary": ([_vp, _ll, _vp, _i, _vp, _i, _vp, _sz, _vp, _vp], _i),
     "msseg_keep_largest_u8": ([_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "msseg_postprocess_u8": ([_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "msseg_restore_native_u8": ([_vp, _i, _i, _vp, _vp, _vp], _i),
@@ -1479,6 +1483,55 @@ def hd_directed_hist(edges_src, edges_tgt, cls: int, box, hist: torch.Tensor):
     _ck(lib().msseg_hd_directed_hist(_p(edges_src), _p(edges_tgt), int(cls), D, H, W, b6, _p(ws), ws.numel(), _p(hist),
                                      hist.numel(), _stream()), "hd_directed_hist")
     return hist
+
+
+def sd_directed_mm(edges_src, edges_tgt, cls: int, box, spacing, workspace_bytes: Optional[int] = None):
+    """float64 map [bz, by, bx] over box = (z0, y0, x0, z1, y1, x1): the squared distance in physical units (spacing: three
+    floats, one per tensor axis) from every class-`cls` surface voxel of edges_tgt to the nearest class-`cls` surface voxel of
+    edges_src (+inf when edges_src has none), -1 at every other voxel.  workspace_bytes: pass less than the entry point needs
+    (for its refusal); default: what it needs."""
+    _need_gpu(edges_src, edges_tgt)
+    assert edges_src.dtype == torch.uint8 and edges_tgt.dtype == torch.uint8 and edges_src.dim() == 3 and \
+        edges_src.shape == edges_tgt.shape and edges_src.is_contiguous() and edges_tgt.is_contiguous()
+    D, H, W = edges_src.shape
+    box = [int(v) for v in box]
+    bz, by, bx = box[3] - box[0], box[4] - box[1], box[5] - box[2]
+    need = lib().msseg_sd_directed_workspace_bytes(max(bz, 0), max(by, 0), max(bx, 0))
+    ws = workspace(need, edges_src.device)
+    # the entry point validates the box and names what is wrong with it; a negative extent only has to get that far
+    out = torch.empty(max(bz, 0), max(by, 0), max(bx, 0), dtype=torch.float64, device=edges_src.device)
+    b6 = (C.c_int * 6)(*box)
+    s3 = (C.c_double * 3)(*[float(v) for v in spacing])
+    _ck(lib().msseg_sd_directed_mm(_p(edges_src), _p(edges_tgt), int(cls), D, H, W, b6, s3, _p(ws),
+                                   ws.numel() if workspace_bytes is None else int(workspace_bytes), _p(out), _stream()),
+        "sd_directed_mm")
+    return out
+
+
+class SurfaceSummary(NamedTuple):
+    n: int                       # surface voxels (entries >= 0 of the map)
+    n_inf: int                   # of them: +inf
+    sum: float                   # sum of sqrt(d2) over the finite ones
+    within: np.ndarray           # int64 [len(tolerances)]: entries with sqrt(d2) <= tolerance
+    d2_at_rank: np.ndarray       # float64 [len(ranks)]: order statistics of d2 (NaN: rank past the last entry)
+
+
+def sd_summary(d2map: torch.Tensor, tolerances=(), ranks=()) -> SurfaceSummary:
+    """reduces a map of sd_directed_mm on the device; 128 bytes come to the host"""
+    import numpy as np
+    _need_gpu(d2map)
+    assert d2map.dtype == torch.float64 and d2map.is_contiguous()
+    tolerances, ranks = [float(t) for t in tolerances], [int(r) for r in ranks]
+    scratch = torch.empty(lib().msseg_sd_summary_scratch_bytes(), dtype=torch.uint8, device=d2map.device)
+    out = torch.empty(16, dtype=torch.int64, device=d2map.device)
+    tol = (C.c_double * max(len(tolerances), 1))(*tolerances)
+    rk = (C.c_longlong * max(len(ranks), 1))(*ranks)
+    _ck(lib().msseg_sd_summary(_p(d2map), d2map.numel(), tol, len(tolerances), rk, len(ranks), _p(scratch), scratch.numel(),
+                               _p(out), _stream()), "sd_summary")
+    rec = out.cpu().numpy()
+    f = rec.view(np.float64)
+    return SurfaceSummary(int(rec[0]), int(rec[1]), float(f[2]), rec[3:3 + len(tolerances)].copy(),
+                          f[11:11 + len(ranks)].copy())
 
 
 def keep_largest_u8(lab: torch.Tensor, n_classes: int, connectivity: int = 26, out: Optional[torch.Tensor] = None,

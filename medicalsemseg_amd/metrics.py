@@ -18,23 +18,34 @@ import torch
 from . import hip
 
 
+def _percentile_ranks(n: int, q: float):
+    """np.percentile of n values at q, method 'linear': -> (prev, nxt, t), the zero-based ranks of the two order statistics it
+    interpolates between and the weight of the second (numpy's get_virtual_index and its clipping)"""
+    quant = np.true_divide(q, 100.0)
+    vi = (n - 1) * quant
+    prev = int(np.floor(vi))
+    nxt = min(prev + 1, n - 1)
+    prev = max(min(prev, n - 1), 0)
+    return prev, nxt, np.float64(vi - np.floor(vi))
+
+
+def _lerp(a, b, t) -> float:
+    """numpy's _lerp of the order statistics a <= b"""
+    d = b - a
+    r = a + d * t
+    if t >= 0.5:
+        r = b - d * (1 - t)
+    return float(r)
+
+
 def _percentile_from_hist(counts: np.ndarray, q: float) -> float:
     """np.percentile(sqrt(d2) for every counted d2, q) (method 'linear', numpy's own arithmetic) from counts[d2]"""
     n = int(counts.sum())
     cum = np.cumsum(counts)
-    quant = np.true_divide(q, 100.0)
-    vi = (n - 1) * quant                      # numpy: get_virtual_index of the 'linear' method
-    prev = int(np.floor(vi))
-    nxt = min(prev + 1, n - 1)
-    prev = max(min(prev, n - 1), 0)
+    prev, nxt, t = _percentile_ranks(n, q)
     a = np.sqrt(np.float64(int(np.searchsorted(cum, prev + 1, side="left"))))    # order statistic `prev` (0-based)
     b = np.sqrt(np.float64(int(np.searchsorted(cum, nxt + 1, side="left"))))
-    t = np.float64(vi - np.floor(vi))
-    d = b - a
-    r = a + d * t
-    if t >= 0.5:                               # numpy's _lerp
-        r = b - d * (1 - t)
-    return float(r)
+    return _lerp(a, b, t)
 
 
 def hausdorff95(pred: torch.Tensor, label: torch.Tensor, n_classes: int, percentile: float = 95.0) -> np.ndarray:
@@ -79,6 +90,59 @@ def hausdorff95(pred: torch.Tensor, label: torch.Tensor, n_classes: int, percent
                 d.append(_percentile_from_hist(counts[:-1], percentile))
             hd[b, c] = max(d)
     return hd
+
+
+def surface_metrics(pred: torch.Tensor, label: torch.Tensor, n_classes: int, spacing, nsd_tolerance, percentile: float = 95.0):
+    """Surface metrics in millimetres of ONE pair of uint8 label maps [D, H, W] on the GPU (no CPU fallback; the scipy
+    restatement is tests/surface_ref.py).  spacing: three floats in tensor-axis order; nsd_tolerance: one float, or one per
+    class.  -> {"hd_mm", "assd_mm", "nsd"}: float64 [n_classes] (host).  Per class, with d_pg the distances of the
+    prediction's surface voxels to the label's surface and d_gp the reverse (MONAI's definitions):
+
+    * hd_mm   = max(np.percentile(d_pg, percentile), np.percentile(d_gp, percentile)), method 'linear'
+    * assd_mm = (sum d_pg + sum d_gp) / (|d_pg| + |d_gp|)         (compute_average_surface_distance(symmetric=True))
+    * nsd     = (#{d_pg <= tau} + #{d_gp <= tau}) / (|d_pg| + |d_gp|)   (compute_surface_dice: voxels, not surface area)
+
+    A class in neither map gives NaN, NaN, NaN.  A class in exactly one map gives inf, inf, 0: on purpose NOT what
+    ``hausdorff95`` does, which lets such a class fall out of the mean as NaN -- a scorer must not flatter a prediction that
+    missed an organ.  The distance maps stay on the device (``msseg_sd_directed_mm``); per class and direction one 128-byte
+    record comes back (``msseg_sd_summary``): counts, the sum, and the two order statistics of d^2 the percentile
+    interpolates between, whose square roots and lerp are taken here as ``_percentile_from_hist`` does."""
+    if not pred.is_cuda or not label.is_cuda:
+        raise RuntimeError("surface_metrics runs on the GPU only (no CPU fallback; the scipy restatement is "
+                           "tests/surface_ref.py)")
+    if pred.dim() != 3 or pred.shape != label.shape or pred.dtype != torch.uint8 or label.dtype != torch.uint8:
+        raise ValueError("surface_metrics: pred and label must be uint8 maps [D, H, W] of one shape")
+    spacing = [float(v) for v in spacing]
+    if len(spacing) != 3:
+        raise ValueError("surface_metrics: spacing must hold three values (tensor-axis order)")
+    tau = np.asarray(nsd_tolerance, dtype=np.float64).reshape(-1)
+    if tau.size not in (1, n_classes):
+        raise ValueError(f"surface_metrics: nsd_tolerance must hold 1 or {n_classes} values")
+    tau = np.broadcast_to(tau, (n_classes,))
+    out = {k: np.full(n_classes, np.nan, dtype=np.float64) for k in ("hd_mm", "assd_mm", "nsd")}
+    ep, eg, stats = hip.hd_edges(pred.contiguous(), label.contiguous(), n_classes)
+    st = stats.cpu().numpy()
+    for c in range(n_classes):
+        n_p, n_g = int(st[c, 6]), int(st[c, 7])
+        if n_p == 0 and n_g == 0:
+            continue
+        if n_p == 0 or n_g == 0:
+            out["hd_mm"][c], out["assd_mm"][c], out["nsd"][c] = np.inf, np.inf, 0.0
+            continue
+        box = (int(st[c, 0]), int(st[c, 1]), int(st[c, 2]), int(st[c, 3]) + 1, int(st[c, 4]) + 1, int(st[c, 5]) + 1)
+        hd, total, within = [], np.float64(0.0), 0
+        for src, tgt, n in ((eg, ep, n_p), (ep, eg, n_g)):    # pred -> gt, then gt -> pred
+            prev, nxt, t = _percentile_ranks(n, percentile)
+            rec = hip.sd_summary(hip.sd_directed_mm(src, tgt, c, box, spacing), [tau[c]], [prev, nxt])
+            assert rec.n == n and rec.n_inf == 0, "a surface voxel found no voxel of a non-empty surface"
+            a, b = np.sqrt(rec.d2_at_rank)
+            hd.append(_lerp(a, b, t))
+            total = total + np.float64(rec.sum)
+            within += int(rec.within[0])
+        out["hd_mm"][c] = max(hd)
+        out["assd_mm"][c] = total / np.float64(n_p + n_g)
+        out["nsd"][c] = np.float64(within) / np.float64(n_p + n_g)
+    return out
 
 
 def hausdorff_mean(hd: np.ndarray):

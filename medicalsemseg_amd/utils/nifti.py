@@ -102,15 +102,9 @@ def _quatern_to_mat(b, c, d, qfac, pixdim):
     return R * vox[None, :]
 
 
-def load_nifti(path: str):
-    """-> (array, affine).  Reads little-endian single-file NIfTI-1: up to 7 dimensions (a 4-D file keeps its channels
-    last), ``scl_slope`` / ``scl_inter`` applied (-> float32) when the slope is finite and non-zero and the pair is not the
-    identity, affine from the sform rows when ``sform_code > 0``, else from the qform quaternion and ``pixdim`` when
-    ``qform_code > 0``, else ``diag(pixdim)``.  What save_nifti writes reads back unchanged."""
-    opener = gzip.open if path.endswith(".gz") else open
-    with opener(path, "rb") as f:
-        raw = f.read()
-    if struct.unpack("<i", raw[:4])[0] != 348 or raw[344:348] != b"n+1\0":
+def _parse_header(raw):
+    """the first 348 bytes of a little-endian single-file NIfTI-1 -> (shape, dtype, data offset, scl_slope, scl_inter, affine)"""
+    if len(raw) < 348 or struct.unpack("<i", raw[:4])[0] != 348 or raw[344:348] != b"n+1\0":
         raise ValueError("not a little-endian single-file NIfTI-1")
     dim = struct.unpack("<8h", raw[40:56])
     code, bits = struct.unpack("<2h", raw[70:74])
@@ -122,9 +116,6 @@ def load_nifti(path: str):
     if code not in _CODES:
         raise ValueError(f"unsupported NIfTI datatype code {code}")
     dt = _CODES[code].newbyteorder("<")
-    data = np.frombuffer(raw, dtype=dt, count=int(np.prod(shape)), offset=off).reshape(shape, order="F")
-    if np.isfinite(slope) and slope != 0.0 and np.isfinite(inter) and not (slope == 1.0 and inter == 0.0):
-        data = data.astype(np.float32) * np.float32(slope) + np.float32(inter)
     aff = np.eye(4)
     if sform_code > 0:
         aff[:3] = np.array(struct.unpack("<12f", raw[280:328])).reshape(3, 4)
@@ -134,4 +125,28 @@ def load_nifti(path: str):
         aff[:3, 3] = (qx, qy, qz)
     else:
         aff[:3, :3] = np.diag([v if v > 0 else 1.0 for v in pixdim[1:4]])
+    return shape, dt, off, slope, inter, aff
+
+
+def read_nifti_header(path: str):
+    """-> (shape, affine) as load_nifti gives them, from the header alone (a .gz is inflated only that far)"""
+    opener = gzip.open if path.endswith(".gz") else open
+    with opener(path, "rb") as f:
+        raw = f.read(348)
+    shape, _, _, _, _, aff = _parse_header(raw)
+    return tuple(shape), aff
+
+
+def load_nifti(path: str):
+    """-> (array, affine).  Reads little-endian single-file NIfTI-1: up to 7 dimensions (a 4-D file keeps its channels
+    last), ``scl_slope`` / ``scl_inter`` applied (-> float32) when the slope is finite and non-zero and the pair is not the
+    identity, affine from the sform rows when ``sform_code > 0``, else from the qform quaternion and ``pixdim`` when
+    ``qform_code > 0``, else ``diag(pixdim)``.  What save_nifti writes reads back unchanged."""
+    opener = gzip.open if path.endswith(".gz") else open
+    with opener(path, "rb") as f:
+        raw = f.read()
+    shape, dt, off, slope, inter, aff = _parse_header(raw)
+    data = np.frombuffer(raw, dtype=dt, count=int(np.prod(shape)), offset=off).reshape(shape, order="F")
+    if np.isfinite(slope) and slope != 0.0 and np.isfinite(inter) and not (slope == 1.0 and inter == 0.0):
+        data = data.astype(np.float32) * np.float32(slope) + np.float32(inter)
     return data, aff

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Test-time inference on the files of a Decathlon data list: what ``run_test.py`` does for ``--synthetic`` volumes (build the
 model, load ``cfg.resume``, run ``engine.test.test_model``), fed by files.  The section ``--test_section`` of the data list
-(``--data_path`` / ``--task`` / ``--json_list``) is dealt to the ranks; every case is loaded, preprocessed on the device,
+(``--data_path`` / ``--task`` / ``--json_list``; ``validation`` without such a section: the held-out cases of fold
+``--cv_fold``) is dealt to the ranks; every case is loaded, preprocessed on the device,
 predicted, mapped back onto its file's grid (``--restore_mode``) and saved before the next one is read.
 
     python run_predict.py --data_path /data --task Task09_Spleen --model UNet --output_dim 2 --vol_size 96 \
@@ -26,6 +27,15 @@ from medicalsemseg_amd.utils import misc
 from medicalsemseg_amd.utils.arguments import get_args
 
 
+def section_files(json_path, section, seed, cv_max_folds, cv_fold):
+    """the cases of a data-list section; "validation" on a data list without that section is the held-out part of fold
+    cv_fold of the seeded split, as data_device.dataset_file_lists (run_training.py, run_evaluation.py) resolves it, so that
+    a fold's own validation cases can be predicted, and then scored, with Decathlon's dataset.json as it comes"""
+    if section == "validation" and not data_files.has_key(json_path, "validation"):
+        return data_files.cv_split(data_files.load_datalist(json_path, "training"), seed, cv_max_folds, cv_fold)[1]
+    return data_files.load_datalist(json_path, section)
+
+
 def main(cfg):
     misc.init_distributed_mode(cfg)
     if not torch.cuda.is_available():
@@ -39,7 +49,7 @@ def main(cfg):
     cfg.eval = True
     misc.load_model(cfg, model)
     js = data_files.datalist_path(cfg.data_path, cfg.task, cfg.json_list)
-    files = data_files.load_datalist(js, cfg.test_section)
+    files = section_files(js, cfg.test_section, cfg.seed, cfg.cv_max_folds, cfg.cv_fold)
     data_device.check_output_names(files)                        # over all ranks' files, before they are dealt
     mine = data_files.partition(files, misc.get_world_size(), misc.get_rank(), even_divisible=False)
     print(f"{js}: {len(files)} case(s) in \"{cfg.test_section}\", {len(mine)} on this rank")
