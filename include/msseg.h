@@ -802,6 +802,9 @@ int msseg_aug_crop_batch(const float* img, const uint8_t* lab, int C, int VD, in
  * pick_voxels: rows[i] = msseg_pick_row; mode 1 / 0: the rank-th foreground / background voxel (flat order) of slice z of
  *            volume vol; mode 2: rank IS the in-slice flat index.  out[i][8] = {centre z, y, x (MONAI correct_crop_centers
  *            clamp for the cubic roi R), crop start z, y, x, z, in-slice flat index of the voxel (-1: rank beyond the count)}.
+ * slab_counts_rule / pick_voxels_rule: the two above with the image side of a background candidate chosen by bg_rule:
+ *            0 = img0 > threshold (what the entry points without _rule forward), 1 = img0 != threshold: the non-zero mask of
+ *            a z-scored cache (msseg_zscore_apply), whose in-mask values have either sign.
  * aug_crop_multi: msseg_aug_crop_batch over many volumes: row i reads volume rows[i].vol at the crop start picks[i][3..5]
  *            (clamped into the volume) with the row's flips / rotk / shift / scale; out_img [npatch][C][R][R][R] fp32 or bf16,
  *            out_lab fp32 [npatch][1][R][R][R].  One launch per batch.  Precondition (the tables live on the device, so the
@@ -830,10 +833,45 @@ int msseg_slab_counts(const float* img0, const uint8_t* lab, int D, int H, int W
                       msseg_stream_t stream);
 int msseg_pick_voxels(const void* volumes, int nvol, const void* rows, int nrows, int R, float threshold, int* out,
                       msseg_stream_t stream);
+int msseg_slab_counts_rule(const float* img0, const uint8_t* lab, int D, int H, int W, float threshold, int bg_rule, int* counts,
+                           msseg_stream_t stream);
+int msseg_pick_voxels_rule(const void* volumes, int nvol, const void* rows, int nrows, int R, float threshold, int bg_rule,
+                           int* out, msseg_stream_t stream);
 int msseg_aug_crop_multi(const void* volumes, int nvol, const void* rows, const int* picks, int npatch, int C, void* out_img,
                          int out_dtype, float* out_lab, int R, msseg_stream_t stream);
 int msseg_aug_crop_affine(const void* volumes, int nvol, const void* rows, const int* picks, const double* mats, int npatch,
                           int C, void* out_img, int out_dtype, float* out_lab, int R, float pad_value, msseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Per-volume z-score over the non-zero voxels (csrc/volume_stats.hip): the last step of the dataset path's preprocessing
+ * for MR data (--t_zscore / --t_zscore_clip; nnU-Net's ZScoreNormalization with use_mask_for_norm, per channel of each
+ * volume; no reference counterpart: the reference normalises per cropped patch).  x: fp32 [C][V], 16-byte aligned,
+ * 1 <= C <= 1024, 1 <= V < 2^32.  The mask of a channel is x != 0 (-0.0 is outside it), n its size.  Semantics:
+ * tests/zscore_ref.py.  Everything is enqueued on the stream; nothing is read back.  scratch:
+ * msseg_volume_stats_scratch_bytes(C) bytes, 8-byte aligned, shared by select_f32 and masked_moments (calls on one stream).
+ * select_f32: exact order statistics of the masked values of every channel (radix select, 4 passes over x).  Either
+ *            `ranks` (HOST, 1..4 zero-based ranks, percentages NULL) or `percentages` (HOST, 1..2 values q in [0, 100], ranks
+ *            NULL): then the ranks are k = floor(h) and min(k + 1, n - 1) per percentage, h = q / 100 * (n - 1), formed on the
+ *            device from n.  out8 (device) [C][8] doubles = {n, the up to 4 order statistics in the order asked for (k, k + 1
+ *            of the first percentage, then of the second; NaN: rank >= n or not asked for), P of the first and of the second
+ *            percentage, 0}; P = x_(k) + (h - k) (x_(k+1) - x_(k)) in double, rounded once to fp32 (numpy's "linear"
+ *            percentile); a slot whose percentile is not formed (ranks given, no second percentage, n == 0) holds -inf
+ *            (first) or +inf (second), i.e. no clip on that side.
+ * masked_moments: stats6 (device) [C][6] doubles = {n, lo, hi, mean, std, number of non-finite masked values}.  lo / hi:
+ *            the clip bounds of channel c read from bounds[c * bound_stride + 0 / 1] (device doubles, rounded to fp32; e.g.
+ *            out8 + 5 with stride 8), -inf / +inf when bounds is NULL.  With y = min(max(x, lo), hi) on the mask:
+ *            mean = sum y / n and std = sqrt(sum (y - mean)^2 / n) (population, second pass over the deviations from the
+ *            double mean), both in double; a std that is 0 as fp32 -> 1; n == 0 -> mean 0, std 1.  2 passes over x.
+ *            Per-block partial rows in double summed in a fixed order: bit-identical from run to run.
+ * zscore_apply: in place, x = (min(max(x, lo), hi) - mean) / std on the mask with lo, hi, mean, std of stats6 each rounded
+ *            once to fp32, one fp32 rounding per operation; voxels outside the mask keep their bits.
+ * ------------------------------------------------------------------------------------------- */
+size_t msseg_volume_stats_scratch_bytes(int C);
+int msseg_select_f32(const float* x, int C, long long V, const long long* ranks, int nrank, const double* percentages, int npct,
+                     void* scratch, size_t scratch_bytes, double* out8, msseg_stream_t stream);
+int msseg_masked_moments(const float* x, int C, long long V, const double* bounds, long long bound_stride, void* scratch,
+                         size_t scratch_bytes, double* stats6, msseg_stream_t stream);
+int msseg_zscore_apply(float* x, int C, long long V, const double* stats6, msseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Intensity augmentation of a gathered batch (csrc/intensity_aug.hip; no reference counterpart: the reference has no

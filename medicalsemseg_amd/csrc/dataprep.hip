@@ -5,7 +5,8 @@
 //                     (data/dataset_builder.py:37-81,194-210, data/transforms.py:45-75)
 //   resample_spacing  Spacingd(pixdim, mode=("bilinear", "nearest"))            (dataset_builder.py:30-36)
 //   crop_pad_copy     CropForegroundd's crop + SpatialPadd(vol_size)            (dataset_builder.py:69-87)
-//   slab_counts       per z-slice numbers of the crop-centre candidates RandCropByPosNegLabeld draws from (:108-120)
+//   slab_counts       per z-slice numbers of the crop-centre candidates RandCropByPosNegLabeld draws from (:108-120);
+//                     the image side of a background candidate is `> threshold` or, for a z-scored cache, `!= threshold`
 //   pick_voxels       the k-th candidate of a slice -> crop centre (correct_crop_centers clamp) and crop start
 //   aug_crop_multi    msseg_aug_crop_batch over many cached volumes: one launch per batch
 //   aug_crop_affine   aug_crop_multi sampling the volume under a 3x3 matrix per patch (rotation + zoom about the patch centre)
@@ -126,16 +127,21 @@ __global__ __launch_bounds__(256) void crop_pad_copy_kernel(const T* __restrict_
     for (int c = 0; c < C; ++c) dst[(long long)c * TV + o] = in ? src[(long long)c * SV + s] : pad;
 }
 
-// one block per z-slice; counts[z] = {#(lab > 0), #(lab == 0 && img0 > thr)}
+// the image side of a background crop-centre candidate: rule 0 = above the threshold (the reference's image_threshold on
+// a cache whose scale is monotone in the raw one), rule 1 = different from it (the non-zero mask of a z-scored cache, whose
+// in-mask values have either sign)
+MSSEG_DEVFN bool bg_image_ok(float v, float thr, int rule) { return rule ? v != thr : v > thr; }
+
+// one block per z-slice; counts[z] = {#(lab > 0), #(lab == 0 && bg_image_ok(img0))}
 __global__ __launch_bounds__(256) void slab_counts_kernel(const float* __restrict__ img0, const unsigned char* __restrict__ lab,
-                                                          int HW, float thr, int* __restrict__ counts) {
+                                                          int HW, float thr, int rule, int* __restrict__ counts) {
     __shared__ int sfg[4], sbg[4];
     const long long base = (long long)blockIdx.x * HW;
     int fg = 0, bg = 0;
     for (int i = threadIdx.x; i < HW; i += 256) {
         const unsigned char l = lab[base + i];
         fg += l > 0;
-        bg += (l == 0 && img0[base + i] > thr);
+        bg += (l == 0 && bg_image_ok(img0[base + i], thr, rule));
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { fg += __shfl_xor(fg, o); bg += __shfl_xor(bg, o); }
@@ -161,7 +167,7 @@ MSSEG_DEVFN int clamp_center(int c, int r, int n) {
 constexpr int PICK_K = 8;
 __global__ __launch_bounds__(256) void pick_voxels_kernel(const VolDesc* __restrict__ vols, int nvol,
                                                           const PickRow* __restrict__ rows, int R, float thr,
-                                                          int* __restrict__ out) {
+                                                          int rule, int* __restrict__ out) {
     __shared__ int scan[256];
     __shared__ int found;
     const PickRow row = rows[blockIdx.x];
@@ -190,7 +196,7 @@ __global__ __launch_bounds__(256) void pick_voxels_kernel(const VolDesc* __restr
                 const int i = first + j;
                 if (i < HW) {
                     const unsigned char l = lab[i];
-                    n += want_fg ? (l > 0) : (l == 0 && img[i] > thr);
+                    n += want_fg ? (l > 0) : (l == 0 && bg_image_ok(img[i], thr, rule));
                 }
             }
             scan[threadIdx.x] = n;
@@ -209,7 +215,7 @@ __global__ __launch_bounds__(256) void pick_voxels_kernel(const VolDesc* __restr
                     const int i = first + j;
                     if (i < HW) {
                         const unsigned char l = lab[i];
-                        const bool m = want_fg ? (l > 0) : (l == 0 && img[i] > thr);
+                        const bool m = want_fg ? (l > 0) : (l == 0 && bg_image_ok(img[i], thr, rule));
                         if (m && k-- == 0) { found = i; break; }
                     }
                 }
@@ -433,22 +439,34 @@ int msseg_crop_pad_copy(const void* src, int elem_bytes, int C, int SD, int SH, 
     return MSSEG_OK;
 }
 
+int msseg_slab_counts_rule(const float* img0, const uint8_t* lab, int D, int H, int W, float threshold, int bg_rule, int* counts,
+                           msseg_stream_t stream) {
+    if (!img0 || !lab || !counts || D < 1 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL || bg_rule < 0 || bg_rule > 1)
+        MSSEG_FAIL(MSSEG_EINVAL, "slab_counts: bad args");
+    hipLaunchKernelGGL(slab_counts_kernel, dim3(D), dim3(256), 0, (hipStream_t)stream, img0, lab, H * W, threshold, bg_rule,
+                       counts);
+    MSSEG_CHECK_LAUNCH("slab_counts");
+    return MSSEG_OK;
+}
+
 int msseg_slab_counts(const float* img0, const uint8_t* lab, int D, int H, int W, float threshold, int* counts,
                       msseg_stream_t stream) {
-    if (!img0 || !lab || !counts || D < 1 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL)
-        MSSEG_FAIL(MSSEG_EINVAL, "slab_counts: bad args");
-    hipLaunchKernelGGL(slab_counts_kernel, dim3(D), dim3(256), 0, (hipStream_t)stream, img0, lab, H * W, threshold, counts);
-    MSSEG_CHECK_LAUNCH("slab_counts");
+    return msseg_slab_counts_rule(img0, lab, D, H, W, threshold, 0, counts, stream);
+}
+
+int msseg_pick_voxels_rule(const void* volumes, int nvol, const void* rows, int nrows, int R, float threshold, int bg_rule,
+                           int* out, msseg_stream_t stream) {
+    if (!volumes || !rows || !out || nvol < 1 || nrows < 1 || R < 1 || bg_rule < 0 || bg_rule > 1)
+        MSSEG_FAIL(MSSEG_EINVAL, "pick_voxels: bad args");
+    hipLaunchKernelGGL(pick_voxels_kernel, dim3(nrows), dim3(256), 0, (hipStream_t)stream, (const VolDesc*)volumes, nvol,
+                       (const PickRow*)rows, R, threshold, bg_rule, out);
+    MSSEG_CHECK_LAUNCH("pick_voxels");
     return MSSEG_OK;
 }
 
 int msseg_pick_voxels(const void* volumes, int nvol, const void* rows, int nrows, int R, float threshold, int* out,
                       msseg_stream_t stream) {
-    if (!volumes || !rows || !out || nvol < 1 || nrows < 1 || R < 1) MSSEG_FAIL(MSSEG_EINVAL, "pick_voxels: bad args");
-    hipLaunchKernelGGL(pick_voxels_kernel, dim3(nrows), dim3(256), 0, (hipStream_t)stream, (const VolDesc*)volumes, nvol,
-                       (const PickRow*)rows, R, threshold, out);
-    MSSEG_CHECK_LAUNCH("pick_voxels");
-    return MSSEG_OK;
+    return msseg_pick_voxels_rule(volumes, nvol, rows, nrows, R, threshold, 0, out, stream);
 }
 
 int msseg_aug_crop_multi(const void* volumes, int nvol, const void* rows, const int* picks, int npatch, int C, void* out_img,

@@ -312,10 +312,34 @@ def _upload(structs, dev):
 
 def check_transform_flags(cfg):
     """the transform flags this build does not implement raise with the flag's name"""
+    hint = {"t_percentile_ct_intensity": " (per-volume percentile clipping: --t_zscore --t_zscore_clip LO HI)",
+            "t_normalize_channel_wise": " (per-volume, per-channel normalisation: --t_zscore)"}
     for flag in ("t_percentile_ct_intensity", "t_normalize_channel_wise", "t_crop_foreground_kdiv", "t_rand_crop_classes",
                  "t_rand_crop_dilated_center", "t_convert_labels_to_brats"):
         if getattr(cfg, flag, False) and not (flag == "t_normalize_channel_wise" and not cfg.t_normalize):
-            raise NotImplementedError(f"--{flag} is not implemented on the device data path")
+            raise NotImplementedError(f"--{flag} is not implemented on the device data path{hint.get(flag, '')}")
+    zscore_config(cfg)
+
+
+def zscore_config(cfg):
+    """--t_zscore / --t_zscore_clip -> None (off), () (z-score without clip) or (LO, HI) percentages; a ValueError names
+    the flag.  --t_zscore excludes --t_normalize: the cache's pad value, the out-of-volume value of the affine gather and
+    the sliding window's cval are the normalised zero, which must stay 0 for the non-zero mask to survive."""
+    on = bool(getattr(cfg, "t_zscore", False))
+    clip = getattr(cfg, "t_zscore_clip", ())
+    clip = tuple(clip) if isinstance(clip, (tuple, list)) else (clip,)
+    if clip and not on:
+        raise ValueError("--t_zscore_clip needs --t_zscore")
+    if not on:
+        return None
+    if getattr(cfg, "t_normalize", False):
+        raise ValueError("--t_zscore and --t_normalize exclude each other: --t_normalize moves the pad value away from 0, "
+                         "--t_zscore keeps zeros zero")
+    if not clip:
+        return ()
+    if len(clip) != 2 or not all(np.isfinite(float(q)) for q in clip) or not 0.0 <= float(clip[0]) < float(clip[1]) <= 100.0:
+        raise ValueError(f"--t_zscore_clip takes two percentages LO HI with 0 <= LO < HI <= 100, got {clip!r}")
+    return float(clip[0]), float(clip[1])
 
 
 def normalised_zero(cfg):
@@ -345,9 +369,13 @@ def preprocess_volume(image, label, affine, cfg, device, filename="volume"):
     with the foreground box -> CropForegroundd -> SpatialPadd(vol_size).  NormalizeIntensityd is applied here for training
     as well: the reference applies it after the random shift / scale, this cache before them (the pad value is the
     normalised zero, as a pad before the normalisation gives; the background crop centres must then be thresholded at
-    normalised_zero(cfg), not at 0)."""
+    normalised_zero(cfg), not at 0).  With --t_zscore the chain ends with the per-volume z-score of every channel over its
+    non-zero voxels (hip.zscore_nonzero_; zeros and pads stay 0, the background crop centres are then the voxels != 0:
+    DeviceDatasetLoader(image_rule="ne")); the record's "zscore" is the host copy of the statistics, float64 [C, 6] =
+    {n, P_LO, P_HI, mean, std, non-finite count}."""
     from . import data_files as df
     check_transform_flags(cfg)
+    zscore = zscore_config(cfg)
     roi = cfg.vol_size if isinstance(cfg.vol_size, int) else cfg.vol_size[0]
     image = np.asarray(image)
     if image.dtype != np.int16 and image.dtype != np.float32:
@@ -396,7 +424,17 @@ def preprocess_volume(image, label, affine, cfg, device, filename="volume"):
         img, before = hip.crop_pad_copy(img, b6, min_size, pad)
         lab = hip.crop_pad_copy(lab[None], b6, min_size, 0)[0][0]
         aff = df.shift_affine(aff, [b6[a] - before[a] for a in range(3)])
-    return {"img": img, "lab": lab.contiguous(), "affine": aff, "original_affine": original_affine, "filename": filename,
+    extra = {}
+    if zscore is not None:
+        # last: the pads (0) and every other zero stay outside the statistics and stay zero
+        img = img.contiguous()
+        stats = hip.zscore_nonzero_(img, zscore or None).cpu().numpy()     # the one small read-back: [C, 6]
+        if not np.isfinite(stats[:, 3:5]).all() or stats[:, 5].any():
+            raise ValueError(f"{filename}: --t_zscore met a NaN or an infinite intensity (per channel: "
+                             f"{[int(v) for v in stats[:, 5]]} non-finite voxel(s), mean {stats[:, 3].tolist()}, "
+                             f"std {stats[:, 4].tolist()})")
+        extra["zscore"] = stats
+    return {**extra, "img": img,"lab": lab.contiguous(), "affine": aff, "original_affine": original_affine, "filename": filename,
             "box": b6, "pad_before": tuple(before),
             # the geometry restore_descriptor needs to map a prediction back onto the file's grid
             "native_shape": native_shape, "orient": (tuple(int(p) for p in perm), tuple(bool(f) for f in flips)),
@@ -457,15 +495,21 @@ class DeviceDatasetLoader:
     intensity: an intensity_config(...).  With any of its stages on, the gather writes an fp32 scratch batch, a patch's
     intensity rows (draw_intensity) are drawn after its other draws and its matrix, and msseg_intensity_aug (noise, blur,
     contrast, gamma inverted, gamma) writes the batch in out_dtype; the rows of the last batch are in last_intensity, the
-    labels are untouched.  With every stage off: no draw, no scratch, no launch."""
+    labels are untouched.  With every stage off: no draw, no scratch, no launch.
+    image_rule: the image side of a background crop centre, "gt" = image[0] > image_threshold, "ne" = image[0] !=
+    image_threshold: for a z-scored cache (--t_zscore), where the reference's `raw image > 0` is the non-zero mask and the
+    in-mask values have either sign (a voxel whose z-score is exactly 0.0 drops out of the candidates)."""
 
     def __init__(self, volumes, roi, batch, n_batches, patches_per_image=1, device=None, seed=13, crop="fgbg", pos=1.0,
                  neg=1.0, flip_prob=0.0, rot_prob=0.0, shift_os=0.1, shift_prob=0.0, scale_f=0.1, scale_prob=0.0,
                  image_threshold=0.0, out_dtype=torch.float32, affine_prob=0.0, affine_rotate=30.0, affine_zoom=(0.7, 1.4),
-                 affine_pad=0.0, intensity=None):
+                 affine_pad=0.0, intensity=None, image_rule="gt"):
         self.affine, self.affine_pad = affine_config(affine_prob, affine_rotate, affine_zoom), float(affine_pad)
         self.intensity = _check_intensity(intensity, int(roi))
         self.last_intensity = None
+        if image_rule not in hip.BG_RULES:
+            raise ValueError(f"image_rule {image_rule!r}: 'gt' or 'ne'")
+        self.image_rule = image_rule
         if not volumes:
             raise ValueError("DeviceDatasetLoader needs at least one cached volume")
         if crop not in ("fgbg", "spatial"):
@@ -490,7 +534,7 @@ class DeviceDatasetLoader:
         # candidate counts per z-slice, cumulative on the host: 8 bytes per slice instead of 8 bytes per voxel
         self.cum = []
         if crop == "fgbg":
-            counts = [hip.slab_counts(v["img"], v["lab"], self.thr) for v in self.vols]
+            counts = [hip.slab_counts(v["img"], v["lab"], self.thr, self.image_rule) for v in self.vols]
             for c in counts:
                 c = c.cpu().numpy().astype(np.int64)
                 self.cum.append((np.cumsum(c[:, 0]), np.cumsum(c[:, 1])))
@@ -551,7 +595,7 @@ class DeviceDatasetLoader:
                 picks = host.to(self.dev, non_blocking=True)
             else:
                 picks = torch.empty(self.batch, 8, dtype=torch.int32, device=self.dev)
-                hip.pick_voxels(self.desc, len(self.vols), table, self.batch, R, self.thr, picks)
+                hip.pick_voxels(self.desc, len(self.vols), table, self.batch, R, self.thr, picks, self.image_rule)
             out = torch.empty(self.batch, self.C, R, R, R, dtype=self.out_dtype, device=self.dev)
             img = torch.empty_like(out, dtype=torch.float32) if aug else out   # the gather's fp32 scratch batch
             lab = torch.empty(self.batch, 1, R, R, R, dtype=torch.float32, device=self.dev)

@@ -144,6 +144,12 @@ SIGNATURES = {
     "msseg_crop_pad_copy": ([_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _f, _i, _vp], _i),
     "msseg_slab_counts": ([_vp, _vp, _i, _i, _i, _f, _vp, _vp], _i),
     "msseg_pick_voxels": ([_vp, _i, _vp, _i, _i, _f, _vp, _vp], _i),
+    "msseg_slab_counts_rule": ([_vp, _vp, _i, _i, _i, _f, _i, _vp, _vp], _i),
+    "msseg_pick_voxels_rule": ([_vp, _i, _vp, _i, _i, _f, _i, _vp, _vp], _i),
+    "msseg_volume_stats_scratch_bytes": ([_i], _sz),
+    "msseg_select_f32": ([_vp, _i, _ll, _vp, _i, _vp, _i, _vp, _sz, _vp, _vp], _i),
+    "msseg_masked_moments": ([_vp, _i, _ll, _vp, _ll, _vp, _sz, _vp, _vp], _i),
+    "msseg_zscore_apply": ([_vp, _i, _ll, _vp, _vp], _i),
     "msseg_aug_crop_multi": ([_vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp], _i),
     "msseg_aug_crop_affine": ([_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _f, _vp], _i),
     "msseg_intensity_aug_workspace_bytes": ([_i, _i, _i, _i, _i], _sz),
@@ -1644,26 +1650,108 @@ def crop_pad_copy(src, box, min_size=None, pad_value=0):
     return dst, tuple(before)
 
 
-def slab_counts(img, lab, threshold=0.0):
+BG_RULES = {"gt": 0, "ne": 1}
+
+
+def _bg_rule(rule):
+    if rule not in BG_RULES:
+        raise ValueError(f"background rule {rule!r}: 'gt' (image > threshold) or 'ne' (image != threshold)")
+    return BG_RULES[rule]
+
+
+def slab_counts(img, lab, threshold=0.0, rule="gt"):
     """img fp32 [C, D, H, W] (channel 0 is read), lab uint8 [D, H, W] -> int32 [D, 2] on the device:
-    per z-slice #(lab > 0), #(lab == 0 and img[0] > threshold)"""
+    per z-slice #(lab > 0), #(lab == 0 and img[0] > threshold); rule "ne": img[0] != threshold, the non-zero mask of a
+    z-scored cache"""
     _need_gpu(img, lab)
     assert img.dtype == torch.float32 and lab.dtype == torch.uint8 and img.is_contiguous() and lab.is_contiguous()
     assert img.dim() == 4 and lab.dim() == 3 and img.shape[1:] == lab.shape
     out = torch.empty(lab.shape[0], 2, dtype=torch.int32, device=lab.device)
-    _ck(lib().msseg_slab_counts(_p(img), _p(lab), *lab.shape, float(threshold), _p(out), _stream()), "slab_counts")
+    _ck(lib().msseg_slab_counts_rule(_p(img), _p(lab), *lab.shape, float(threshold), _bg_rule(rule), _p(out), _stream()),
+        "slab_counts")
     return out
 
 
-def pick_voxels(volumes, nvol, rows, nrows, roi, threshold, out):
+def pick_voxels(volumes, nvol, rows, nrows, roi, threshold, out, rule="gt"):
     """volumes: uint8 device tensor of nvol msseg_volume_desc; rows: uint8 device tensor of nrows msseg_pick_row;
-    out: int32 [nrows, 8] on the device"""
+    out: int32 [nrows, 8] on the device; rule as slab_counts"""
     _need_gpu(volumes, rows, out)
     assert volumes.numel() >= nvol * 32 and rows.numel() >= nrows * 32 and out.dtype == torch.int32
     assert out.is_contiguous() and out.numel() >= nrows * 8
-    _ck(lib().msseg_pick_voxels(_p(volumes), nvol, _p(rows), nrows, int(roi), float(threshold), _p(out), _stream()),
-        "pick_voxels")
+    _ck(lib().msseg_pick_voxels_rule(_p(volumes), nvol, _p(rows), nrows, int(roi), float(threshold), _bg_rule(rule), _p(out),
+                                     _stream()), "pick_voxels")
     return out
+
+
+# ---- per-volume z-score over the non-zero voxels (csrc/volume_stats.hip) ----------------------------------------------
+def _flat_channels(x):
+    _need_gpu(x)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() >= 2, "a contiguous fp32 [C, ...] tensor expected"
+    return int(x.shape[0]), int(x.numel() // x.shape[0])
+
+
+def _stats_scratch(x):
+    return torch.empty(lib().msseg_volume_stats_scratch_bytes(int(x.shape[0])), dtype=torch.uint8, device=x.device)
+
+
+def select_f32(x, ranks=None, percentages=None, scratch=None):
+    """exact order statistics of the non-zero values of every channel of x fp32 [C, ...]: `ranks` (1..4 zero-based ranks) or
+    `percentages` (1..2 values in [0, 100]: the ranks k, k + 1 of numpy's linear percentile, formed on the device) ->
+    float64 [C, 8] on the device = {n, up to 4 order statistics (NaN: rank >= n), P of each percentage as fp32 (-inf, +inf
+    where none is formed), 0}.  Nothing is read back."""
+    C_, V = _flat_channels(x)
+    assert (ranks is None) != (percentages is None), "select_f32: ranks or percentages"
+    scratch = _stats_scratch(x) if scratch is None else scratch
+    out = torch.empty(C_, 8, dtype=torch.float64, device=x.device)
+    rk = (C.c_longlong * len(ranks))(*[int(r) for r in ranks]) if ranks is not None else None
+    pc = (C.c_double * len(percentages))(*[float(q) for q in percentages]) if percentages is not None else None
+    _ck(lib().msseg_select_f32(_p(x), C_, V, rk, len(ranks) if ranks is not None else 0, pc,
+                               len(percentages) if percentages is not None else 0, _p(scratch), scratch.numel(), _p(out),
+                               _stream()), "select_f32")
+    return out
+
+
+def masked_moments(x, bounds=None, scratch=None):
+    """x fp32 [C, ...]; bounds: None or a float64 [C, 2] device tensor (a view with unit inner stride will do) of clip bounds
+    -> float64 [C, 6] on the device = {n, lo, hi, mean, std, number of non-finite masked values} over the non-zero values,
+    clipped to [lo, hi] first (tests/zscore_ref.py)"""
+    C_, V = _flat_channels(x)
+    stride = 0
+    if bounds is not None:
+        _need_gpu(bounds)
+        assert bounds.dtype == torch.float64 and tuple(bounds.shape) == (C_, 2) and bounds.stride(1) == 1
+        stride = int(bounds.stride(0)) if C_ > 1 else 2
+        assert stride >= 2
+    scratch = _stats_scratch(x) if scratch is None else scratch
+    stats = torch.empty(C_, 6, dtype=torch.float64, device=x.device)
+    _ck(lib().msseg_masked_moments(_p(x), C_, V, _p(bounds), stride, _p(scratch), scratch.numel(), _p(stats), _stream()),
+        "masked_moments")
+    return stats
+
+
+def zscore_apply_(x, stats):
+    """in place: x = (clip(x, lo, hi) - mean) / std on the non-zero voxels of every channel, with the fp32 values of
+    stats (masked_moments' [C, 6])"""
+    C_, V = _flat_channels(x)
+    _need_gpu(stats)
+    assert stats.dtype == torch.float64 and stats.is_contiguous() and tuple(stats.shape) == (C_, 6)
+    _ck(lib().msseg_zscore_apply(_p(x), C_, V, _p(stats), _stream()), "zscore_apply")
+    return x
+
+
+def zscore_nonzero_(img, clip=None):
+    """--t_zscore on one cached volume, in place: every channel of img fp32 [C, D, H, W] normalised by the mean and the
+    population std of its own non-zero voxels; clip = (LO, HI) percentages: those voxels are first clipped to the channel's
+    own percentiles.  -> stats, float64 [C, 6] on the device = {n, P_LO, P_HI, mean, std, non-finite count} (bounds -inf,
+    +inf without clip).  The whole sequence is enqueued without a host synchronisation."""
+    scratch = _stats_scratch(img)
+    bounds = None
+    if clip is not None:
+        lo, hi = clip
+        bounds = select_f32(img, percentages=(lo, hi), scratch=scratch)[:, 5:7]
+    stats = masked_moments(img, bounds, scratch=scratch)
+    zscore_apply_(img, stats)
+    return stats
 
 
 def aug_crop_multi(volumes, nvol, rows, picks, out_img, out_lab, roi):

@@ -1,7 +1,7 @@
 """CLI of the training / evaluation drivers: every flag of ``/root/reference/utils/arguments.py:29-313`` with
 the same name, type, default and list-collapsing rule (``:19-24``: a list argument of length 1 becomes a scalar,
 longer lists become tuples), declared as a table; plus a few flags of this build (synthetic data, compute
-dtype, hipGraph replay, post-processing, rotation + zoom in the device crop gather, mirror test-time augmentation, intensity augmentation, file inference).  Flags whose subsystem is out of the hot-path scope (learned class vectors, MONAI
+dtype, hipGraph replay, post-processing, rotation + zoom in the device crop gather, mirror test-time augmentation, intensity augmentation, per-volume z-score, file inference).  Flags whose subsystem is out of the hot-path scope (learned class vectors, MONAI
 transforms, Neptune) are accepted and ignored so reference command lines keep working."""
 from __future__ import annotations
 
@@ -77,6 +77,10 @@ _SPEC = {
         ("--t_blur_prob", "v", 0.0, F), ("--t_blur_sigma", "l", [0.5, 1.0], F), ("--t_blur_channel_prob", "v", 0.5, F),
         ("--t_contrast_prob", "v", 0.0, F), ("--t_contrast_range", "l", [0.75, 1.25], F),
         ("--t_gamma_invert_prob", "v", 0.0, F), ("--t_gamma_prob", "v", 0.0, F), ("--t_gamma_range", "l", [0.7, 1.5], F),
+        # MR data: every channel of every cached volume normalised by the mean and std of its own non-zero voxels, as the
+        # last preprocessing step (data_device.py, csrc/volume_stats.hip; nnU-Net's per-volume z-score); --t_zscore_clip
+        # LO HI first clips those voxels to the channel's own percentiles, e.g. 0.5 99.5
+        ("--t_zscore", "t"), ("--t_zscore_clip", "l", [], F),
     ],
     "file inference": [  # run_predict.py: the files of a data list (engine/test.py, csrc/restore.hip)
         # the section of the data list to predict (labels of "validation" / "training" are ignored)

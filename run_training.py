@@ -67,7 +67,9 @@ def file_loaders(cfg, device, seed, vol):
                                        affine_prob=cfg.t_affine_prob, affine_rotate=cfg.t_affine_rotate,
                                        affine_zoom=cfg.t_affine_zoom, affine_pad=normalised_zero(cfg),
                                        # noise, blur, contrast and gamma on the gathered batch
-                                       intensity=intensity_config_from_args(cfg))
+                                       intensity=intensity_config_from_args(cfg),
+                                       # on a z-scored cache the reference's `raw image > 0` is the non-zero mask
+                                       image_rule="ne" if cfg.t_zscore else "gt")
     return loader_train, DeviceVolumeLoader(rec_val)
 
 
