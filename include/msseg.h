@@ -843,6 +843,32 @@ int msseg_aug_crop_affine(const void* volumes, int nvol, const void* rows, const
                           int C, void* out_img, int out_dtype, float* out_lab, int R, float pad_value, msseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Class-ratio crop centres (csrc/class_crop.hip; the reference's RandCropByLabelClassesd, --t_rand_crop_class_ratios /
+ * --t_rand_crop_center_dilation here).  Semantics: tests/class_crop_ref.py.  With image_ok(v) = v > threshold (bg_rule 0)
+ * or v != threshold (bg_rule 1) as in slab_counts_rule, voxel v is a candidate of class c < K iff image_ok(img0(v)) and a
+ * voxel u with lab(u) == c exists with |u - v|_1 <= N; N = 0: lab(v) == c.  Label values >= K belong to no class.
+ * A class pick is a msseg_pick_row with mode = MSSEG_PICK_CLASS0 + c; the gather kernels never read mode.
+ * class_candidate_mask: N > 0, once per cached volume.  mask (device, uint16 [D][H][W]) gets bit c = that predicate for every
+ *            class c of class_bits (bits 0..15), 0 for the others.  0 <= N <= 254.  scratch: D * H * W bytes on the device,
+ *            reused by the classes.  Per class three capped chamfer sweeps of the L1 distance to the class (forward and
+ *            backward along x, then y, then z, capped at N + 1 so that it fits a byte); equal to scipy's
+ *            binary_dilation(lab == c, iterations=N) with the default structure.
+ * class_slab_counts: counts[z][c], int32 [D][K] on the device, 1 <= K <= 16: the candidates of class c in slice z, read from
+ *            mask when it is not NULL (img0 and lab are then unused and may be NULL), from (img0, lab) with N = 0 otherwise.
+ * class_pick_voxels: pick_voxels_rule whose rows may also carry mode 16 + c: the rank-th candidate of class c (flat order)
+ *            of slice z of volume vol, read from masks[vol] when masks (NULL, or a device array of nvol mask pointers) and
+ *            that entry are not NULL, from the volume's label with N = 0 otherwise.  Rows of mode 0, 1, 2 and the output
+ *            row are exactly those of pick_voxels_rule; any other mode reports -1 as a rank beyond the count does.
+ * ------------------------------------------------------------------------------------------- */
+#define MSSEG_PICK_CLASS0 16
+int msseg_class_candidate_mask(const float* img0, const uint8_t* lab, int D, int H, int W, float threshold, int bg_rule,
+                               unsigned class_bits, int N, uint8_t* scratch, uint16_t* mask, msseg_stream_t stream);
+int msseg_class_slab_counts(const float* img0, const uint8_t* lab, const uint16_t* mask, int D, int H, int W, int K,
+                            float threshold, int bg_rule, int* counts, msseg_stream_t stream);
+int msseg_class_pick_voxels(const void* volumes, const void* masks, int nvol, const void* rows, int nrows, int R,
+                            float threshold, int bg_rule, int* out, msseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Per-volume z-score over the non-zero voxels (csrc/volume_stats.hip): the last step of the dataset path's preprocessing
  * for MR data (--t_zscore / --t_zscore_clip; nnU-Net's ZScoreNormalization with use_mask_for_norm, per channel of each
  * volume; no reference counterpart: the reference normalises per cropped patch).  x: fp32 [C][V], 16-byte aligned,

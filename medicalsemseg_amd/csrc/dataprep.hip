@@ -7,18 +7,21 @@
 //   crop_pad_copy     CropForegroundd's crop + SpatialPadd(vol_size)            (dataset_builder.py:69-87)
 //   slab_counts       per z-slice numbers of the crop-centre candidates RandCropByPosNegLabeld draws from (:108-120);
 //                     the image side of a background candidate is `> threshold` or, for a z-scored cache, `!= threshold`
-//   pick_voxels       the k-th candidate of a slice -> crop centre (correct_crop_centers clamp) and crop start
+//   pick_voxels       the k-th candidate of a slice -> crop centre (correct_crop_centers clamp) and crop start; the scan
+//                     lives in pick_scan.h, which class_crop.hip shares
 //   aug_crop_multi    msseg_aug_crop_batch over many cached volumes: one launch per batch
 //   aug_crop_affine   aug_crop_multi sampling the volume under a 3x3 matrix per patch (rotation + zoom about the patch centre)
 //
 // MONAI is absent: the semantics are those of the numpy / scipy restatement in tests/dataprep_ref.py (MONAI parity
 // unpinned).  All kernels are HBM-bound; geometry (z, y) comes from the launch grid, threads run along x.
 #include "common.h"
+#include "pick_scan.h"
 
 namespace {
 
-struct VolDesc { const float* img; const unsigned char* lab; int C, D, H, W; };              // mirrors msseg_volume_desc
-struct PickRow { int vol, mode, z, rank, flips, rotk; float shift, scale; };                   // mirrors msseg_pick_row
+using pick::VolDesc;
+using pick::PickRow;
+using pick::bg_image_ok;
 
 typedef float f32x4u_t __attribute__((ext_vector_type(4), aligned(4)));
 
@@ -127,11 +130,6 @@ __global__ __launch_bounds__(256) void crop_pad_copy_kernel(const T* __restrict_
     for (int c = 0; c < C; ++c) dst[(long long)c * TV + o] = in ? src[(long long)c * SV + s] : pad;
 }
 
-// the image side of a background crop-centre candidate: rule 0 = above the threshold (the reference's image_threshold on
-// a cache whose scale is monotone in the raw one), rule 1 = different from it (the non-zero mask of a z-scored cache, whose
-// in-mask values have either sign)
-MSSEG_DEVFN bool bg_image_ok(float v, float thr, int rule) { return rule ? v != thr : v > thr; }
-
 // one block per z-slice; counts[z] = {#(lab > 0), #(lab == 0 && bg_image_ok(img0))}
 __global__ __launch_bounds__(256) void slab_counts_kernel(const float* __restrict__ img0, const unsigned char* __restrict__ lab,
                                                           int HW, float thr, int rule, int* __restrict__ counts) {
@@ -153,18 +151,7 @@ __global__ __launch_bounds__(256) void slab_counts_kernel(const float* __restric
     }
 }
 
-// MONAI correct_crop_centers for one axis (oracle/augment.py): centre clamped so that the roi stays inside the image
-MSSEG_DEVFN int clamp_center(int c, int r, int n) {
-    const int lo = r / 2;
-    int hi = n + 1 - r / 2;      // floor for even r, ceil for odd r of n + 1 - r / 2.0
-    if (lo == hi) hi += 1;
-    c = c < lo ? lo : c;
-    c = c >= hi ? hi - 1 : c;
-    return c;
-}
-
-// one block per row: counting scan of slice `z` of volume `vol` in flat order, chunks of 256 threads x 8 voxels
-constexpr int PICK_K = 8;
+// one block per row: counting scan (pick_scan.h) of slice `z` of volume `vol` in flat order
 __global__ __launch_bounds__(256) void pick_voxels_kernel(const VolDesc* __restrict__ vols, int nvol,
                                                           const PickRow* __restrict__ rows, int R, float thr,
                                                           int rule, int* __restrict__ out) {
@@ -179,61 +166,14 @@ __global__ __launch_bounds__(256) void pick_voxels_kernel(const VolDesc* __restr
     const VolDesc vd = vols[row.vol];
     const int HW = vd.H * vd.W;
     const int z = row.z < 0 ? 0 : (row.z >= vd.D ? vd.D - 1 : row.z);
-    int hit = -1;
+    int hit;
     if (row.mode == 2) {
         hit = row.rank < 0 ? 0 : (row.rank >= HW ? HW - 1 : row.rank);      // explicit voxel of the slice
     } else {
-        const unsigned char* lab = vd.lab + (long long)z * HW;
-        const float* img = vd.img + (long long)z * HW;
-        const bool want_fg = row.mode == 1;
-        if (threadIdx.x == 0) found = -1;
-        int running = 0;
-        for (int base = 0; base < HW; base += 256 * PICK_K) {
-            const int first = base + threadIdx.x * PICK_K;
-            int n = 0;
-#pragma unroll
-            for (int j = 0; j < PICK_K; ++j) {
-                const int i = first + j;
-                if (i < HW) {
-                    const unsigned char l = lab[i];
-                    n += want_fg ? (l > 0) : (l == 0 && bg_image_ok(img[i], thr, rule));
-                }
-            }
-            scan[threadIdx.x] = n;
-            __syncthreads();
-            for (int s = 1; s < 256; s <<= 1) {                              // inclusive prefix sum over the block
-                const int v = threadIdx.x >= s ? scan[threadIdx.x - s] : 0;
-                __syncthreads();
-                scan[threadIdx.x] += v;
-                __syncthreads();
-            }
-            const int incl = scan[threadIdx.x], total = scan[255];
-            const int want = row.rank - running;                             // rank inside this chunk
-            if (want >= 0 && want < total && want >= incl - n && want < incl) {
-                int k = want - (incl - n);
-                for (int j = 0; j < PICK_K; ++j) {
-                    const int i = first + j;
-                    if (i < HW) {
-                        const unsigned char l = lab[i];
-                        const bool m = want_fg ? (l > 0) : (l == 0 && bg_image_ok(img[i], thr, rule));
-                        if (m && k-- == 0) { found = i; break; }
-                    }
-                }
-            }
-            __syncthreads();
-            if (want >= 0 && want < total) break;                            // uniform over the block
-            running += total;
-        }
-        __syncthreads();
-        hit = found;
+        const pick::FgBgPred pred{vd.lab + (long long)z * HW, vd.img + (long long)z * HW, thr, rule, row.mode == 1};
+        hit = pick::scan_slice(HW, row.rank, pred, scan, &found);
     }
-    if (threadIdx.x == 0) {
-        const int py = hit >= 0 ? hit / vd.W : 0, px = hit >= 0 ? hit % vd.W : 0;
-        const int cz = clamp_center(z, R, vd.D), cy = clamp_center(py, R, vd.H), cx = clamp_center(px, R, vd.W);
-        o[0] = cz; o[1] = cy; o[2] = cx;
-        o[3] = cz - R / 2; o[4] = cy - R / 2; o[5] = cx - R / 2;
-        o[6] = z; o[7] = hit;                                                // hit == -1: rank beyond the slice's count
-    }
+    if (threadIdx.x == 0) pick::write_pick(o, vd, z, hit, R);
 }
 
 // grid: (y tiles, R, npatch), block (runs of 4 along x, rows).  Every thread moves runs of 4 consecutive output x.

@@ -58,6 +58,59 @@ def draw_rows(rng: np.random.Generator, n, fg_count, bg_count, cfg_like):
     return rows
 
 
+def draw_class_rows(rng: np.random.Generator, n, counts, ratios, cfg_like):
+    """the random draws of n patches of the class-ratio crop: (class, index into that class's candidate list, flips, rotk,
+    shift, scale) per patch.  counts: the volume's candidates per class.  The ratios of the classes without a candidate are
+    zeroed and the rest renormalised (MONAI generate_label_classes_crop_centers); one uniform number picks the class by the
+    inverse CDF, one integer the candidate; the other draws follow in draw_rows's order.  With no candidate of any class of
+    positive ratio the class is -1 and the index 0 (the caller takes a uniform voxel): the uniform number is then not drawn."""
+    p = np.array([float(r) if int(c) > 0 else 0.0 for r, c in zip(ratios, counts)], dtype=np.float64)
+    live = np.nonzero(p > 0.0)[0]
+    cdf = np.cumsum(p / p.sum()) if live.size else None
+    rows = []
+    for _ in range(n):
+        # side="right": a class of probability 0 spans no interval; the last live class also takes a rounded-down total
+        cls = min(int(np.searchsorted(cdf, rng.random(), side="right")), int(live[-1])) if live.size else -1
+        idx = int(rng.integers(0, int(counts[cls]) if cls >= 0 else 1))
+        flips = tuple(bool(rng.random() < cfg_like["flip_prob"]) for _ in range(3))
+        rotk = int(rng.integers(1, 4)) if rng.random() < cfg_like["rot_prob"] else 0
+        shift = float(rng.uniform(-cfg_like["shift_os"], cfg_like["shift_os"])) if rng.random() < cfg_like["shift_prob"] else 0.0
+        scale = 1.0 + (float(rng.uniform(-cfg_like["scale_f"], cfg_like["scale_f"])) if rng.random() < cfg_like["scale_prob"] else 0.0)
+        rows.append((cls, idx, flips, rotk, shift, scale))
+    return rows
+
+
+def class_crop_config(ratios, dilation=0, n_classes=None):
+    """--t_rand_crop_class_ratios / --t_rand_crop_center_dilation -> (ratios as a tuple of floats, or None when the crop is
+    off; dilation); a ValueError names the flag.  n_classes: --output_dim, the number of ratios expected."""
+    r = tuple(ratios) if isinstance(ratios, (tuple, list)) else (() if ratios is None else (ratios,))
+    n = int(dilation)
+    if not 0 <= n <= hip.MAX_CENTER_DILATION:
+        raise ValueError(f"--t_rand_crop_center_dilation takes a number of voxels in 0..{hip.MAX_CENTER_DILATION}, got {dilation!r}")
+    if not r:
+        if n:
+            raise ValueError("--t_rand_crop_center_dilation needs --t_rand_crop_class_ratios")
+        return None, 0
+    want = f"one ratio per class ({n_classes} for --output_dim {n_classes})" if n_classes is not None else "one ratio per class"
+    if len(r) > hip.MAX_CROP_CLASSES or (n_classes is not None and len(r) != int(n_classes)):
+        raise ValueError(f"--t_rand_crop_class_ratios takes {want}, at most {hip.MAX_CROP_CLASSES}, got {len(r)}: {ratios!r}")
+    if not all(np.isfinite(float(v)) and float(v) >= 0.0 for v in r) or not any(float(v) > 0.0 for v in r):
+        raise ValueError(f"--t_rand_crop_class_ratios takes finite ratios >= 0 with at least one > 0, got {ratios!r}")
+    return tuple(float(v) for v in r), n
+
+
+def class_crop_config_from_args(cfg):
+    """the flags of a parsed command line -> class_crop_config(...); giving the class ratios together with another crop
+    flag is a ValueError that names both"""
+    ratios, n = class_crop_config(getattr(cfg, "t_rand_crop_class_ratios", ()), getattr(cfg, "t_rand_crop_center_dilation", 0),
+                                  getattr(cfg, "output_dim", None))
+    if ratios is not None:
+        for other in ("t_rand_crop_fgbg", "t_rand_spatial_crop"):
+            if getattr(cfg, other, False):
+                raise ValueError(f"--t_rand_crop_class_ratios and --{other} are both crop flags: give one")
+    return ratios, n
+
+
 def affine_matrix(angles_rad, zoom):
     """R0(a0) . R1(a1) . R2(a2) / zoom in float64: Rk is the right-handed rotation about tensor axis k of (D, H, W), zoom > 1
     magnifies.  The gather reads the volume at patch centre + M (patch index - (roi - 1) / 2)."""
@@ -288,7 +341,9 @@ class DevicePatchLoader:
 # The transforms are the chain of the reference's data/dataset_builder.py:19-217 (training) and :220-306 (validation) up
 # to the random crop; MONAI is absent, so what is pinned is parity with the numpy / scipy restatement in
 # tests/dataprep_ref.py (MONAI parity unpinned).  Cache cost: 4 bytes per voxel and channel (fp32 image) + 1 (uint8 label)
-# + 8 bytes per z-slice of candidate counts; no per-voxel index lists.
+# + 8 bytes per z-slice of candidate counts; no per-voxel index lists.  The class-ratio crop with a centre dilation adds a
+# candidate mask of 2 bytes per voxel per volume for as long as its loader lives (and 1 byte per voxel of scratch while the
+# mask is built).
 # ---------------------------------------------------------------------------------------------------------------------
 class PickRow(C.Structure):
     """mirror of msseg_pick_row (include/msseg.h)"""
@@ -302,6 +357,8 @@ class VolumeDesc(C.Structure):
 
 
 PICK_BG, PICK_FG, PICK_VOXEL = 0, 1, 2
+# the transform name a batch records for its crop (engine/train.py reads the crop location of any of them)
+CROP_TRANSFORM = {"fgbg": "RandCropByPosNegLabeld", "spatial": "RandSpatialCropd", "class_ratios": "RandCropByClassesd"}
 
 
 def _upload(structs, dev):
@@ -313,12 +370,17 @@ def _upload(structs, dev):
 def check_transform_flags(cfg):
     """the transform flags this build does not implement raise with the flag's name"""
     hint = {"t_percentile_ct_intensity": " (per-volume percentile clipping: --t_zscore --t_zscore_clip LO HI)",
-            "t_normalize_channel_wise": " (per-volume, per-channel normalisation: --t_zscore)"}
+            "t_normalize_channel_wise": " (per-volume, per-channel normalisation: --t_zscore)",
+            "t_rand_crop_classes": " (crop centres per class: --t_rand_crop_class_ratios NEG POS POS ..., one ratio per "
+                                   "class, is the same sampler)",
+            "t_rand_crop_dilated_center": " (crop centres near a class: --t_rand_crop_class_ratios R0 R1 ... with "
+                                          "--t_rand_crop_center_dilation 48)"}
     for flag in ("t_percentile_ct_intensity", "t_normalize_channel_wise", "t_crop_foreground_kdiv", "t_rand_crop_classes",
                  "t_rand_crop_dilated_center", "t_convert_labels_to_brats"):
         if getattr(cfg, flag, False) and not (flag == "t_normalize_channel_wise" and not cfg.t_normalize):
             raise NotImplementedError(f"--{flag} is not implemented on the device data path{hint.get(flag, '')}")
     zscore_config(cfg)
+    class_crop_config_from_args(cfg)
 
 
 def zscore_config(cfg):
@@ -498,12 +560,22 @@ class DeviceDatasetLoader:
     labels are untouched.  With every stage off: no draw, no scratch, no launch.
     image_rule: the image side of a background crop centre, "gt" = image[0] > image_threshold, "ne" = image[0] !=
     image_threshold: for a z-scored cache (--t_zscore), where the reference's `raw image > 0` is the non-zero mask and the
-    in-mask values have either sign (a voxel whose z-score is exactly 0.0 drops out of the candidates)."""
+    in-mask values have either sign (a voxel whose z-score is exactly 0.0 drops out of the candidates).
+    crop = "class_ratios" (RandCropByLabelClassesd) with class_ratios = one ratio >= 0 per class (K <= 16) and
+    center_dilation = N in 0..254: voxel v is a candidate of class c iff the image rule holds at v (for every class,
+    channel 0) and a voxel of label c lies within L1 distance N of v (N = 0: v itself has label c); labels >= K belong to
+    no class.  Per patch draw_class_rows picks the class (ratios of the classes the volume has no candidate of zeroed, the
+    rest renormalised) and the candidate; msseg_class_pick_voxels resolves it from the per-slice, per-class counts.  With
+    N > 0 every cached volume gets a uint16 candidate mask at construction (msseg_class_candidate_mask, for the classes
+    of positive ratio; 2 bytes per voxel for as long as the loader lives).  class_candidates[volume][class] are the totals,
+    last_classes the class of each patch of the last batch (-1: no candidate at all, a uniform voxel).  With class_ratios
+    and center_dilation at their defaults nothing changes for "fgbg" and "spatial": same kernels, same generator stream, no
+    extra memory."""
 
     def __init__(self, volumes, roi, batch, n_batches, patches_per_image=1, device=None, seed=13, crop="fgbg", pos=1.0,
                  neg=1.0, flip_prob=0.0, rot_prob=0.0, shift_os=0.1, shift_prob=0.0, scale_f=0.1, scale_prob=0.0,
                  image_threshold=0.0, out_dtype=torch.float32, affine_prob=0.0, affine_rotate=30.0, affine_zoom=(0.7, 1.4),
-                 affine_pad=0.0, intensity=None, image_rule="gt"):
+                 affine_pad=0.0, intensity=None, image_rule="gt", class_ratios=None, center_dilation=0):
         self.affine, self.affine_pad = affine_config(affine_prob, affine_rotate, affine_zoom), float(affine_pad)
         self.intensity = _check_intensity(intensity, int(roi))
         self.last_intensity = None
@@ -512,8 +584,12 @@ class DeviceDatasetLoader:
         self.image_rule = image_rule
         if not volumes:
             raise ValueError("DeviceDatasetLoader needs at least one cached volume")
-        if crop not in ("fgbg", "spatial"):
-            raise NotImplementedError(f"crop mode {crop!r}: --t_rand_crop_fgbg and --t_rand_spatial_crop are implemented")
+        if crop not in ("fgbg", "spatial", "class_ratios"):
+            raise NotImplementedError(f"crop mode {crop!r}: --t_rand_crop_fgbg, --t_rand_spatial_crop and "
+                                      f"--t_rand_crop_class_ratios (\"class_ratios\") are implemented")
+        self.class_ratios, self.center_dilation = class_crop_config(class_ratios, center_dilation)
+        if (self.class_ratios is not None) != (crop == "class_ratios"):
+            raise ValueError("crop=\"class_ratios\" and class_ratios (--t_rand_crop_class_ratios) go together")
         self.vols, self.roi, self.batch, self.n = list(volumes), int(roi), int(batch), int(n_batches)
         self.ppi, self.dev, self.crop, self.thr, self.out_dtype = max(int(patches_per_image), 1), device, crop, float(image_threshold), out_dtype
         self.cfg = dict(pos=pos, neg=neg, flip_prob=flip_prob, rot_prob=rot_prob, shift_os=shift_os, shift_prob=shift_prob,
@@ -538,6 +614,21 @@ class DeviceDatasetLoader:
             for c in counts:
                 c = c.cpu().numpy().astype(np.int64)
                 self.cum.append((np.cumsum(c[:, 0]), np.cumsum(c[:, 1])))
+        # class-ratio crop: [D, K] cumulative counts per volume; with a dilation the candidate masks (2 bytes per voxel)
+        self.class_cum, self.class_candidates, self.masks, self.mask_ptrs = [], [], [], None
+        self.last_classes = None
+        if crop == "class_ratios":
+            K = len(self.class_ratios)
+            if self.center_dilation > 0:
+                live = [c for c in range(K) if self.class_ratios[c] > 0.0]
+                self.masks = [hip.class_candidate_mask(v["img"], v["lab"], live, self.center_dilation, self.thr, self.image_rule)
+                              for v in self.vols]
+                self.mask_ptrs = torch.tensor([m.data_ptr() for m in self.masks], dtype=torch.int64).to(device)
+            counts = [hip.class_slab_counts(v["img"], v["lab"], K, self.thr, self.image_rule,
+                                            mask=self.masks[k] if self.masks else None) for k, v in enumerate(self.vols)]
+            for c in counts:
+                self.class_cum.append(np.cumsum(c.cpu().numpy().astype(np.int64), axis=0))
+                self.class_candidates.append([int(t) for t in self.class_cum[-1][-1]])
         self.order, self.taken = [], 0
         self.launches = 0
         self.last_rows = self.last_picks = self.last_mats = None
@@ -561,6 +652,18 @@ class DeviceDatasetLoader:
             start = [int(self.rng.integers(0, n - self.roi + 1)) for n in (D, H, W)]
             fl = int(flips[0]) | int(flips[1]) << 1 | int(flips[2]) << 2
             return PickRow(vi, PICK_VOXEL, 0, 0, fl, rotk, shift, scale), start
+        if self.crop == "class_ratios":
+            (cls, idx, flips, rotk, shift, scale), = draw_class_rows(self.rng, 1, self.class_candidates[vi], self.class_ratios,
+                                                                     self.cfg)
+            fl = int(flips[0]) | int(flips[1]) << 1 | int(flips[2]) << 2
+            self._classes.append(cls)
+            if cls < 0:                                              # no candidate at all: a uniform voxel of the volume
+                flat = int(self.rng.integers(0, D * H * W))
+                return PickRow(vi, PICK_VOXEL, flat // (H * W), flat % (H * W), fl, rotk, shift, scale), None
+            cum = self.class_cum[vi][:, cls]
+            z = int(np.searchsorted(cum, idx, side="right"))
+            rank = idx - (int(cum[z - 1]) if z else 0)
+            return PickRow(vi, hip.PICK_CLASS0 + cls, z, rank, fl, rotk, shift, scale), None
         cf, cb = self.cum[vi]
         nf, nb = int(cf[-1]), int(cb[-1])
         (use_fg, idx, flips, rotk, shift, scale), = draw_rows(self.rng, 1, nf, nb, self.cfg)
@@ -579,7 +682,7 @@ class DeviceDatasetLoader:
             vis = [self._next_volume() for _ in range(self.batch)]
             aug = intensity_on(self.intensity)
             # a patch's matrix is drawn right after its other draws, its intensity rows after the matrix
-            made, irows = [], []
+            made, irows, self._classes = [], [], []
             mats = np.empty((self.batch, 3, 3), dtype=np.float64) if self.affine[0] > 0.0 else None
             for j, vi in enumerate(vis):
                 made.append(self._row(vi))
@@ -595,7 +698,11 @@ class DeviceDatasetLoader:
                 picks = host.to(self.dev, non_blocking=True)
             else:
                 picks = torch.empty(self.batch, 8, dtype=torch.int32, device=self.dev)
-                hip.pick_voxels(self.desc, len(self.vols), table, self.batch, R, self.thr, picks, self.image_rule)
+                if self.crop == "class_ratios":
+                    hip.class_pick_voxels(self.desc, len(self.vols), table, self.batch, R, self.thr, picks, self.image_rule,
+                                          masks=self.mask_ptrs)
+                else:
+                    hip.pick_voxels(self.desc, len(self.vols), table, self.batch, R, self.thr, picks, self.image_rule)
             out = torch.empty(self.batch, self.C, R, R, R, dtype=self.out_dtype, device=self.dev)
             img = torch.empty_like(out, dtype=torch.float32) if aug else out   # the gather's fp32 scratch batch
             lab = torch.empty(self.batch, 1, R, R, R, dtype=torch.float32, device=self.dev)
@@ -611,6 +718,7 @@ class DeviceDatasetLoader:
             if self.crop != "spatial":
                 host = picks.cpu()                               # the one small device-to-host copy of the batch
             self.last_rows, self.last_picks, self.last_mats = rows, host, mats
+            self.last_classes = list(self._classes) if self.crop == "class_ratios" else None
             cen = host[:, :3].float()
             recs = [self.vols[vi] for vi in vis]
             sizes = [[float(r["lab"].shape[a]) for r in recs] for a in range(3)]
@@ -618,7 +726,7 @@ class DeviceDatasetLoader:
                    "image_meta_dict": {"original_affine": _aff(recs, "original_affine"), "affine": _aff(recs, "affine"),
                                        "filename_or_obj": [r["filename"] for r in recs]},
                    "label_meta_dict": {"affine": _aff(recs, "affine")},
-                   "image_transforms": [{"class": ["RandCropByPosNegLabeld" if self.crop == "fgbg" else "RandSpatialCropd"] * self.batch,
+                   "image_transforms": [{"class": [CROP_TRANSFORM[self.crop]] * self.batch,
                                          "orig_size": [torch.tensor(s) for s in sizes],
                                          "extra_info": {"center": [cen[:, 0], cen[:, 1], cen[:, 2]]}}]}
 
@@ -686,14 +794,19 @@ class FileCaseLoader:
 
 
 def crop_mode(cfg):
-    """the crop flag of a command line -> DeviceDatasetLoader's crop mode"""
+    """the crop flag of a command line -> DeviceDatasetLoader's crop mode: "fgbg" (--t_rand_crop_fgbg), "spatial"
+    (--t_rand_spatial_crop) or "class_ratios" (--t_rand_crop_class_ratios, whose ratios and dilation
+    class_crop_config_from_args returns); two crop flags at once are a ValueError that names both"""
     check_transform_flags(cfg)
+    if class_crop_config_from_args(cfg)[0] is not None:
+        return "class_ratios"
     if cfg.t_rand_crop_fgbg:
         return "fgbg"
     if cfg.t_rand_spatial_crop:
         return "spatial"
     raise SystemExit("training on files needs a crop flag: --t_rand_crop_fgbg, --t_rand_spatial_crop or "
-                     "--t_rand_crop_classes (the last one is not implemented on the device data path)")
+                     "--t_rand_crop_classes (the last one is not implemented on the device data path), or "
+                     "--t_rand_crop_class_ratios R0 R1 ... (crop centres per class, one ratio per class)")
 
 
 def dataset_file_lists(cfg, rank, world):

@@ -146,6 +146,9 @@ SIGNATURES = {
     "msseg_pick_voxels": ([_vp, _i, _vp, _i, _i, _f, _vp, _vp], _i),
     "msseg_slab_counts_rule": ([_vp, _vp, _i, _i, _i, _f, _i, _vp, _vp], _i),
     "msseg_pick_voxels_rule": ([_vp, _i, _vp, _i, _i, _f, _i, _vp, _vp], _i),
+    "msseg_class_candidate_mask": ([_vp, _vp, _i, _i, _i, _f, _i, C.c_uint, _i, _vp, _vp, _vp], _i),
+    "msseg_class_slab_counts": ([_vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp], _i),
+    "msseg_class_pick_voxels": ([_vp, _vp, _i, _vp, _i, _i, _f, _i, _vp, _vp], _i),
     "msseg_volume_stats_scratch_bytes": ([_i], _sz),
     "msseg_select_f32": ([_vp, _i, _ll, _vp, _i, _vp, _i, _vp, _sz, _vp, _vp], _i),
     "msseg_masked_moments": ([_vp, _i, _ll, _vp, _ll, _vp, _sz, _vp, _vp], _i),
@@ -1680,6 +1683,68 @@ def pick_voxels(volumes, nvol, rows, nrows, roi, threshold, out, rule="gt"):
     assert out.is_contiguous() and out.numel() >= nrows * 8
     _ck(lib().msseg_pick_voxels_rule(_p(volumes), nvol, _p(rows), nrows, int(roi), float(threshold), _bg_rule(rule), _p(out),
                                      _stream()), "pick_voxels")
+    return out
+
+
+# ---- class-ratio crop centres (csrc/class_crop.hip) --------------------------------------------------------------------
+PICK_CLASS0 = 16            # MSSEG_PICK_CLASS0: a pick row of class c carries mode PICK_CLASS0 + c
+MAX_CROP_CLASSES = 16
+MAX_CENTER_DILATION = 254
+
+
+def _check_volume(img, lab):
+    _need_gpu(img, lab)
+    assert img.dtype == torch.float32 and lab.dtype == torch.uint8 and img.is_contiguous() and lab.is_contiguous()
+    assert img.dim() == 4 and lab.dim() == 3 and img.shape[1:] == lab.shape
+
+
+def class_candidate_mask(img, lab, classes, dilation, threshold=0.0, rule="gt"):
+    """img fp32 [C, D, H, W] (channel 0 is read), lab uint8 [D, H, W], classes: the class numbers (each in 0..15) to build
+    -> uint16 [D, H, W] on the device: bit c is set where image_ok(img[0]) (rule as slab_counts) and a voxel of label c lies
+    within L1 distance `dilation` (0..254); bits of other classes are 0.  One byte per voxel of scratch for the call."""
+    _check_volume(img, lab)
+    n = int(dilation)
+    if not 0 <= n <= MAX_CENTER_DILATION:
+        raise ValueError(f"centre dilation {dilation!r}: 0..{MAX_CENTER_DILATION} (the chamfer distances are bytes)")
+    bits = 0
+    for c in classes:
+        if not 0 <= int(c) < MAX_CROP_CLASSES:
+            raise ValueError(f"class {c!r}: 0..{MAX_CROP_CLASSES - 1}")
+        bits |= 1 << int(c)
+    mask = torch.empty(lab.shape, dtype=torch.uint16, device=lab.device)
+    scratch = torch.empty(lab.shape, dtype=torch.uint8, device=lab.device)
+    _ck(lib().msseg_class_candidate_mask(_p(img), _p(lab), *lab.shape, float(threshold), _bg_rule(rule), bits, n, _p(scratch),
+                                         _p(mask), _stream()), "class_candidate_mask")
+    return mask
+
+
+def class_slab_counts(img, lab, n_classes, threshold=0.0, rule="gt", mask=None):
+    """-> int32 [D, n_classes] on the device: per z-slice the candidates of every class c < n_classes (<= 16), i.e.
+    #(lab == c and image_ok(img[0])), or, with a class_candidate_mask(...) `mask`, #(bit c of mask)"""
+    _check_volume(img, lab)
+    K = int(n_classes)
+    if not 1 <= K <= MAX_CROP_CLASSES:
+        raise ValueError(f"{n_classes!r} classes: 1..{MAX_CROP_CLASSES}")
+    if mask is not None:
+        _need_gpu(mask)
+        assert mask.dtype == torch.uint16 and mask.is_contiguous() and mask.shape == lab.shape
+    out = torch.empty(lab.shape[0], K, dtype=torch.int32, device=lab.device)
+    _ck(lib().msseg_class_slab_counts(_p(img), _p(lab), _p(mask), *lab.shape, K, float(threshold), _bg_rule(rule), _p(out),
+                                      _stream()), "class_slab_counts")
+    return out
+
+
+def class_pick_voxels(volumes, nvol, rows, nrows, roi, threshold, out, rule="gt", masks=None):
+    """pick_voxels whose rows may carry mode PICK_CLASS0 + c: the rank-th candidate of class c of the row's slice.  masks:
+    None, or an int64 device tensor of nvol pointers to the volumes' candidate masks (0: that volume has none; its class
+    rows then read the label)"""
+    _need_gpu(volumes, rows, out, masks)
+    assert volumes.numel() >= nvol * 32 and rows.numel() >= nrows * 32 and out.dtype == torch.int32
+    assert out.is_contiguous() and out.numel() >= nrows * 8
+    if masks is not None:
+        assert masks.dtype == torch.int64 and masks.is_contiguous() and masks.numel() >= nvol
+    _ck(lib().msseg_class_pick_voxels(_p(volumes), _p(masks), nvol, _p(rows), nrows, int(roi), float(threshold),
+                                      _bg_rule(rule), _p(out), _stream()), "class_pick_voxels")
     return out
 
 

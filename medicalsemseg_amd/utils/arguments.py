@@ -1,7 +1,7 @@
 """CLI of the training / evaluation drivers: every flag of ``/root/reference/utils/arguments.py:29-313`` with
 the same name, type, default and list-collapsing rule (``:19-24``: a list argument of length 1 becomes a scalar,
 longer lists become tuples), declared as a table; plus a few flags of this build (synthetic data, compute
-dtype, hipGraph replay, post-processing, rotation + zoom in the device crop gather, mirror test-time augmentation, intensity augmentation, per-volume z-score, file inference).  Flags whose subsystem is out of the hot-path scope (learned class vectors, MONAI
+dtype, hipGraph replay, post-processing, rotation + zoom in the device crop gather, mirror test-time augmentation, intensity augmentation, per-volume z-score, class-ratio crop centres, file inference).  Flags whose subsystem is out of the hot-path scope (learned class vectors, MONAI
 transforms, Neptune) are accepted and ignored so reference command lines keep working."""
 from __future__ import annotations
 
@@ -81,6 +81,11 @@ _SPEC = {
         # last preprocessing step (data_device.py, csrc/volume_stats.hip; nnU-Net's per-volume z-score); --t_zscore_clip
         # LO HI first clips those voxels to the channel's own percentiles, e.g. 0.5 99.5
         ("--t_zscore", "t"), ("--t_zscore_clip", "l", [], F),
+        # crop centres per class (data_device.py, csrc/class_crop.hip; the reference's --t_rand_crop_classes is the case NEG
+        # POS POS ...): one ratio >= 0 per class, --output_dim of them; a crop flag like --t_rand_crop_fgbg.
+        # --t_rand_crop_center_dilation N takes the centres within L1 distance N (0..254) of a class instead of on it (the
+        # reference's --t_rand_crop_dilated_center is N = 48)
+        ("--t_rand_crop_class_ratios", "l", [], F), ("--t_rand_crop_center_dilation", "v", 0, I),
     ],
     "file inference": [  # run_predict.py: the files of a data list (engine/test.py, csrc/restore.hip)
         # the section of the data list to predict (labels of "validation" / "training" are ignored)

@@ -34,9 +34,10 @@ from medicalsemseg_amd.utils.arguments import get_args
 def file_loaders(cfg, device, seed, vol):
     """Decathlon data list -> this rank's training / validation volumes, preprocessed once and cached in HBM
     (the reference's ``data/dataset_builder.py:431-491``; transforms :19-306 as device kernels, MONAI parity unpinned)"""
-    from medicalsemseg_amd.data_device import (DeviceDatasetLoader, DeviceVolumeLoader, build_cache, crop_mode,
-                                               dataset_file_lists, intensity_config_from_args, normalised_zero)
+    from medicalsemseg_amd.data_device import (DeviceDatasetLoader, DeviceVolumeLoader, build_cache, class_crop_config_from_args,
+                                               crop_mode, dataset_file_lists, intensity_config_from_args, normalised_zero)
     crop = crop_mode(cfg)
+    class_ratios, center_dilation = class_crop_config_from_args(cfg)
     rank, world = misc.get_rank(), misc.get_world_size()
     part_train, part_val, train, val = dataset_file_lists(cfg, rank, world)
     if misc.is_main_process():
@@ -69,13 +70,46 @@ def file_loaders(cfg, device, seed, vol):
                                        # noise, blur, contrast and gamma on the gathered batch
                                        intensity=intensity_config_from_args(cfg),
                                        # on a z-scored cache the reference's `raw image > 0` is the non-zero mask
-                                       image_rule="ne" if cfg.t_zscore else "gt")
+                                       image_rule="ne" if cfg.t_zscore else "gt",
+                                       # crop centres per class, on the class or within a distance of it
+                                       class_ratios=class_ratios, center_dilation=center_dilation)
+    report_class_candidates(loader_train, rank)
     return loader_train, DeviceVolumeLoader(rec_val)
+
+
+def report_class_candidates(loader, rank):
+    """class-ratio crop: every rank prints the crop-centre candidates per class of each of its volumes"""
+    if loader.crop != "class_ratios":
+        return
+    for rec, counts in zip(loader.vols, loader.class_candidates):
+        sys.stdout.write("rank {}: {} crop-centre candidates per class (ratios {}, dilation {}): {}\n".format(
+            rank, os.path.basename(str(rec["filename"])), list(loader.class_ratios), loader.center_dilation, counts))
+    sys.stdout.flush()
 
 
 def synthetic_loaders(cfg, device, seed, vol):
     vval = cfg.synthetic_val_size if isinstance(cfg.synthetic_val_size, int) else cfg.synthetic_val_size[0]
-    if cfg.t_rand_crop_fgbg:
+    from medicalsemseg_amd.data_device import class_crop_config_from_args
+    class_ratios, center_dilation = class_crop_config_from_args(cfg)
+    if class_ratios is not None:
+        # the class-ratio crop of the dataset path on the one synthetic volume, wrapped in a cache record
+        from medicalsemseg_amd.data import sphere_labels
+        from medicalsemseg_amd.data_device import DeviceDatasetLoader, intensity_config_from_args
+        g = torch.Generator().manual_seed(seed)
+        lab = sphere_labels(2 * vol, cfg.output_dim)
+        img = torch.randn(cfg.in_chans, 2 * vol, 2 * vol, 2 * vol, generator=g) + 0.5 * lab[None]
+        rec = {"img": img.to(device).contiguous(), "lab": lab.to(device=device, dtype=torch.uint8).contiguous(),
+               "affine": np.eye(4), "original_affine": np.eye(4), "filename": "synthetic_volume"}
+        loader_train = DeviceDatasetLoader([rec], vol, cfg.n_images_per_batch, cfg.synthetic_steps, 1, device, seed=seed,
+                                           crop="class_ratios", flip_prob=cfg.t_flip_prob, rot_prob=cfg.t_rot_prob,
+                                           shift_os=cfg.t_intensity_shift_os, shift_prob=cfg.t_intensity_shift_prob,
+                                           scale_f=cfg.t_intensity_scale_factors, scale_prob=cfg.t_intensity_scale_prob,
+                                           image_threshold=-1e9, affine_prob=cfg.t_affine_prob,
+                                           affine_rotate=cfg.t_affine_rotate, affine_zoom=cfg.t_affine_zoom, affine_pad=0.0,
+                                           intensity=intensity_config_from_args(cfg), class_ratios=class_ratios,
+                                           center_dilation=center_dilation)
+        report_class_candidates(loader_train, misc.get_rank())
+    elif cfg.t_rand_crop_fgbg:
         # device-side data path (SURVEY.md 8(f) N1): one synthetic "CT" of 2x the patch size cached in HBM, patches cropped
         # (fg / bg centres with the reference's pos : neg odds) and augmented by one gather kernel per batch
         from medicalsemseg_amd.data import sphere_labels
