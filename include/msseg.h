@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MSSEG_ABI_VERSION 2
+#define MSSEG_ABI_VERSION 3
 
 #define MSSEG_OK 0
 #define MSSEG_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -132,16 +132,13 @@ int msseg_zero_stuff2(const void* dy, long long lddy, void* out, long long ldo, 
 /* Conv3d k=3 s=1 p=1 with ONE input channel (BasicUNet conv_0.conv_0, the stem): dedicated kernel, bf16, Cout % 32 == 0 or
  * % 48 == 0 (Swin-UNETR's 1 -> 48 first conv); y == NULL with stats != NULL: statistics only, nothing is stored;
  * wp = the msseg_pack_weights image used by msseg_conv3d_gather_fwd (K = 27); optional fused statistics as
- * msseg_conv3d_k3_fwd.  msseg_conv3d_gather_fwd / _wgrad route eligible problems here by themselves; this entry
- * point adds the statistics.  Returns MSSEG_EINVAL for problems the stem kernel does not cover. */
+ * msseg_conv3d_k3_fwd.  k = 3, or k = 1: the 1x1x1 convolution of a one-channel volume (UnetResBlock conv3 of Swin-UNETR's
+ * encoder1; wp = the gather image with K = 1) on the same kernel, centre tap only; any other k is MSSEG_EINVAL.
+ * msseg_conv3d_gather_fwd / _wgrad route eligible problems here by themselves; this entry point adds the statistics.
+ * Returns MSSEG_EINVAL for problems the stem kernel does not cover. */
 int msseg_conv3d_stem_fwd(const void* x, long long ldx, const void* wp, const float* bias, void* y, long long ldy,
-                          int N, int D, int H, int W, int Cout, float* stats, void* scratch, size_t scratch_bytes,
+                          int N, int D, int H, int W, int Cout, int k, float* stats, void* scratch, size_t scratch_bytes,
                           int dtype, msseg_stream_t stream);
-/* ... the 1x1x1 convolution of a one-channel volume (UnetResBlock conv3 of Swin-UNETR's encoder1; wp = the gather image with
- * K = 1) on the same kernel: centre tap only, same optional statistics */
-int msseg_conv3d_stem_k1_fwd(const void* x, long long ldx, const void* wp, const float* bias, void* y, long long ldy,
-                             int N, int D, int H, int W, int Cout, float* stats, void* scratch, size_t scratch_bytes,
-                             int dtype, msseg_stream_t stream);
 /* Inference form of the stem unit: y = lrelu(instance_norm(conv(x) + bias) * gamma + beta) with the statistics stats[N][Cout][2]
  * of a statistics-only msseg_conv3d_stem_fwd call in front -- the one-channel conv is cheap enough to run twice, and the raw
  * output's write and the normalisation pass over it disappear (sliding-window inference of BasicUNet at 96^3 windows). */
@@ -156,15 +153,6 @@ int msseg_conv3d_k1_fwd(const void* x, long long ldx, const void* wp, const floa
  * MSSEG_EINVAL for other shapes (use msseg_conv3d_k1_fwd). */
 int msseg_conv3d_k1_head_fwd(const void* x, long long ldx, const float* w, const float* bias, void* y, long long ldy,
                              long long NV, int Cin, int Cout, int dtype, msseg_stream_t stream);
-/* Its input gradient fused with the InstanceNorm-backward sums of the layer that feeds the head (as
- * msseg_conv3d_k1_dgrad_inbwd, same streaming form): da[v][c] = sum_k dy[v][k] * w[k][c] for the C channels of that
- * layer, red[n][c] = (sum dz, sum dz*xhat) with the LeakyReLU sign recomputed from yraw (gamma, beta nullable),
- * dgamma/dbeta written or accumulated.  dy rows 16-byte aligned with >= 4 readable channels (classes zero-padded). */
-int msseg_conv3d_k1_head_dgrad_inbwd(const void* dy, long long lddy, const float* w, void* da, long long ldda, int N,
-                                     long long S, int C, int Cout, const void* yraw, long long ldyraw,
-                                     const float* fwd_stats, const float* gamma, const float* beta, float slope, float eps,
-                                     float* red, float* dgamma, float* dbeta, int accumulate, void* scratch,
-                                     size_t scratch_bytes, int dtype, msseg_stream_t stream);
 /* The head reading the RAW conv output `x` of the last conv + InstanceNorm + LeakyReLU unit (N samples of S voxels):
  * y = conv1x1(T(lrelu(IN(x) * gamma + beta))) with the normalisation applied in registers -- the unit's activation is
  * never written.  stats: [N][Cin][2] (sum, sum of squares) of x.  Replaces InstanceNorm3d + LeakyReLU + final Conv3d(k=1)
@@ -172,9 +160,12 @@ int msseg_conv3d_k1_head_dgrad_inbwd(const void* dy, long long lddy, const float
 int msseg_conv3d_k1_head_norm_fwd(const void* x, long long ldx, const float* stats, const float* gamma, const float* beta,
                                   float slope, float eps, const float* w, const float* bias, void* y, long long ldy, int N,
                                   long long S, int Cin, int Cout, int dtype, msseg_stream_t stream);
-/* msseg_conv3d_k1_head_dgrad_inbwd plus the head's weight gradient dw[Cout][C] (+)= sum_v dy[v][k] * a[v][c] with the
- * activation a recomputed from yraw (as the fused forward does): one streaming pass for da, the InstanceNorm-backward sums
- * and dw. */
+/* The head's backward in one streaming pass.  Its input gradient fused with the InstanceNorm-backward sums of the layer
+ * that feeds the head (as msseg_conv3d_k1_dgrad_inbwd, same streaming form): da[v][c] = sum_k dy[v][k] * w[k][c] for the C
+ * channels of that layer, red[n][c] = (sum dz, sum dz*xhat) with the LeakyReLU sign recomputed from yraw (gamma, beta
+ * nullable), dgamma/dbeta written or accumulated.  dy rows 16-byte aligned with >= 4 readable channels (classes
+ * zero-padded).  dw (nullable: no weight gradient): dw[Cout][C] (+)= sum_v dy[v][k] * a[v][c] with the activation a
+ * recomputed from yraw (as the fused forward does).  da == NULL (dw given): da is not stored. */
 int msseg_conv3d_k1_head_bwd_fused(const void* dy, long long lddy, const float* w, void* da, long long ldda, int N,
                                    long long S, int C, int Cout, const void* yraw, long long ldyraw, const float* fwd_stats,
                                    const float* gamma, const float* beta, float slope, float eps, float* red, float* dgamma,
@@ -562,33 +553,23 @@ int msseg_linear_add_fwd(const void* x, long long ldx, const void* wp, const flo
  * logits: channels-last [N, S, ld] with ld >= C the voxel stride, or NCDHW when ld == 0; labels: one value
  * per voxel; C <= 16.
  * ------------------------------------------------------------------------------------------- */
-/* partial[n][c][0..3] += (sum p*t, sum p^2, sum t, -sum t*log p); hard[n][c][0..2] += (|P&T|, |P|, |T|)
- * (either pointer may be NULL).  label_dtype: 0 = f32, 1 = bf16, 2 = u8, 3 = i64. */
-int msseg_dice_ce_partials(const void* logits, long long ld, int dtype, const void* labels, int label_dtype,
-                           float* partial, float* hard, int N, long long S, int C, msseg_stream_t stream);
-/* loss[0] = mean_{n,c}(1 - (2I+snr)/(den+sdr)) + CE ; loss[1] = dice term, loss[2] = ce term. */
-/* Deterministic one-call form of the forward (N <= 8): per-block partial rows in `scratch` (the reduce scratch,
- * msseg_reduce_scratch_bytes()), added in a fixed order by a one-block second step that also writes partial[N][C][4],
- * hard[N][C][3] (nullable) and loss[3] = (dice + ce, dice, ce).  No zero-initialised outputs, no atomics: two runs on the
- * same inputs give the same bits. */
-int msseg_dice_ce_fwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype, float* partial,
-                      float* hard, float* loss, int N, long long S, int C, float smooth_nr, float smooth_dr, void* scratch,
-                      size_t scratch_bytes, msseg_stream_t stream);
-int msseg_dice_ce_finalize(const float* partial, float* loss, int N, long long S, int C, float smooth_nr,
-                           float smooth_dr, msseg_stream_t stream);
-/* dlogits = gscale[0] * dLoss/dlogits (same layout/dtype as logits). */
-int msseg_dice_ce_bwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype,
-                      const float* partial, const float* gscale, void* dlogits, long long ldd, int N, long long S,
-                      int C, float smooth_nr, float smooth_dr, msseg_stream_t stream);
-
-/* The same four passes for a loss `kind`; the dice_ce_* entry points above are kind MSSEG_LOSS_DICE_CE.
+/* Four passes for a loss `kind`:
+ *  MSSEG_LOSS_DICE_CE: the loss above.
  *  MSSEG_LOSS_TVERSKY (MONAI TverskyLoss(to_onehot_y, softmax, alpha, beta), no squared prediction): slot 1 of partial is
  *    sum p, slot 3 stays 0; loss = mean_{n,c}(1 - (I + snr) / (I + alpha*(P - I) + beta*(T - I) + sdr)); loss[3] =
  *    (tversky, tversky, 0).
  *  MSSEG_LOSS_DICE_FOCAL (MONAI DiceFocalLoss(to_onehot_y, softmax, squared_pred), gamma 2, lambdas 1): slot 3 of partial
  *    is the sum of the SIGMOID focal values of the raw logits (MONAI's FocalLoss does not see the softmax flag), the focal
  *    term their mean over N*C*S elements; loss[3] = (dice + focal, dice, focal).
- *  alpha, beta are read by MSSEG_LOSS_TVERSKY only.  hard[] does not depend on the kind. */
+ *  alpha, beta are read by MSSEG_LOSS_TVERSKY only.  hard[] does not depend on the kind.
+ * partials: partial[n][c][0..3] += (sum p*t, sum p^2, sum t, -sum t*log p); hard[n][c][0..2] += (|P&T|, |P|, |T|)
+ *    (either pointer may be NULL).  label_dtype: 0 = f32, 1 = bf16, 2 = u8, 3 = i64.
+ * finalize: loss[0] = mean_{n,c}(1 - (2I+snr)/(den+sdr)) + CE ; loss[1] = dice term, loss[2] = ce term.
+ * fwd: deterministic one-call form of the forward (N <= 8): per-block partial rows in `scratch` (the reduce scratch,
+ *    msseg_reduce_scratch_bytes()), added in a fixed order by a one-block second step that also writes partial[N][C][4],
+ *    hard[N][C][3] (nullable) and loss[3] = (dice + ce, dice, ce).  No zero-initialised outputs, no atomics: two runs on the
+ *    same inputs give the same bits.
+ * bwd: dlogits = gscale[0] * dLoss/dlogits (same layout/dtype as logits). */
 #define MSSEG_LOSS_DICE_CE 0
 #define MSSEG_LOSS_TVERSKY 1
 #define MSSEG_LOSS_DICE_FOCAL 2
@@ -630,29 +611,21 @@ int msseg_sw_normalize(float* out, const float* cnt, int C, long long V, msseg_s
  * blend : out[b][c][vol] += imp * win[j][c], cnt[b][vol] += imp for every window of the table, each output voxel
  *         accumulated in table order with the reference's roundings (bit-identical to blending the nwin windows one
  *         after the other); windows of one batch may overlap.  nwin <= 256, C <= 16. */
-int msseg_sw_gather_batch(const float* vol, long long vol_bstride, void* win, long long ldw, int dtype, const int* table,
-                          int nwin, int C, int VD, int VH, int VW, int RD, int RH, int RW, float cval,
-                          msseg_stream_t stream);
-int msseg_sw_blend_batch(const void* win, long long ldw, int dtype, const float* imp, float* out, long long out_bstride,
-                         float* cnt, long long cnt_bstride, const int* table, int nwin, int C, int VD, int VH, int VW,
-                         int RD, int RH, int RW, msseg_stream_t stream);
-/* The same two launches with a mirror mask per table row (mirror test-time augmentation: a (window, mask) pair is one
- * more row).  flips: device int32 [nwin], bit 0 / 1 / 2 set = row j is mirrored along D / H / W; null = no row is
- * mirrored, which is exactly the two calls above (they forward here).  With f(r) = R - 1 - r on a mirrored axis of
- * extent R and f(r) = r otherwise:
+/* A mirror mask per table row (mirror test-time augmentation: a (window, mask) pair is one more row).  flips: device
+ * int32 [nwin], bit 0 / 1 / 2 set = row j is mirrored along D / H / W; null = no row is mirrored, which is exactly the
+ * above.  With f(r) = R - 1 - r on a mirrored axis of extent R and f(r) = r otherwise:
  * gather: win[j][rz][ry][rx] = vol[b][z0 + fz(rz)][y0 + fy(ry)][x0 + fx(rx)], `cval` outside -- the window as above,
  *         flipped along the mirrored axes.
  * blend : out[b][c][z0+dz][y0+dy][x0+dx] += imp[dz][dy][dx] * win[j][c][fz(dz)][fy(dy)][fx(dx)], cnt += imp[dz][dy][dx]:
  *         the logits are un-mirrored on the way in, the weight is NOT mirrored (it is indexed in volume orientation;
  *         the Gaussian map of an even extent peaks at R / 2 and is not symmetric).  Order and roundings as above;
  *         rows of one start under several masks overlap completely.  RD, RH, RW are independent, even or odd. */
-int msseg_sw_gather_batch_mirror(const float* vol, long long vol_bstride, void* win, long long ldw, int dtype,
-                                 const int* table, const int* flips, int nwin, int C, int VD, int VH, int VW, int RD,
-                                 int RH, int RW, float cval, msseg_stream_t stream);
-int msseg_sw_blend_batch_mirror(const void* win, long long ldw, int dtype, const float* imp, float* out,
-                                long long out_bstride, float* cnt, long long cnt_bstride, const int* table,
-                                const int* flips, int nwin, int C, int VD, int VH, int VW, int RD, int RH, int RW,
-                                msseg_stream_t stream);
+int msseg_sw_gather_batch(const float* vol, long long vol_bstride, void* win, long long ldw, int dtype, const int* table,
+                          const int* flips, int nwin, int C, int VD, int VH, int VW, int RD, int RH, int RW, float cval,
+                          msseg_stream_t stream);
+int msseg_sw_blend_batch(const void* win, long long ldw, int dtype, const float* imp, float* out, long long out_bstride,
+                         float* cnt, long long cnt_bstride, const int* table, const int* flips, int nwin, int C, int VD,
+                         int VH, int VW, int RD, int RH, int RW, msseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Layout passes of the vendored MONAI Swin-UNETR encoder (csrc/layout.hip; /root/reference/models/segmentors/
@@ -798,13 +771,12 @@ int msseg_aug_crop_batch(const float* img, const uint8_t* lab, int C, int VD, in
  *            (fp32, is_label 0): trilinear, border clamped; label (uint8, is_label 1): nearest, floor(c + 0.5).
  * crop_pad_copy: dst[c][pad_before + i] = src[c][box start + i] for i inside box6 = {z0, y0, x0, z1, y1, x1} (half-open,
  *            HOST ints, as pad_before3), the pad value elsewhere; elem_bytes 4 (fp32) or 1 (uint8).
- * slab_counts: counts[z] = {#(lab > 0), #(lab == 0 && img0 > threshold)} per z-slice, int32 [D][2] on the device.
+ * slab_counts: counts[z] = {#(lab > 0), #(lab == 0 && image_ok(img0))} per z-slice, int32 [D][2] on the device.  The image
+ *            side of a background candidate is chosen by bg_rule: 0 = img0 > threshold, 1 = img0 != threshold: the non-zero
+ *            mask of a z-scored cache (msseg_zscore_apply), whose in-mask values have either sign.
  * pick_voxels: rows[i] = msseg_pick_row; mode 1 / 0: the rank-th foreground / background voxel (flat order) of slice z of
  *            volume vol; mode 2: rank IS the in-slice flat index.  out[i][8] = {centre z, y, x (MONAI correct_crop_centers
  *            clamp for the cubic roi R), crop start z, y, x, z, in-slice flat index of the voxel (-1: rank beyond the count)}.
- * slab_counts_rule / pick_voxels_rule: the two above with the image side of a background candidate chosen by bg_rule:
- *            0 = img0 > threshold (what the entry points without _rule forward), 1 = img0 != threshold: the non-zero mask of
- *            a z-scored cache (msseg_zscore_apply), whose in-mask values have either sign.
  * aug_crop_multi: msseg_aug_crop_batch over many volumes: row i reads volume rows[i].vol at the crop start picks[i][3..5]
  *            (clamped into the volume) with the row's flips / rotk / shift / scale; out_img [npatch][C][R][R][R] fp32 or bf16,
  *            out_lab fp32 [npatch][1][R][R][R].  One launch per batch.  Precondition (the tables live on the device, so the
@@ -829,14 +801,10 @@ int msseg_resample_spacing(const void* src, int is_label, int C, int SD, int SH,
                            double rz, double ry, double rx, msseg_stream_t stream);
 int msseg_crop_pad_copy(const void* src, int elem_bytes, int C, int SD, int SH, int SW, const int* box6, void* dst, int TD,
                         int TH, int TW, const int* pad_before3, float pad_f32, int pad_u8, msseg_stream_t stream);
-int msseg_slab_counts(const float* img0, const uint8_t* lab, int D, int H, int W, float threshold, int* counts,
+int msseg_slab_counts(const float* img0, const uint8_t* lab, int D, int H, int W, float threshold, int bg_rule, int* counts,
                       msseg_stream_t stream);
-int msseg_pick_voxels(const void* volumes, int nvol, const void* rows, int nrows, int R, float threshold, int* out,
+int msseg_pick_voxels(const void* volumes, int nvol, const void* rows, int nrows, int R, float threshold, int bg_rule, int* out,
                       msseg_stream_t stream);
-int msseg_slab_counts_rule(const float* img0, const uint8_t* lab, int D, int H, int W, float threshold, int bg_rule, int* counts,
-                           msseg_stream_t stream);
-int msseg_pick_voxels_rule(const void* volumes, int nvol, const void* rows, int nrows, int R, float threshold, int bg_rule,
-                           int* out, msseg_stream_t stream);
 int msseg_aug_crop_multi(const void* volumes, int nvol, const void* rows, const int* picks, int npatch, int C, void* out_img,
                          int out_dtype, float* out_lab, int R, msseg_stream_t stream);
 int msseg_aug_crop_affine(const void* volumes, int nvol, const void* rows, const int* picks, const double* mats, int npatch,
@@ -845,7 +813,7 @@ int msseg_aug_crop_affine(const void* volumes, int nvol, const void* rows, const
 /* ---------------------------------------------------------------------------------------------
  * Class-ratio crop centres (csrc/class_crop.hip; the reference's RandCropByLabelClassesd, --t_rand_crop_class_ratios /
  * --t_rand_crop_center_dilation here).  Semantics: tests/class_crop_ref.py.  With image_ok(v) = v > threshold (bg_rule 0)
- * or v != threshold (bg_rule 1) as in slab_counts_rule, voxel v is a candidate of class c < K iff image_ok(img0(v)) and a
+ * or v != threshold (bg_rule 1) as in slab_counts, voxel v is a candidate of class c < K iff image_ok(img0(v)) and a
  * voxel u with lab(u) == c exists with |u - v|_1 <= N; N = 0: lab(v) == c.  Label values >= K belong to no class.
  * A class pick is a msseg_pick_row with mode = MSSEG_PICK_CLASS0 + c; the gather kernels never read mode.
  * class_candidate_mask: N > 0, once per cached volume.  mask (device, uint16 [D][H][W]) gets bit c = that predicate for every
@@ -855,10 +823,10 @@ int msseg_aug_crop_affine(const void* volumes, int nvol, const void* rows, const
  *            binary_dilation(lab == c, iterations=N) with the default structure.
  * class_slab_counts: counts[z][c], int32 [D][K] on the device, 1 <= K <= 16: the candidates of class c in slice z, read from
  *            mask when it is not NULL (img0 and lab are then unused and may be NULL), from (img0, lab) with N = 0 otherwise.
- * class_pick_voxels: pick_voxels_rule whose rows may also carry mode 16 + c: the rank-th candidate of class c (flat order)
+ * class_pick_voxels: pick_voxels whose rows may also carry mode 16 + c: the rank-th candidate of class c (flat order)
  *            of slice z of volume vol, read from masks[vol] when masks (NULL, or a device array of nvol mask pointers) and
  *            that entry are not NULL, from the volume's label with N = 0 otherwise.  Rows of mode 0, 1, 2 and the output
- *            row are exactly those of pick_voxels_rule; any other mode reports -1 as a rank beyond the count does.
+ *            row are exactly those of pick_voxels; any other mode reports -1 as a rank beyond the count does.
  * ------------------------------------------------------------------------------------------- */
 #define MSSEG_PICK_CLASS0 16
 int msseg_class_candidate_mask(const float* img0, const uint8_t* lab, int D, int H, int W, float threshold, int bg_rule,

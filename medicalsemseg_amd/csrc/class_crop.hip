@@ -9,7 +9,7 @@
 //                         class along x, then + y, then + z, capped at N + 1); the last sweep folds in image_ok and ORs the bit.
 //   class_slab_counts     counts[z][c] from (img0, lab) or from the mask; one block per slice, integer counting
 //   class_pick_voxels     pick_voxels with the per-class predicates: mode 16 + c is the rank-th candidate of class c of the
-//                         slice; modes 0 / 1 / 2 as msseg_pick_voxels_rule (one scan, pick_scan.h)
+//                         slice; modes 0 / 1 / 2 as msseg_pick_voxels (one scan, pick_scan.h)
 //
 // Semantics: the numpy / scipy restatement in tests/class_crop_ref.py.  Geometry: lanes run along x everywhere.
 #include "common.h"

@@ -176,6 +176,42 @@ __global__ __launch_bounds__(256) void pick_voxels_kernel(const VolDesc* __restr
     if (threadIdx.x == 0) pick::write_pick(o, vd, z, hit, R);
 }
 
+// Row prologue shared by the two crop gathers below; (z, y) is the thread's output row of patch b.
+// *vd = the row's volume; true when the patch can be read from it.  A row that names no volume, or a volume that cannot
+// hold the patch: this thread's share of a defined all-zero patch is written, nothing is read, and the answer is false.
+template <typename TO>
+MSSEG_DEVFN bool crop_row_volume(const VolDesc* __restrict__ vols, int nvol, const PickRow& row, int b, int z, int y,
+                                 TO* __restrict__ out_img, float* __restrict__ out_lab, int C, int R, VolDesc* vd) {
+    const bool known = row.vol >= 0 && row.vol < nvol;
+    *vd = vols[known ? row.vol : 0];
+    if (known && vd->C == C && R <= vd->D && R <= vd->H && R <= vd->W) return true;
+    const long long R3 = (long long)R * R * R, orow = ((long long)z * R + y) * R;
+    for (int x = threadIdx.x; x < R; x += blockDim.x) {
+        for (int c = 0; c < C; ++c) DT<TO>::st(out_img + ((long long)b * C + c) * R3 + orow + x, 0.0f);
+        out_lab[(long long)b * R3 + orow + x] = 0.0f;
+    }
+    return false;
+}
+
+// crop start from the pick table, kept inside the volume whatever the table holds
+MSSEG_DEVFN void crop_start(const int* __restrict__ picks, int b, const VolDesc& vd, int R, int* z0, int* y0, int* x0) {
+    const int pz = picks[8 * b + 3], py = picks[8 * b + 4], px = picks[8 * b + 5];
+    *z0 = pz < 0 ? 0 : (pz > vd.D - R ? vd.D - R : pz);
+    *y0 = py < 0 ? 0 : (py > vd.H - R ? vd.H - R : py);
+    *x0 = px < 0 ? 0 : (px > vd.W - R ? vd.W - R : px);
+}
+
+// patch index (sz, sy) of output row (z, y): rot90^k in the (z, y) plane undone -- out[i, j] = m[j, n-1-i] (k = 1),
+// m[n-1-i, n-1-j] (2), m[n-1-j, i] (3) -- then the flips along z and y; the flip along x is left to the caller's x loop
+MSSEG_DEVFN void patch_row_index(const PickRow& row, int z, int y, int R, int* sz, int* sy) {
+    *sz = z; *sy = y;
+    if (row.rotk == 1) { *sz = y; *sy = R - 1 - z; }
+    else if (row.rotk == 2) { *sz = R - 1 - z; *sy = R - 1 - y; }
+    else if (row.rotk == 3) { *sz = R - 1 - y; *sy = z; }
+    if (row.flips & 1) *sz = R - 1 - *sz;
+    if (row.flips & 2) *sy = R - 1 - *sy;
+}
+
 // grid: (y tiles, R, npatch), block (runs of 4 along x, rows).  Every thread moves runs of 4 consecutive output x.
 template <typename TO>
 __global__ __launch_bounds__(256) void aug_crop_multi_kernel(const VolDesc* __restrict__ vols, int nvol,
@@ -185,29 +221,11 @@ __global__ __launch_bounds__(256) void aug_crop_multi_kernel(const VolDesc* __re
     const int b = blockIdx.z, z = blockIdx.y, y = blockIdx.x * blockDim.y + threadIdx.y;
     if (y >= R) return;
     const PickRow row = rows[b];
-    const bool known = row.vol >= 0 && row.vol < nvol;
-    const VolDesc vd = vols[known ? row.vol : 0];
-    if (!known || vd.C != C || R > vd.D || R > vd.H || R > vd.W) {
-        // a row that names no volume, or a volume that cannot hold the patch: a defined all-zero patch, no read
-        const long long R3z = (long long)R * R * R, oz = ((long long)z * R + y) * R;
-        for (int x = threadIdx.x; x < R; x += blockDim.x) {
-            for (int c = 0; c < C; ++c) DT<TO>::st(out_img + ((long long)b * C + c) * R3z + oz + x, 0.0f);
-            out_lab[(long long)b * R3z + oz + x] = 0.0f;
-        }
-        return;
-    }
-    // crop start from the pick table, kept inside the volume whatever the table holds
-    int z0 = picks[8 * b + 3], y0 = picks[8 * b + 4], x0 = picks[8 * b + 5];
-    z0 = z0 < 0 ? 0 : (z0 > vd.D - R ? vd.D - R : z0);
-    y0 = y0 < 0 ? 0 : (y0 > vd.H - R ? vd.H - R : y0);
-    x0 = x0 < 0 ? 0 : (x0 > vd.W - R ? vd.W - R : x0);
-    // undo rot90^k in the (z, y) plane: out[i, j] = m[j, n-1-i] (k = 1), m[n-1-i, n-1-j] (2), m[n-1-j, i] (3)
-    int sz = z, sy = y;
-    if (row.rotk == 1) { sz = y; sy = R - 1 - z; }
-    else if (row.rotk == 2) { sz = R - 1 - z; sy = R - 1 - y; }
-    else if (row.rotk == 3) { sz = R - 1 - y; sy = z; }
-    if (row.flips & 1) sz = R - 1 - sz;
-    if (row.flips & 2) sy = R - 1 - sy;
+    VolDesc vd;
+    if (!crop_row_volume(vols, nvol, row, b, z, y, out_img, out_lab, C, R, &vd)) return;
+    int z0, y0, x0, sz, sy;
+    crop_start(picks, b, vd, R, &z0, &y0, &x0);
+    patch_row_index(row, z, y, R, &sz, &sy);
     const bool fx = (row.flips & 4) != 0;
     const long long V = (long long)vd.D * vd.H * vd.W, R3 = (long long)R * R * R;
     const long long srow = ((long long)(z0 + sz) * vd.H + (y0 + sy)) * vd.W + x0;
@@ -262,27 +280,12 @@ __global__ __launch_bounds__(256) void aug_crop_affine_kernel(const VolDesc* __r
     const int b = blockIdx.z, z = blockIdx.y, y = blockIdx.x * blockDim.y + threadIdx.y;
     if (y >= R) return;
     const PickRow row = rows[b];
-    const bool known = row.vol >= 0 && row.vol < nvol;
-    const VolDesc vd = vols[known ? row.vol : 0];
+    VolDesc vd;
+    if (!crop_row_volume(vols, nvol, row, b, z, y, out_img, out_lab, C, R, &vd)) return;
+    int z0, y0, x0, sz, sy;
+    crop_start(picks, b, vd, R, &z0, &y0, &x0);
+    patch_row_index(row, z, y, R, &sz, &sy);
     const long long R3 = (long long)R * R * R, orow = ((long long)z * R + y) * R;
-    if (!known || vd.C != C || R > vd.D || R > vd.H || R > vd.W) {
-        for (int x = threadIdx.x; x < R; x += blockDim.x) {
-            for (int c = 0; c < C; ++c) DT<TO>::st(out_img + ((long long)b * C + c) * R3 + orow + x, 0.0f);
-            out_lab[(long long)b * R3 + orow + x] = 0.0f;
-        }
-        return;
-    }
-    int z0 = picks[8 * b + 3], y0 = picks[8 * b + 4], x0 = picks[8 * b + 5];
-    z0 = z0 < 0 ? 0 : (z0 > vd.D - R ? vd.D - R : z0);
-    y0 = y0 < 0 ? 0 : (y0 > vd.H - R ? vd.H - R : y0);
-    x0 = x0 < 0 ? 0 : (x0 > vd.W - R ? vd.W - R : x0);
-    // patch index of this output row: rot90^k and the flips undone as in aug_crop_multi_kernel
-    int sz = z, sy = y;
-    if (row.rotk == 1) { sz = y; sy = R - 1 - z; }
-    else if (row.rotk == 2) { sz = R - 1 - z; sy = R - 1 - y; }
-    else if (row.rotk == 3) { sz = R - 1 - y; sy = z; }
-    if (row.flips & 1) sz = R - 1 - sz;
-    if (row.flips & 2) sy = R - 1 - sy;
     const bool flipx = (row.flips & 4) != 0;
     const double* M = mats + 9 * (long long)b;
     const double h = (double)(R - 1) / 2.0;
@@ -379,8 +382,8 @@ int msseg_crop_pad_copy(const void* src, int elem_bytes, int C, int SD, int SH, 
     return MSSEG_OK;
 }
 
-int msseg_slab_counts_rule(const float* img0, const uint8_t* lab, int D, int H, int W, float threshold, int bg_rule, int* counts,
-                           msseg_stream_t stream) {
+int msseg_slab_counts(const float* img0, const uint8_t* lab, int D, int H, int W, float threshold, int bg_rule, int* counts,
+                      msseg_stream_t stream) {
     if (!img0 || !lab || !counts || D < 1 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL || bg_rule < 0 || bg_rule > 1)
         MSSEG_FAIL(MSSEG_EINVAL, "slab_counts: bad args");
     hipLaunchKernelGGL(slab_counts_kernel, dim3(D), dim3(256), 0, (hipStream_t)stream, img0, lab, H * W, threshold, bg_rule,
@@ -389,24 +392,14 @@ int msseg_slab_counts_rule(const float* img0, const uint8_t* lab, int D, int H, 
     return MSSEG_OK;
 }
 
-int msseg_slab_counts(const float* img0, const uint8_t* lab, int D, int H, int W, float threshold, int* counts,
+int msseg_pick_voxels(const void* volumes, int nvol, const void* rows, int nrows, int R, float threshold, int bg_rule, int* out,
                       msseg_stream_t stream) {
-    return msseg_slab_counts_rule(img0, lab, D, H, W, threshold, 0, counts, stream);
-}
-
-int msseg_pick_voxels_rule(const void* volumes, int nvol, const void* rows, int nrows, int R, float threshold, int bg_rule,
-                           int* out, msseg_stream_t stream) {
     if (!volumes || !rows || !out || nvol < 1 || nrows < 1 || R < 1 || bg_rule < 0 || bg_rule > 1)
         MSSEG_FAIL(MSSEG_EINVAL, "pick_voxels: bad args");
     hipLaunchKernelGGL(pick_voxels_kernel, dim3(nrows), dim3(256), 0, (hipStream_t)stream, (const VolDesc*)volumes, nvol,
                        (const PickRow*)rows, R, threshold, bg_rule, out);
     MSSEG_CHECK_LAUNCH("pick_voxels");
     return MSSEG_OK;
-}
-
-int msseg_pick_voxels(const void* volumes, int nvol, const void* rows, int nrows, int R, float threshold, int* out,
-                      msseg_stream_t stream) {
-    return msseg_pick_voxels_rule(volumes, nvol, rows, nrows, R, threshold, 0, out, stream);
 }
 
 int msseg_aug_crop_multi(const void* volumes, int nvol, const void* rows, const int* picks, int npatch, int C, void* out_img,

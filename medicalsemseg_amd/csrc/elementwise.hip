@@ -1625,19 +1625,19 @@ int msseg_conv3d_k1_head_fwd(const void* x, long long ldx, const float* w, const
     return MSSEG_OK;
 }
 
-static int head_bwd_impl(const void* dy, long long lddy, const float* w, void* da, long long ldda, int N, long long S,
-                         int C, int Cout, const void* yraw, long long ldyraw, const float* fwd_stats, const float* gamma,
-                         const float* beta, float slope, float eps, float* red, float* dgamma, float* dbeta, int accumulate,
-                         float* dw, int dw_accumulate, void* scratch, size_t scratch_bytes, int dtype,
-                         msseg_stream_t stream) {
+int msseg_conv3d_k1_head_bwd_fused(const void* dy, long long lddy, const float* w, void* da, long long ldda, int N,
+                                   long long S, int C, int Cout, const void* yraw, long long ldyraw, const float* fwd_stats,
+                                   const float* gamma, const float* beta, float slope, float eps, float* red, float* dgamma,
+                                   float* dbeta, int accumulate, float* dw, int dw_accumulate, void* scratch,
+                                   size_t scratch_bytes, int dtype, msseg_stream_t stream) {
     if (!dy || !w || (!da && !dw) || !yraw || !fwd_stats || !red || N < 1 || S < 1)   // da == NULL (with dw): da is not stored
-        MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k1_head_dgrad_inbwd: bad args");
-    if (dtype != MSSEG_F32 && dtype != MSSEG_BF16) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k1_head_dgrad_inbwd: bad dtype");
-    if (int rc = scratch_ok(scratch, scratch_bytes, "conv3d_k1_head_dgrad_inbwd")) return rc;
+        MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k1_head_bwd_fused: bad args");
+    if (dtype != MSSEG_F32 && dtype != MSSEG_BF16) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k1_head_bwd_fused: bad dtype");
+    if (int rc = scratch_ok(scratch, scratch_bytes, "conv3d_k1_head_bwd_fused")) return rc;
     const int esz = dtype == MSSEG_F32 ? 4 : 2, epc = 16 / esz;
     if (Cout < 1 || Cout > 4 || C < 1 || C > 64 || !vec_ok(yraw, ldyraw, C, esz) || (da && !vec_ok(da, ldda, C, esz)) ||
         (lddy % epc) || ((uintptr_t)dy & 15))
-        MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k1_head_dgrad_inbwd: needs <= 4 classes in 16-byte aligned gradient rows and "
+        MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k1_head_bwd_fused: needs <= 4 classes in 16-byte aligned gradient rows and "
                                  "16-byte channel chunks (C=%d, Cout=%d, lddy=%lld)", C, Cout, lddy);
     HeadBwdParams p{dy, lddy, w, yraw, ldyraw, fwd_stats, gamma, beta, da, ldda, S, C, Cout, eps, slope, 0, 0, 0, nullptr, 0};
     p.ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
@@ -1665,25 +1665,6 @@ static int head_bwd_impl(const void* dy, long long lddy, const float* w, void* d
     hipLaunchKernelGGL(head_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
     MSSEG_CHECK_LAUNCH("head_finalize");
     return MSSEG_OK;
-}
-
-int msseg_conv3d_k1_head_dgrad_inbwd(const void* dy, long long lddy, const float* w, void* da, long long ldda, int N,
-                                     long long S, int C, int Cout, const void* yraw, long long ldyraw,
-                                     const float* fwd_stats, const float* gamma, const float* beta, float slope, float eps,
-                                     float* red, float* dgamma, float* dbeta, int accumulate, void* scratch,
-                                     size_t scratch_bytes, int dtype, msseg_stream_t stream) {
-    return head_bwd_impl(dy, lddy, w, da, ldda, N, S, C, Cout, yraw, ldyraw, fwd_stats, gamma, beta, slope, eps, red, dgamma,
-                         dbeta, accumulate, nullptr, 0, scratch, scratch_bytes, dtype, stream);
-}
-
-int msseg_conv3d_k1_head_bwd_fused(const void* dy, long long lddy, const float* w, void* da, long long ldda, int N,
-                                   long long S, int C, int Cout, const void* yraw, long long ldyraw, const float* fwd_stats,
-                                   const float* gamma, const float* beta, float slope, float eps, float* red, float* dgamma,
-                                   float* dbeta, int accumulate, float* dw, int dw_accumulate, void* scratch,
-                                   size_t scratch_bytes, int dtype, msseg_stream_t stream) {
-    if (!dw) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k1_head_bwd_fused: dw is required");
-    return head_bwd_impl(dy, lddy, w, da, ldda, N, S, C, Cout, yraw, ldyraw, fwd_stats, gamma, beta, slope, eps, red, dgamma,
-                         dbeta, accumulate, dw, dw_accumulate, scratch, scratch_bytes, dtype, stream);
 }
 
 int msseg_conv3d_k1_head_norm_fwd(const void* x, long long ldx, const float* stats, const float* gamma, const float* beta,

@@ -634,31 +634,6 @@ int msseg_seg_loss_bwd(const void* logits, long long ld, int dtype, const void* 
                 smooth_dr, kind, alpha, beta, (hipStream_t)stream);
 }
 
-// the Dice + cross-entropy forms of the four entry points above
-int msseg_dice_ce_partials(const void* logits, long long ld, int dtype, const void* labels, int label_dtype,
-                           float* partial, float* hard, int N, long long S, int C, msseg_stream_t stream) {
-    return msseg_seg_loss_partials(logits, ld, dtype, labels, label_dtype, partial, hard, N, S, C, MSSEG_LOSS_DICE_CE, stream);
-}
-
-int msseg_dice_ce_fwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype, float* partial,
-                      float* hard, float* loss, int N, long long S, int C, float smooth_nr, float smooth_dr, void* scratch,
-                      size_t scratch_bytes, msseg_stream_t stream) {
-    return msseg_seg_loss_fwd(logits, ld, dtype, labels, label_dtype, partial, hard, loss, N, S, C, smooth_nr, smooth_dr,
-                              MSSEG_LOSS_DICE_CE, 0.f, 0.f, scratch, scratch_bytes, stream);
-}
-
-int msseg_dice_ce_finalize(const float* partial, float* loss, int N, long long S, int C, float smooth_nr,
-                           float smooth_dr, msseg_stream_t stream) {
-    return msseg_seg_loss_finalize(partial, loss, N, S, C, smooth_nr, smooth_dr, MSSEG_LOSS_DICE_CE, 0.f, 0.f, stream);
-}
-
-int msseg_dice_ce_bwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype,
-                      const float* partial, const float* gscale, void* dlogits, long long ldd, int N, long long S, int C,
-                      float smooth_nr, float smooth_dr, msseg_stream_t stream) {
-    return msseg_seg_loss_bwd(logits, ld, dtype, labels, label_dtype, partial, gscale, dlogits, ldd, N, S, C, smooth_nr,
-                              smooth_dr, MSSEG_LOSS_DICE_CE, 0.f, 0.f, stream);
-}
-
 int msseg_sw_normalize(float* out, const float* cnt, int C, long long V, msseg_stream_t stream) {
     if (!out || !cnt || C < 1 || V < 1) MSSEG_FAIL(MSSEG_EINVAL, "sw_normalize: bad args");
     hipLaunchKernelGGL(sw_normalize_kernel, dim3(stream_grid((long long)C * V, 1024)), dim3(256), 0, (hipStream_t)stream, out, cnt,
@@ -667,10 +642,9 @@ int msseg_sw_normalize(float* out, const float* cnt, int C, long long V, msseg_s
     return MSSEG_OK;
 }
 
-int msseg_sw_blend_batch_mirror(const void* win, long long ldw, int dtype, const float* imp, float* out,
-                                long long out_bstride, float* cnt, long long cnt_bstride, const int* table,
-                                const int* flips, int nwin, int C, int VD, int VH, int VW, int RD, int RH, int RW,
-                                msseg_stream_t stream) {
+int msseg_sw_blend_batch(const void* win, long long ldw, int dtype, const float* imp, float* out, long long out_bstride,
+                         float* cnt, long long cnt_bstride, const int* table, const int* flips, int nwin, int C, int VD,
+                         int VH, int VW, int RD, int RH, int RW, msseg_stream_t stream) {
     if (!win || !imp || !out || !cnt || !table) MSSEG_FAIL(MSSEG_EINVAL, "sw_blend_batch: null pointer");
     if (nwin < 1 || nwin > 256) MSSEG_FAIL(MSSEG_EINVAL, "sw_blend_batch: 1 <= nwin <= 256 windows per launch (got %d)", nwin);
     if (C < 1 || C > 16) MSSEG_FAIL(MSSEG_EINVAL, "sw_blend_batch: 1 <= C <= 16 classes");
@@ -680,16 +654,9 @@ int msseg_sw_blend_batch_mirror(const void* win, long long ldw, int dtype, const
                 VD, VH, VW, RD, RH, RW, (hipStream_t)stream);
 }
 
-int msseg_sw_blend_batch(const void* win, long long ldw, int dtype, const float* imp, float* out, long long out_bstride,
-                         float* cnt, long long cnt_bstride, const int* table, int nwin, int C, int VD, int VH, int VW,
-                         int RD, int RH, int RW, msseg_stream_t stream) {
-    return msseg_sw_blend_batch_mirror(win, ldw, dtype, imp, out, out_bstride, cnt, cnt_bstride, table, nullptr, nwin, C,
-                                       VD, VH, VW, RD, RH, RW, stream);
-}
-
-int msseg_sw_gather_batch_mirror(const float* vol, long long vol_bstride, void* win, long long ldw, int dtype,
-                                 const int* table, const int* flips, int nwin, int C, int VD, int VH, int VW, int RD,
-                                 int RH, int RW, float cval, msseg_stream_t stream) {
+int msseg_sw_gather_batch(const float* vol, long long vol_bstride, void* win, long long ldw, int dtype, const int* table,
+                          const int* flips, int nwin, int C, int VD, int VH, int VW, int RD, int RH, int RW, float cval,
+                          msseg_stream_t stream) {
     if (!vol || !win || !table) MSSEG_FAIL(MSSEG_EINVAL, "sw_gather_batch: null pointer");
     if (nwin < 1 || nwin > 65535 || C < 1) MSSEG_FAIL(MSSEG_EINVAL, "sw_gather_batch: bad window / channel count");
     if (ldw != 0 && ldw < C) MSSEG_FAIL(MSSEG_EINVAL, "sw_gather_batch: ldw smaller than the channel count");
@@ -704,13 +671,6 @@ int msseg_sw_gather_batch_mirror(const float* vol, long long vol_bstride, void* 
     if (!known) MSSEG_FAIL(MSSEG_EINVAL, "sw_gather_batch: bad dtype");
     MSSEG_CHECK_LAUNCH("sw_gather_batch");
     return MSSEG_OK;
-}
-
-int msseg_sw_gather_batch(const float* vol, long long vol_bstride, void* win, long long ldw, int dtype, const int* table,
-                          int nwin, int C, int VD, int VH, int VW, int RD, int RH, int RW, float cval,
-                          msseg_stream_t stream) {
-    return msseg_sw_gather_batch_mirror(vol, vol_bstride, win, ldw, dtype, table, nullptr, nwin, C, VD, VH, VW, RD, RH,
-                                        RW, cval, stream);
 }
 
 }  // extern "C"

@@ -11,7 +11,7 @@ normalise are HIP kernels (``msseg_sw_gather_batch/_blend_batch/_normalize``); t
 all-gather, after which every rank blends the step's windows in the reference order (bit-identical to the single-GPU
 result).  An addition of this build: ``mirror_axes`` (``--infer_mirror_axes``) predicts every window under each flip
 combination of the given axes and blends the un-mirrored logits of all of them -- the flips are index changes inside the
-gather and blend kernels (``msseg_sw_gather_batch_mirror/_blend_batch_mirror``), nothing else in the loop changes.
+gather and blend kernels (the ``flips`` table of ``msseg_sw_gather_batch/_blend_batch``), nothing else in the loop changes.
 """
 from __future__ import annotations
 

@@ -83,11 +83,8 @@ SIGNATURES = {
     "msseg_linear_gelu_bwd": ([_vp, _ll, _vp, _vp, _ll, _vp, _ll, _ll, _i, _i, _i, _vp], _i),
     "msseg_linear_add_ok": ([_ll, _i, _i, _i], _i),
     "msseg_linear_add_fwd": ([_vp, _ll, _vp, _vp, _vp, _ll, _vp, _ll, _ll, _i, _i, _i, _vp], _i),
-    "msseg_conv3d_stem_fwd": ([_vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _vp, _vp, _sz, _i, _vp], _i),
-    "msseg_conv3d_stem_k1_fwd": ([_vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _vp, _vp, _sz, _i, _vp], _i),
+    "msseg_conv3d_stem_fwd": ([_vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _i, _vp], _i),
     "msseg_conv3d_stem_norm_fwd": ([_vp, _ll, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "msseg_conv3d_k1_head_dgrad_inbwd": ([_vp, _ll, _vp, _vp, _ll, _i, _ll, _i, _i, _vp, _ll, _vp, _vp, _vp, _f, _f, _vp, _vp,
-                                          _vp, _i, _vp, _sz, _i, _vp], _i),
     "msseg_conv3d_k1_head_norm_fwd": ([_vp, _ll, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _ll, _i, _ll, _i, _i, _i, _vp], _i),
     "msseg_conv3d_k1_head_bwd_fused": ([_vp, _ll, _vp, _vp, _ll, _i, _ll, _i, _i, _vp, _ll, _vp, _vp, _vp, _f, _f, _vp, _vp,
                                         _vp, _i, _vp, _i, _vp, _sz, _i, _vp], _i),
@@ -121,10 +118,6 @@ SIGNATURES = {
     "msseg_channel_sum": ([_vp, _ll, _vp, _ll, _i, _i, _vp, _sz, _i, _vp], _i),
     "msseg_axpy_rows": ([_vp, _vp, _vp, _vp, _i, _ll, _i, _vp], _i),
     "msseg_add": ([_vp, _ll, _vp, _ll, _vp, _ll, _ll, _i, _i, _vp], _i),
-    "msseg_dice_ce_partials": ([_vp, _ll, _i, _vp, _i, _vp, _vp, _i, _ll, _i, _vp], _i),
-    "msseg_dice_ce_fwd": ([_vp, _ll, _i, _vp, _i, _vp, _vp, _vp, _i, _ll, _i, _f, _f, _vp, _sz, _vp], _i),
-    "msseg_dice_ce_finalize": ([_vp, _vp, _i, _ll, _i, _f, _f, _vp], _i),
-    "msseg_dice_ce_bwd": ([_vp, _ll, _i, _vp, _i, _vp, _vp, _vp, _ll, _i, _ll, _i, _f, _f, _vp], _i),
     "msseg_seg_loss_partials": ([_vp, _ll, _i, _vp, _i, _vp, _vp, _i, _ll, _i, _i, _vp], _i),
     "msseg_seg_loss_fwd": ([_vp, _ll, _i, _vp, _i, _vp, _vp, _vp, _i, _ll, _i, _f, _f, _i, _f, _f, _vp, _sz, _vp], _i),
     "msseg_seg_loss_finalize": ([_vp, _vp, _i, _ll, _i, _f, _f, _i, _f, _f, _vp], _i),
@@ -142,10 +135,8 @@ SIGNATURES = {
     "msseg_intensity_prep": ([_vp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _f, _f, _vp, _vp, _vp], _i),
     "msseg_resample_spacing": ([_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp], _i),
     "msseg_crop_pad_copy": ([_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _f, _i, _vp], _i),
-    "msseg_slab_counts": ([_vp, _vp, _i, _i, _i, _f, _vp, _vp], _i),
-    "msseg_pick_voxels": ([_vp, _i, _vp, _i, _i, _f, _vp, _vp], _i),
-    "msseg_slab_counts_rule": ([_vp, _vp, _i, _i, _i, _f, _i, _vp, _vp], _i),
-    "msseg_pick_voxels_rule": ([_vp, _i, _vp, _i, _i, _f, _i, _vp, _vp], _i),
+    "msseg_slab_counts": ([_vp, _vp, _i, _i, _i, _f, _i, _vp, _vp], _i),
+    "msseg_pick_voxels": ([_vp, _i, _vp, _i, _i, _f, _i, _vp, _vp], _i),
     "msseg_class_candidate_mask": ([_vp, _vp, _i, _i, _i, _f, _i, C.c_uint, _i, _vp, _vp, _vp], _i),
     "msseg_class_slab_counts": ([_vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp], _i),
     "msseg_class_pick_voxels": ([_vp, _vp, _i, _vp, _i, _i, _f, _i, _vp, _vp], _i),
@@ -158,10 +149,8 @@ SIGNATURES = {
     "msseg_intensity_aug_workspace_bytes": ([_i, _i, _i, _i, _i], _sz),
     "msseg_intensity_aug": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp], _i),
     "msseg_intensity_noise_bits": ([C.c_uint, C.c_uint, _ll, _ll, _vp, _vp], _i),
-    "msseg_sw_gather_batch": ([_vp, _ll, _vp, _ll, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp], _i),
-    "msseg_sw_blend_batch": ([_vp, _ll, _i, _vp, _vp, _ll, _vp, _ll, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "msseg_sw_gather_batch_mirror": ([_vp, _ll, _vp, _ll, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp], _i),
-    "msseg_sw_blend_batch_mirror": ([_vp, _ll, _i, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "msseg_sw_gather_batch": ([_vp, _ll, _vp, _ll, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp], _i),
+    "msseg_sw_blend_batch": ([_vp, _ll, _i, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "msseg_deconv_k2s2_bwd_partials_ok": ([_i, _i, _i], _i),
     "msseg_deconv_k2s2_bwd_partials": ([_vp, _ll, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "msseg_conv3d_k3_small_ok": ([_i, _i, _i, _i, _i, _i, _i], _i),
@@ -205,7 +194,7 @@ def load_library(path: Optional[str] = None):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res
-    if lib.msseg_abi_version() != 2:
+    if lib.msseg_abi_version() != 3:
         raise RuntimeError("libmsseg_hip.so ABI version mismatch")
     _lib = lib
     return lib
@@ -669,22 +658,6 @@ def conv3d_k1_head(x, w, bias, y, cin, cout):
     return y
 
 
-def conv3d_k1_head_dgrad_inbwd(dy, w, da, cin, cout, yraw, fwd_stats, gamma, beta, slope, eps, dgamma=None, dbeta=None,
-                               accumulate=False):
-    """da = dy . w for a head with `cout` <= 4 classes (w fp32 [cout, cin]) and the InstanceNorm-backward sums of the layer
-    (yraw, fwd_stats, gamma, beta) that receives da.  Returns red[N][cin][2]."""
-    _need_gpu(dy, w, da, yraw, fwd_stats)
-    N = dy.shape[0]
-    S = dy.numel() // dy.shape[-1] // N
-    red = torch.empty(N, cin, 2, dtype=torch.float32, device=dy.device)
-    sc = scratch(dy.device)
-    _ck(lib().msseg_conv3d_k1_head_dgrad_inbwd(_p(dy), ld(dy), _p(w), _p(da), ld(da), N, S, cin, cout, _p(yraw), ld(yraw),
-                                               _p(fwd_stats), _p(gamma), _p(beta), slope, eps, _p(red), _p(dgamma),
-                                               _p(dbeta), int(accumulate), _p(sc), sc.numel(), dt(dy), _stream()),
-        "conv3d_k1_head_dgrad_inbwd")
-    return red
-
-
 def conv3d_k1_head_norm(yraw, stats, gamma, beta, slope, eps, w, bias, y, cin, cout):
     """y = conv1x1(lrelu(instance_norm(yraw))) for a head with <= 4 classes, normalisation applied on load"""
     _need_gpu(yraw, stats, w, y)
@@ -695,10 +668,13 @@ def conv3d_k1_head_norm(yraw, stats, gamma, beta, slope, eps, w, bias, y, cin, c
     return y
 
 
-def conv3d_k1_head_bwd_fused(dy, w, da, cin, cout, yraw, fwd_stats, gamma, beta, slope, eps, dw, dw_accumulate,
+def conv3d_k1_head_bwd_fused(dy, w, da, cin, cout, yraw, fwd_stats, gamma, beta, slope, eps, dw=None, dw_accumulate=False,
                              dgamma=None, dbeta=None, accumulate=False):
-    """conv3d_k1_head_dgrad_inbwd + the head's weight gradient dw[cout][cin] from the recomputed activation.
-    da None: the input gradient is not stored (the sums and dw are the same bits); instnorm_act_bwd_apply_head forms it again"""
+    """da = dy . w for a head with `cout` <= 4 classes (w fp32 [cout, cin]) and the InstanceNorm-backward sums of the layer
+    (yraw, fwd_stats, gamma, beta) that receives da; with dw also the head's weight gradient dw[cout][cin] from the
+    recomputed activation.  Returns red[N][cin][2].
+    da None (dw given): the input gradient is not stored (the sums and dw are the same bits); instnorm_act_bwd_apply_head
+    forms it again"""
     _need_gpu(dy, w, da, yraw, fwd_stats, dw)
     N = dy.shape[0]
     S = dy.numel() // dy.shape[-1] // N
@@ -779,9 +755,9 @@ def conv3d_stem(x, wp, bias, y, cout, stats=None, k=3):
     _need_gpu(x, wp)
     N, D, H, W = x.shape[:4]
     sc = scratch(x.device) if stats is not None else None
-    fn = lib().msseg_conv3d_stem_fwd if k == 3 else lib().msseg_conv3d_stem_k1_fwd
-    _ck(fn(_p(x), ld(x), _p(wp), _p(bias), _p(y), ld(y) if y is not None else 0, N, D, H, W, cout, _p(stats), _p(sc),
-                                    sc.numel() if sc is not None else 0, dt(x), _stream()), "conv3d_stem_fwd")
+    _ck(lib().msseg_conv3d_stem_fwd(_p(x), ld(x), _p(wp), _p(bias), _p(y), ld(y) if y is not None else 0, N, D, H, W, cout,
+                                    int(k), _p(stats), _p(sc), sc.numel() if sc is not None else 0, dt(x), _stream()),
+        "conv3d_stem_fwd")
     return y
 
 
@@ -1267,12 +1243,13 @@ def add(a, b, y):
 # --------------------------------------------------------------------------------------------
 # loss / metric
 # --------------------------------------------------------------------------------------------
-# loss kinds of the seg_loss_* passes (MSSEG_LOSS_* of include/msseg.h); msseg_dice_ce_* are kind LOSS_DICE_CE
+# loss kinds of the seg_loss_* passes (MSSEG_LOSS_* of include/msseg.h)
 LOSS_DICE_CE, LOSS_TVERSKY, LOSS_DICE_FOCAL = 0, 1, 2
 
 
 def seg_loss_partials(logits, labels, n_cls, kind, channels_last_ld=0, want_hard=False):
-    """atomic partial sums (any N) for a loss kind: slot 1 / slot 3 of partial hold (sum p^2, CE sum) | (sum p, 0) | (sum p^2, focal sum)"""
+    """atomic partial sums (any N) for a loss kind: slot 1 / slot 3 of partial hold (sum p^2, CE sum) | (sum p, 0) | (sum p^2, focal sum).
+    logits: NCDHW (channels_last_ld == 0) or channels-last with voxel stride ld.  Returns (partial, hard)."""
     _need_gpu(logits, labels)
     N = logits.shape[0]
     S = labels.numel() // N
@@ -1281,11 +1258,6 @@ def seg_loss_partials(logits, labels, n_cls, kind, channels_last_ld=0, want_hard
     _ck(lib().msseg_seg_loss_partials(_p(logits), channels_last_ld, dt(logits), _p(labels), _LAB[labels.dtype],
                                       _p(partial), _p(hard), N, S, n_cls, kind, _stream()), "seg_loss_partials")
     return partial, hard
-
-
-def dice_ce_partials(logits, labels, n_cls, channels_last_ld=0, want_hard=False):
-    """logits: NCDHW (channels_last_ld == 0) or channels-last with voxel stride ld.  Returns (partial, hard)."""
-    return seg_loss_partials(logits, labels, n_cls, LOSS_DICE_CE, channels_last_ld, want_hard)
 
 
 def seg_loss_fwd(logits, labels, n_cls, smooth_nr, smooth_dr, kind, alpha=0.0, beta=0.0, channels_last_ld=0, want_hard=True):
@@ -1373,13 +1345,8 @@ def sw_gather_batch(vol, win, table, nwin, cval=0.0, channels_last_ld=0, flips=N
     Cc = vol.shape[1]
     VD, VH, VW = vol.shape[2:]
     RD, RH, RW = win.shape[2:] if channels_last_ld == 0 else win.shape[1:4]
-    if flips is None:
-        _ck(lib().msseg_sw_gather_batch(_p(vol), vol.stride(0), _p(win), channels_last_ld, dt(win), _p(table), nwin, Cc, VD,
-                                        VH, VW, RD, RH, RW, float(cval), _stream()), "sw_gather_batch")
-    else:
-        _ck(lib().msseg_sw_gather_batch_mirror(_p(vol), vol.stride(0), _p(win), channels_last_ld, dt(win), _p(table),
-                                               _p(flips), nwin, Cc, VD, VH, VW, RD, RH, RW, float(cval), _stream()),
-            "sw_gather_batch_mirror")
+    _ck(lib().msseg_sw_gather_batch(_p(vol), vol.stride(0), _p(win), channels_last_ld, dt(win), _p(table), _p(flips), nwin,
+                                    Cc, VD, VH, VW, RD, RH, RW, float(cval), _stream()), "sw_gather_batch")
     return win
 
 
@@ -1393,14 +1360,9 @@ def sw_blend_batch(win, imp, out, cnt, table, nwin, channels_last_ld=0, flips=No
     Cc = out.shape[1]
     VD, VH, VW = out.shape[2:]
     RD, RH, RW = imp.shape
-    if flips is None:
-        _ck(lib().msseg_sw_blend_batch(_p(win), channels_last_ld, dt(win), _p(imp), _p(out), out.stride(0), _p(cnt),
-                                       cnt.stride(0), _p(table), nwin, Cc, VD, VH, VW, RD, RH, RW, _stream()),
-            "sw_blend_batch")
-    else:
-        _ck(lib().msseg_sw_blend_batch_mirror(_p(win), channels_last_ld, dt(win), _p(imp), _p(out), out.stride(0), _p(cnt),
-                                              cnt.stride(0), _p(table), _p(flips), nwin, Cc, VD, VH, VW, RD, RH, RW,
-                                              _stream()), "sw_blend_batch_mirror")
+    _ck(lib().msseg_sw_blend_batch(_p(win), channels_last_ld, dt(win), _p(imp), _p(out), out.stride(0), _p(cnt),
+                                   cnt.stride(0), _p(table), _p(flips), nwin, Cc, VD, VH, VW, RD, RH, RW, _stream()),
+        "sw_blend_batch")
 
 
 # --------------------------------------------------------------------------------------------
@@ -1662,15 +1624,25 @@ def _bg_rule(rule):
     return BG_RULES[rule]
 
 
+def _check_volume(img, lab):
+    _need_gpu(img, lab)
+    assert img.dtype == torch.float32 and lab.dtype == torch.uint8 and img.is_contiguous() and lab.is_contiguous()
+    assert img.dim() == 4 and lab.dim() == 3 and img.shape[1:] == lab.shape
+
+
+def _check_pick_tables(volumes, nvol, rows, nrows, out):
+    """the device tables of the pick calls: nvol msseg_volume_desc, nrows msseg_pick_row, int32 out [nrows, 8]"""
+    assert volumes.numel() >= nvol * 32 and rows.numel() >= nrows * 32 and out.dtype == torch.int32
+    assert out.is_contiguous() and out.numel() >= nrows * 8
+
+
 def slab_counts(img, lab, threshold=0.0, rule="gt"):
     """img fp32 [C, D, H, W] (channel 0 is read), lab uint8 [D, H, W] -> int32 [D, 2] on the device:
     per z-slice #(lab > 0), #(lab == 0 and img[0] > threshold); rule "ne": img[0] != threshold, the non-zero mask of a
     z-scored cache"""
-    _need_gpu(img, lab)
-    assert img.dtype == torch.float32 and lab.dtype == torch.uint8 and img.is_contiguous() and lab.is_contiguous()
-    assert img.dim() == 4 and lab.dim() == 3 and img.shape[1:] == lab.shape
+    _check_volume(img, lab)
     out = torch.empty(lab.shape[0], 2, dtype=torch.int32, device=lab.device)
-    _ck(lib().msseg_slab_counts_rule(_p(img), _p(lab), *lab.shape, float(threshold), _bg_rule(rule), _p(out), _stream()),
+    _ck(lib().msseg_slab_counts(_p(img), _p(lab), *lab.shape, float(threshold), _bg_rule(rule), _p(out), _stream()),
         "slab_counts")
     return out
 
@@ -1679,10 +1651,9 @@ def pick_voxels(volumes, nvol, rows, nrows, roi, threshold, out, rule="gt"):
     """volumes: uint8 device tensor of nvol msseg_volume_desc; rows: uint8 device tensor of nrows msseg_pick_row;
     out: int32 [nrows, 8] on the device; rule as slab_counts"""
     _need_gpu(volumes, rows, out)
-    assert volumes.numel() >= nvol * 32 and rows.numel() >= nrows * 32 and out.dtype == torch.int32
-    assert out.is_contiguous() and out.numel() >= nrows * 8
-    _ck(lib().msseg_pick_voxels_rule(_p(volumes), nvol, _p(rows), nrows, int(roi), float(threshold), _bg_rule(rule), _p(out),
-                                     _stream()), "pick_voxels")
+    _check_pick_tables(volumes, nvol, rows, nrows, out)
+    _ck(lib().msseg_pick_voxels(_p(volumes), nvol, _p(rows), nrows, int(roi), float(threshold), _bg_rule(rule), _p(out),
+                                _stream()), "pick_voxels")
     return out
 
 
@@ -1690,12 +1661,6 @@ def pick_voxels(volumes, nvol, rows, nrows, roi, threshold, out, rule="gt"):
 PICK_CLASS0 = 16            # MSSEG_PICK_CLASS0: a pick row of class c carries mode PICK_CLASS0 + c
 MAX_CROP_CLASSES = 16
 MAX_CENTER_DILATION = 254
-
-
-def _check_volume(img, lab):
-    _need_gpu(img, lab)
-    assert img.dtype == torch.float32 and lab.dtype == torch.uint8 and img.is_contiguous() and lab.is_contiguous()
-    assert img.dim() == 4 and lab.dim() == 3 and img.shape[1:] == lab.shape
 
 
 def class_candidate_mask(img, lab, classes, dilation, threshold=0.0, rule="gt"):
@@ -1739,8 +1704,7 @@ def class_pick_voxels(volumes, nvol, rows, nrows, roi, threshold, out, rule="gt"
     None, or an int64 device tensor of nvol pointers to the volumes' candidate masks (0: that volume has none; its class
     rows then read the label)"""
     _need_gpu(volumes, rows, out, masks)
-    assert volumes.numel() >= nvol * 32 and rows.numel() >= nrows * 32 and out.dtype == torch.int32
-    assert out.is_contiguous() and out.numel() >= nrows * 8
+    _check_pick_tables(volumes, nvol, rows, nrows, out)
     if masks is not None:
         assert masks.dtype == torch.int64 and masks.is_contiguous() and masks.numel() >= nvol
     _ck(lib().msseg_class_pick_voxels(_p(volumes), _p(masks), nvol, _p(rows), nrows, int(roi), float(threshold),
@@ -1819,16 +1783,22 @@ def zscore_nonzero_(img, clip=None):
     return stats
 
 
+def _check_crop_tables(volumes, nvol, rows, picks, out_img, out_lab, roi):
+    """the device tables and outputs of the crop gathers; -> the number of patches"""
+    npatch = out_img.shape[0]
+    assert volumes.numel() >= nvol * 32 and rows.numel() >= npatch * 32 and picks.numel() >= npatch * 8
+    assert picks.dtype == torch.int32 and picks.is_contiguous() and out_img.is_contiguous() and out_lab.is_contiguous()
+    assert out_lab.dtype == torch.float32 and out_lab.numel() == npatch * roi ** 3 and tuple(out_img.shape[2:]) == (roi,) * 3
+    return npatch
+
+
 def aug_crop_multi(volumes, nvol, rows, picks, out_img, out_lab, roi):
     """one gather launch for a batch over many cached volumes; out_img [n, C, R, R, R] fp32 / bf16, out_lab fp32 [n, 1, R, R, R].
     The descriptor and row tables are device memory: the caller guarantees that every row names one of the nvol volumes,
     that it has out_img's channel count and holds an roi^3 patch (DeviceDatasetLoader checks this at construction); a row
     that does not comes back as an all-zero patch."""
     _need_gpu(volumes, rows, picks, out_img, out_lab)
-    npatch = out_img.shape[0]
-    assert volumes.numel() >= nvol * 32 and rows.numel() >= npatch * 32 and picks.numel() >= npatch * 8
-    assert picks.dtype == torch.int32 and picks.is_contiguous() and out_img.is_contiguous() and out_lab.is_contiguous()
-    assert out_lab.dtype == torch.float32 and out_lab.numel() == npatch * roi ** 3 and tuple(out_img.shape[2:]) == (roi,) * 3
+    npatch = _check_crop_tables(volumes, nvol, rows, picks, out_img, out_lab, roi)
     _ck(lib().msseg_aug_crop_multi(_p(volumes), nvol, _p(rows), _p(picks), npatch, out_img.shape[1], _p(out_img), dt(out_img),
                                    _p(out_lab), int(roi), _stream()), "aug_crop_multi")
     return out_img, out_lab
@@ -1840,11 +1810,8 @@ def aug_crop_affine(volumes, nvol, rows, picks, mats, out_img, out_lab, roi, pad
     volume reading pad_value, label nearest with 0 outside.  Identity matrices give aug_crop_multi's output bit for bit.
     Tables and preconditions as aug_crop_multi."""
     _need_gpu(volumes, rows, picks, mats, out_img, out_lab)
-    npatch = out_img.shape[0]
-    assert volumes.numel() >= nvol * 32 and rows.numel() >= npatch * 32 and picks.numel() >= npatch * 8
-    assert picks.dtype == torch.int32 and picks.is_contiguous() and out_img.is_contiguous() and out_lab.is_contiguous()
+    npatch = _check_crop_tables(volumes, nvol, rows, picks, out_img, out_lab, roi)
     assert mats.dtype == torch.float64 and mats.is_contiguous() and mats.numel() == npatch * 9
-    assert out_lab.dtype == torch.float32 and out_lab.numel() == npatch * roi ** 3 and tuple(out_img.shape[2:]) == (roi,) * 3
     _ck(lib().msseg_aug_crop_affine(_p(volumes), nvol, _p(rows), _p(picks), _p(mats), npatch, out_img.shape[1], _p(out_img),
                                     dt(out_img), _p(out_lab), int(roi), float(pad_value), _stream()), "aug_crop_affine")
     return out_img, out_lab

@@ -435,8 +435,8 @@ class Conv1:
             red = hip.conv3d_k1_head_bwd_fused(dyk, self.w.detach(), dx, self.cin, self.cout, yraw, stats, nrm.gamma, nrm.beta,
                                                nrm.slope, nrm.eps, gw, wacc, dg, db, acc)
         else:
-            red = hip.conv3d_k1_head_dgrad_inbwd(dyk, self.w.detach(), dx, self.cin, self.cout, yraw, stats, nrm.gamma,
-                                                 nrm.beta, nrm.slope, nrm.eps, dg, db, acc)
+            red = hip.conv3d_k1_head_bwd_fused(dyk, self.w.detach(), dx, self.cin, self.cout, yraw, stats, nrm.gamma, nrm.beta,
+                                               nrm.slope, nrm.eps, dgamma=dg, dbeta=db, accumulate=acc)
         return (HeadGrad(dyk, self.w.detach(), self.cout) if defer else dx), red
 
     def bwd(self, x, dy, need_dx=True, dy_channels=None, next_norm=None):
@@ -472,8 +472,8 @@ class Conv1:
             # segmentation head: streaming kernel on the fp32 weight, with the receiving layer's backward sums
             nrm, yraw, stats, act = next_norm
             dg, db, acc = _norm_grad_bufs(nrm)
-            red = hip.conv3d_k1_head_dgrad_inbwd(dyk, self.w.detach(), dx, self.cin, self.cout, yraw, stats, nrm.gamma,
-                                                 nrm.beta, nrm.slope, nrm.eps, dg, db, acc)
+            red = hip.conv3d_k1_head_bwd_fused(dyk, self.w.detach(), dx, self.cin, self.cout, yraw, stats, nrm.gamma, nrm.beta,
+                                               nrm.slope, nrm.eps, dgamma=dg, dbeta=db, accumulate=acc)
             return dx, red
         wp = self.cache.get(self.w, dtype, "d",
                             lambda: hip.pack_conv_k1(self.w.detach().reshape(self.cout, self.cin), dtype, dgrad=True))

@@ -195,5 +195,5 @@ def dice_metric(logits: torch.Tensor, labels: torch.Tensor):
     ld = _channels_last_rows(logits)
     if ld == 0 or logits.data_ptr() % 16 or (ld * logits.element_size()) % 16:
         ld, logits = 0, logits.contiguous()
-    _, hard = hip.dice_ce_partials(logits, labels, logits.shape[1], ld, want_hard=True)
+    _, hard = hip.seg_loss_partials(logits, labels, logits.shape[1], hip.LOSS_DICE_CE, ld, want_hard=True)
     return dice_from_counts(hard)

@@ -114,7 +114,7 @@ def test_sixteen_classes():
 @pytest.mark.parametrize("rule", ["gt", "ne"])
 def test_class_zero_of_two_classes_is_the_background_pick_and_old_modes_pass_through(rule):
     """K = 2: lab == 0 with the image rule is the background candidate set, so class-0 rows give the rows PICK_BG gives,
-    bit for bit; rows of mode 0 / 1 / 2 through the new entry point equal msseg_pick_voxels_rule"""
+    bit for bit; rows of mode 0 / 1 / 2 through the new entry point equal msseg_pick_voxels"""
     from medicalsemseg_amd import hip
     from medicalsemseg_amd.data_device import PICK_BG, PICK_FG, PICK_VOXEL, PickRow, _upload
     dev = _dev()

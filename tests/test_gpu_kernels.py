@@ -168,6 +168,11 @@ def test_conv3d_gather(dtype, cin, cout, k, s, p, sp):
         yf = y.float().reshape(N, -1, cout)
         ref = torch.stack([yf.sum(1), (yf * yf).sum(1)], dim=-1)
         assert float((stats - ref).abs().max()) / float(ref.abs().max()) < 1e-5
+        # any k but 1 and 3 is refused before a launch: the outputs keep their bits
+        y2c, sc = y2.clone(), stats.clone()
+        with pytest.raises(hip.MssegError, match=r"conv3d_stem: k = 1 .* or 3, got 2"):
+            hip.conv3d_stem(xg, wp, b.to(dev), y2, cout, stats, k=2)
+        assert torch.equal(y2, y2c) and torch.equal(stats, sc)
 
 
 @pytest.mark.parametrize("cout,sp,N", [(32, (16, 16, 16), 2), (64, (10, 13, 21), 3), (32, (33, 20, 48), 2),
@@ -896,8 +901,8 @@ def test_conv3d_k1_head_dgrad_inbwd(dtype, cin, cout):
     stats = hip.channel_stats(yc)
     dx = torch.empty_like(yc)
     dg, db = torch.zeros(cin, device=DEV), torch.zeros(cin, device=DEV)
-    red = hip.conv3d_k1_head_dgrad_inbwd(dlc, w.to(DEV), dx, cin, cout, yc, stats, gamma.to(DEV), beta.to(DEV), 0.1, 1e-5,
-                                         dg, db, False)
+    red = hip.conv3d_k1_head_bwd_fused(dlc, w.to(DEV), dx, cin, cout, yc, stats, gamma.to(DEV), beta.to(DEV), 0.1, 1e-5,
+                                       dgamma=dg, dbeta=db, accumulate=False)
     check(ncdhw(dx), da, dtype, "head dgrad")
     tol = 2e-4 if dtype == torch.float32 else 3e-2
     sc = float(red_ref.abs().max())
@@ -936,7 +941,8 @@ def test_conv3d_k1_head_norm_fused_fwd_bwd(dtype, cin, cout, affine):
     dx0, dx1 = torch.empty_like(yc), torch.empty_like(yc)
     dg0, db0 = (torch.zeros(cin, device=DEV), torch.zeros(cin, device=DEV)) if affine else (None, None)
     dg1, db1 = (torch.zeros(cin, device=DEV), torch.zeros(cin, device=DEV)) if affine else (None, None)
-    red0 = hip.conv3d_k1_head_dgrad_inbwd(dlc, w, dx0, cin, cout, yc, stats, gamma, beta, 0.1, 1e-5, dg0, db0, False)
+    red0 = hip.conv3d_k1_head_bwd_fused(dlc, w, dx0, cin, cout, yc, stats, gamma, beta, 0.1, 1e-5, dgamma=dg0, dbeta=db0,
+                                        accumulate=False)
     dw = torch.full((cout, cin), 0.25, device=DEV)
     red1 = hip.conv3d_k1_head_bwd_fused(dlc, w, dx1, cin, cout, yc, stats, gamma, beta, 0.1, 1e-5, dw, True, dg1, db1, False)
     if dtype == torch.bfloat16:

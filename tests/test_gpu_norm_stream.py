@@ -165,8 +165,8 @@ def test_conv3d_k1_head_dgrad_inbwd_small(dtype):
     stats = hip.channel_stats(yc)
     dx = Guarded(N, sp, cin, "first", dtype, DEV)
     dg, db = torch.zeros(cin, device=DEV), torch.zeros(cin, device=DEV)
-    red = hip.conv3d_k1_head_dgrad_inbwd(dlc, w.to(DEV), dx.t, cin, cout, yc, stats, gamma.to(DEV), beta.to(DEV), 0.1, 1e-5,
-                                         dg, db, False)
+    red = hip.conv3d_k1_head_bwd_fused(dlc, w.to(DEV), dx.t, cin, cout, yc, stats, gamma.to(DEV), beta.to(DEV), 0.1, 1e-5,
+                                       dgamma=dg, dbeta=db, accumulate=False)
     dx.assert_exact("head dgrad")
     assert torch.equal(dlc, dlc_before)
     check(ncdhw(dx.t), da, dtype, "head dgrad")

@@ -1,5 +1,5 @@
-"""GPU tests of mirror test-time augmentation inside the sliding-window kernels (msseg_sw_gather_batch_mirror /
-msseg_sw_blend_batch_mirror, sliding_window_inference(..., mirror_axes=...), --infer_mirror_axes).  The kernels are compared
+"""GPU tests of mirror test-time augmentation inside the sliding-window kernels (the flips table of
+msseg_sw_gather_batch / msseg_sw_blend_batch, sliding_window_inference(..., mirror_axes=...), --infer_mirror_axes).  The kernels are compared
 bit for bit with compositions of the un-mirrored kernels and torch.flip, the whole function with the CPU restatement
 tests/sw_mirror_ref.py."""
 import os
@@ -56,9 +56,9 @@ def test_gather_mirror_is_flip_of_plain_gather(roi, layout):
         zero = hip.sw_gather_batch(vol.to(DEV), new(), table, 8, cval=-3.0, flips=torch.zeros_like(fl), **kw)
         assert torch.equal(zero, plain)
         null = new()
-        rc = hip.lib().msseg_sw_gather_batch_mirror(vol.to(DEV).data_ptr(), vol.stride(0), null.data_ptr(),
-                                                    kw.get("channels_last_ld", 0), hip.dt(null), table.data_ptr(), None, 8,
-                                                    2, *vol.shape[2:], *roi, -3.0, None)
+        rc = hip.lib().msseg_sw_gather_batch(vol.to(DEV).data_ptr(), vol.stride(0), null.data_ptr(),
+                                             kw.get("channels_last_ld", 0), hip.dt(null), table.data_ptr(), None, 8, 2,
+                                             *vol.shape[2:], *roi, -3.0, None)
         torch.cuda.synchronize()
         assert rc == 0 and torch.equal(null, plain)
 

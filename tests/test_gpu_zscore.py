@@ -205,25 +205,25 @@ def test_pick_rule_ne_counts_and_picks_the_nonzero_mask():
     assert (out[:, 7] >= 0).all() and np.array_equal(flat, lst[idxs])
     assert (lab.reshape(-1)[flat] == 0).all() and (img[0].reshape(-1)[flat] != 0).all()
     assert (img[0].reshape(-1)[flat] < 0).any()                                              # picks "gt" cannot make
-    # rule "gt" through the new entry points == the old entry points
-    L = hip.lib()
-    old_c = torch.empty(shape[0], 2, dtype=torch.int32, device=dev)
-    assert L.msseg_slab_counts(imd.data_ptr(), lad.data_ptr(), *shape, 0.0, old_c.data_ptr(), None) == 0
-    assert torch.equal(old_c, hip.slab_counts(imd, lad, 0.0)) and torch.equal(old_c, hip.slab_counts(imd, lad, 0.0, rule="gt"))
-    cum_gt = np.cumsum(old_c.cpu().numpy()[:, 1].astype(np.int64))
+    # rule "gt", which is the default, against numpy on the same volume
+    gt_c = hip.slab_counts(imd, lad, 0.0, rule="gt")
+    assert np.array_equal(gt_c.cpu().numpy(), ref.slab_counts(img[0], lab, 0.0)) and torch.equal(gt_c, hip.slab_counts(imd, lad, 0.0))
+    lst_gt = np.nonzero(((lab == 0) & (img[0] > 0)).reshape(-1))[0]
+    cum_gt = np.cumsum(gt_c.cpu().numpy()[:, 1].astype(np.int64))
+    assert cum_gt[-1] == lst_gt.size
+    idxs_gt = [int(rng.integers(0, lst_gt.size)) for _ in range(64)]
     rows_gt = []
-    for _ in range(64):
-        idx = int(rng.integers(0, cum_gt[-1]))
+    for idx in idxs_gt:
         z = int(np.searchsorted(cum_gt, idx, side="right"))
         rows_gt.append(PickRow(0, PICK_BG, z, idx - (int(cum_gt[z - 1]) if z else 0), 0, 0, 0.0, 1.0))
     table = _upload(rows_gt, dev)
-    old_p = torch.empty(64, 8, dtype=torch.int32, device=dev)
-    new_p = torch.empty(64, 8, dtype=torch.int32, device=dev)
-    torch.cuda.synchronize()
-    assert L.msseg_pick_voxels(desc.data_ptr(), 1, table.data_ptr(), 64, roi, 0.0, old_p.data_ptr(), None) == 0
-    torch.cuda.synchronize()
-    hip.pick_voxels(desc, 1, table, 64, roi, 0.0, new_p, rule="gt")
-    assert torch.equal(old_p, new_p) and (old_p[:, 7] >= 0).all()
+    gt_p = torch.empty(64, 8, dtype=torch.int32, device=dev)
+    def_p = torch.empty(64, 8, dtype=torch.int32, device=dev)
+    hip.pick_voxels(desc, 1, table, 64, roi, 0.0, gt_p, rule="gt")
+    hip.pick_voxels(desc, 1, table, 64, roi, 0.0, def_p)
+    assert torch.equal(gt_p, def_p) and (gt_p[:, 7] >= 0).all()
+    gt_p = gt_p.cpu().numpy()
+    assert np.array_equal(gt_p[:, 6].astype(np.int64) * shape[1] * shape[2] + gt_p[:, 7], lst_gt[idxs_gt])
     with pytest.raises(ValueError, match="'gt'.*'ne'"):
         hip.slab_counts(imd, lad, 0.0, rule="lt")
 
