@@ -118,6 +118,18 @@ int msseg_conv3d_k3_fwd(const void* x, long long ldx, const void* wp, const floa
 int msseg_conv3d_k3_fwd_accumulate(const void* x, long long ldx, const void* wp, void* y, long long ldy, int N, int D, int H,
                                    int W, int Cin, int Cout, float* stats, void* scratch, size_t scratch_bytes, int dtype,
                                    msseg_stream_t stream);
+/* Conv3d k=3 s=1 p=1 with TWO destinations: output channels [0, split) go to (y, ldy), channels [split, Cout) to (y2, ldy2)
+ * from its channel 0.  For the input gradient of a conv over cat([a, b]) (BasicUNet's UpCat convs): the gradients of a and b
+ * come out as two dense tensors, so that their readers fetch whole cache lines instead of half rows of one 2 x 32-channel
+ * tensor.  Same values as msseg_conv3d_k3_fwd, element for element.  Only for problems msseg_conv3d_k3_split_ok accepts
+ * (the ping-pong kernel, split on a 32-channel boundary) and only with the plain epilogue: stats != NULL or accumulate != 0
+ * is MSSEG_EINVAL, as is any other problem -- there is no second implementation on the generic kernels. */
+int msseg_conv3d_k3_fwd_split(const void* x, long long ldx, const void* wp, const float* bias, void* y, long long ldy,
+                              void* y2, long long ldy2, int split, int N, int D, int H, int W, int Cin, int Cout,
+                              float* stats, int accumulate, int dtype, msseg_stream_t stream);
+/* 1 if msseg_conv3d_k3_fwd_split takes this problem (16-byte aligned, dense operands): it runs on the ping-pong kernel
+ * (msseg_conv3d_k3_kernel() == 3), Cout % 32 == 0, 0 < split < Cout and split % 32 == 0; 0 otherwise */
+int msseg_conv3d_k3_split_ok(int N, int D, int H, int W, int Cin, int Cout, int split, int dtype);
 int msseg_conv3d_k3_dgrad_inbwd(const void* dy, long long lddy, const void* wp, void* da, long long ldda, int N, int D,
                                 int H, int W, int Cin, int Cout, const void* yraw, long long ldyraw, const void* act,
                                 long long ldact, const float* fwd_stats, float slope, float eps, float* red,

@@ -64,7 +64,13 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3pp_kernel(const K3ppParams p) {
     const int r = lane & 15, q = lane >> 4;
     const int coutblk = blockIdx.y;
     const bf16_t* __restrict__ xg = (const bf16_t*)p.x;
-    bf16_t* __restrict__ yg = (bf16_t*)p.y;
+    // split output (plain epilogue only): the cout blocks from split_cb on go to the second destination, at its own row
+    // length and from its channel 0 -- a choice per workgroup, held in scalars (ycb, ldy) that the epilogue's addresses are
+    // built from anyway
+    const bool second = STATS == 0 && p.y2 != nullptr && p.split_cb > 0 && coutblk >= p.split_cb;
+    bf16_t* __restrict__ yg = (bf16_t*)(second ? p.y2 : p.y);
+    const long long ldy = second ? p.ldy2 : p.ldy;
+    const int ycb = second ? coutblk - p.split_cb : coutblk;
 
     Sched<TD, TH, TW> sc;
     sc.init(p.N, p.D, p.H, p.W);
@@ -192,14 +198,14 @@ __global__ __launch_bounds__(NTHREADS, 1) void k3pp_kernel(const K3ppParams p) {
 #pragma unroll
     for (int m = 0; m < TH; ++m) {
         const long long rel = ((long long)wq * p.H + m) * p.W + r;
-        o_off[m] = (unsigned)(rel * p.ldy * 2 + q * 8);
+        o_off[m] = (unsigned)(rel * ldy * 2 + q * 8);
         ny_off[m] = (unsigned)(rel * p.fused.nb_ldy * 2 + q * 8);
         na_off[m] = (unsigned)(rel * p.fused.nb_lda * 2 + q * 8);
     }
     auto epilogue = [&](const TileCo& tc) {
         if constexpr (STATS != 0) sacc.sample(tc.n);
         const long long vox = (((long long)tc.n * p.D + tc.d0) * p.H + tc.h0) * p.W + tc.w0;
-        unsigned char* ybase = (unsigned char*)yg + (vox * p.ldy + coutblk * 32) * 2;
+        unsigned char* ybase = (unsigned char*)yg + (vox * ldy + ycb * 32) * 2;
         const unsigned char* nyb = (const unsigned char*)p.fused.nb_y + (vox * p.fused.nb_ldy + coutblk * 32) * 2;
         const unsigned char* nab = (const unsigned char*)p.fused.nb_a + (vox * p.fused.nb_lda + coutblk * 32) * 2;
         const bool full = tc.d0 + TD <= p.D && tc.h0 + TH <= p.H && tc.w0 + TW <= p.W;
@@ -326,6 +332,7 @@ bool msseg_k3pp_eligible(const K3ppParams& p) {
     if (p.K != 32 || p.M % 32 || p.M > 256) return false;
     if ((p.ldx % 8) || (p.ldy % 4) || ((uintptr_t)p.x & 15) || ((uintptr_t)p.y & 7)) return false;
     if (p.bias && ((uintptr_t)p.bias & 15)) return false;
+    if (p.split_cb > 0 && p.y2 != nullptr && ((p.ldy2 % 4) || ((uintptr_t)p.y2 & 7))) return false;
     if (p.fused.stats && p.N > MSSEG_STATS_NMAX) return false;
     if (p.fused.nb_y && ((p.fused.nb_ldy % 4) || (p.fused.nb_lda % 4) || ((uintptr_t)p.fused.nb_y & 7) || ((uintptr_t)p.fused.nb_a & 7))) return false;
     const long long tiles = msseg_k3_tiles(p.N, p.D, p.H, p.W);
@@ -336,6 +343,10 @@ bool msseg_k3pp_eligible(const K3ppParams& p) {
 
 int msseg_k3pp_launch(const K3ppParams& p, hipStream_t stream) {
     static const bool timing = getenv("MSSEG_K3PP_TIMING") != nullptr;
+    if (p.split_cb > 0 && p.y2 != nullptr) {
+        if (p.split_cb >= p.M / 32) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_pp: split output needs 0 < split_cb < cout blocks");
+        if (p.accumulate || p.fused.stats) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_pp: split output comes with the plain epilogue only (no fused reductions, no accumulate)");
+    }
     if (p.accumulate) {
         if (p.fused.stats == nullptr || p.fused.nb_y != nullptr) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_pp: accumulate mode comes with forward statistics");
         return launch<3, 0>(p, stream);

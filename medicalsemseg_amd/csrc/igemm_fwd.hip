@@ -227,6 +227,33 @@ int msseg_conv3d_k3_fwd_accumulate(const void* x, long long ldx, const void* wp,
     return msseg_k3pp_launch(pp, (hipStream_t)stream);
 }
 
+int msseg_conv3d_k3_split_ok(int N, int D, int H, int W, int Cin, int Cout, int split, int dtype) {
+    if (N < 1 || D < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return 0;
+    if (Cout % 32 || split <= 0 || split >= Cout || split % 32) return 0;
+    return msseg_conv3d_k3_kernel(N, D, H, W, Cin, Cout, dtype) == 3;
+}
+
+int msseg_conv3d_k3_fwd_split(const void* x, long long ldx, const void* wp, const float* bias, void* y, long long ldy,
+                              void* y2, long long ldy2, int split, int N, int D, int H, int W, int Cin, int Cout,
+                              float* stats, int accumulate, int dtype, msseg_stream_t stream) {
+    if (int rc = check_common(x, ldx, wp, y, ldy, dtype, dtype == MSSEG_F32 ? 4 : 2)) return rc;
+    if (!y2) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_fwd_split: null pointer");
+    if (stats || accumulate)
+        MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_fwd_split: two destinations come with the plain epilogue only (no fused statistics, no accumulate)");
+    if (!msseg_conv3d_k3_split_ok(N, D, H, W, Cin, Cout, split, dtype))
+        MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_fwd_split: only problems of the ping-pong kernel (msseg_conv3d_k3_kernel() == 3) with "
+                                 "0 < split < Cout on a 32-channel boundary (split=%d, Cout=%d)", split, Cout);
+    if (ldx < Cin || ldy < split || ldy2 < Cout - split) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_fwd_split: ld smaller than channels");
+    K3ppParams pp{};
+    pp.x = x; pp.ldx = ldx; pp.wp = wp; pp.bias = bias; pp.y = y; pp.ldy = ldy;
+    pp.y2 = y2; pp.ldy2 = ldy2; pp.split_cb = split / 32;
+    pp.N = N; pp.D = D; pp.H = H; pp.W = W; pp.K = Cin; pp.M = Cout;
+    if (!msseg_k3pp_eligible(pp))
+        MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3_fwd_split: the ping-pong kernel needs 16-byte aligned x and bias, 8-byte aligned y / y2 "
+                                 "and row lengths that are multiples of 4 elements");
+    return msseg_k3pp_launch(pp, (hipStream_t)stream);
+}
+
 int msseg_conv3d_k3_dgrad_inbwd(const void* dy, long long lddy, const void* wp, void* da, long long ldda, int N, int D,
                                 int H, int W, int Cin, int Cout, const void* yraw, long long ldyraw, const void* act,
                                 long long ldact, const float* fwd_stats, float slope, float eps, float* red,

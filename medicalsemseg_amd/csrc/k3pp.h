@@ -63,6 +63,11 @@ struct K3ppParams {
     int N, D, H, W, K, M;
     K3Fused fused;
     int accumulate;      // 1: y += conv(x) (the stored bf16 values are read back in the epilogue), statistics of the sums
+    // split output (split_cb > 0; plain epilogue only): cout blocks [0, split_cb) go to (y, ldy) as always, blocks
+    // [split_cb, M / 32) to (y2, ldy2) from its channel 0 -- two dense tensors instead of the two halves of one row
+    void* y2;
+    long long ldy2;
+    int split_cb;
 };
 
 // true when the problem can run on the ping-pong kernel (otherwise the generic igemm kernel is used)

@@ -37,6 +37,8 @@ SIGNATURES = {
     "msseg_conv3d_k3_resident_per_cu": ([_i, _i, _i, _i, _i, _i, _i], _i),
     "msseg_conv3d_k3_fwd": ([_vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _i, _vp], _i),
     "msseg_conv3d_k3_fwd_accumulate": ([_vp, _ll, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _i, _vp], _i),
+    "msseg_conv3d_k3_fwd_split": ([_vp, _ll, _vp, _vp, _vp, _ll, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp], _i),
+    "msseg_conv3d_k3_split_ok": ([_i, _i, _i, _i, _i, _i, _i, _i], _i),
     "msseg_dwconv3d_k3_fwd": ([_vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "msseg_dwconv3d_k3_wgrad": ([_vp, _ll, _vp, _ll, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp], _i),
     "msseg_dwconv3d_fwd": ([_vp, _ll, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
@@ -523,6 +525,30 @@ def conv3d_k3(x, wp, bias, y, cin, cout, stats=None):
         key += "/v%d" % lib().msseg_conv3d_k3_kernel(N, D, H, W, cin, cout, dt(x))
     TIMER.launch(key, 2.0 * nv * 27 * cin * cout, nv * (cin + cout) * esz + 27 * cin * cout * esz, go)
     return y
+
+
+def conv3d_k3_split_ok(vol, cin, cout, split, dtype) -> bool:
+    """does conv3d_k3_split take conv k3 cin -> cout on the grid vol = (N, D, H, W) with the output split at channel `split`?"""
+    return dtype in _DT and bool(lib().msseg_conv3d_k3_split_ok(*vol, cin, cout, split, _DT[dtype]))
+
+
+def conv3d_k3_split(x, wp, bias, ya, yb, cin, cout, stats=None, accumulate=False):
+    """conv3d_k3 with the output channels [0, ca) written to ya and [ca, cout) to yb (ca = ya.shape[-1]): the same values as
+    conv3d_k3 into one cout-wide tensor, as two tensors.  Ping-pong kernel only (conv3d_k3_split_ok); stats / accumulate are
+    refused by the library."""
+    _need_gpu(x, wp, ya, yb)
+    N, D, H, W = x.shape[:4]
+    nv = N * D * H * W
+    esz = x.element_size()
+    ca = ya.shape[-1]
+    if tuple(ya.shape[:4]) != (N, D, H, W) or tuple(yb.shape[:4]) != (N, D, H, W) or ca + yb.shape[-1] != cout:
+        raise ValueError("conv3d_k3_split: ya / yb must be [N, D, H, W, ca] and [N, D, H, W, cout - ca] on x's grid")
+
+    def go():
+        _ck(lib().msseg_conv3d_k3_fwd_split(_p(x), ld(x), _p(wp), _p(bias), _p(ya), ld(ya), _p(yb), ld(yb), ca, N, D, H, W,
+                                            cin, cout, _p(stats), int(accumulate), dt(x), _stream()), "conv3d_k3_fwd_split")
+    TIMER.launch("conv3d_k3_fwd/v3", 2.0 * nv * 27 * cin * cout, nv * (cin + cout) * esz + 27 * cin * cout * esz, go)
+    return ya, yb
 
 
 def conv3d_k3_accumulate(x, wp, y, cin, cout, stats):

@@ -293,10 +293,21 @@ class Conv3:
         vol = tuple(dy.shape[:4])
         return hip.lib().msseg_conv3d_k3_kernel(*vol, self.cout, self.cin, hip.BF16) == (4 if self.cout == 48 else 3)
 
-    def bwd(self, x, dy, need_dx=True, dx_out=None, bias_grad_is_zero=False, next_norm=None, accumulate_dx=False):
+    def dx_split_ok(self, vol, dtype, dx_split) -> bool:
+        """can the input gradient on the grid vol = (N, D, H, W) be written as two dense tensors of dx_split = (ca, cb)
+        channels (the ping-pong kernel's split output)?  MSSEG_NO_SPLIT_DGRAD=1 (read per call): never."""
+        ca, cb_ = dx_split
+        if os.environ.get("MSSEG_NO_SPLIT_DGRAD") or ca + cb_ != self.cin:
+            return False
+        return hip.conv3d_k3_split_ok(vol, self.cout, self.cin, ca, dtype)
+
+    def bwd(self, x, dy, need_dx=True, dx_out=None, bias_grad_is_zero=False, next_norm=None, accumulate_dx=False,
+            dx_split=None):
         """next_norm = (InstNormAct, yraw, stats, act) of the layer whose activation is this conv's input: its
         InstanceNorm-backward reductions are then fused into the input-gradient kernel; returns (dx, red).
-        accumulate_dx (with dx_out, dgrad_accumulate_ok()): dx_out += the input gradient (one rounding of the sum)."""
+        accumulate_dx (with dx_out, dgrad_accumulate_ok()): dx_out += the input gradient (one rounding of the sum).
+        dx_split = (ca, cb) (the input is cat([a, b]); without dx_out / next_norm): where dx_split_ok() the result is the
+        LIST [da, db] of two dense tensors, the same values as dx[..., :ca] and dx[..., ca:]; elsewhere one tensor as always."""
         dtype = x.dtype
         if self.w.requires_grad:
             g, acc = _grad_buf(self.w)
@@ -331,6 +342,11 @@ class Conv3:
             return hip.conv3d_k3_small_bwd_finish(part, ng, dx)
         wp = self.cache.get(self.w, dtype, ("d", vol),
                             lambda: hip.pack_conv_k3(self.w.detach(), dtype, dgrad=True, vol=vol))
+        if dx_split is not None and dx_out is None and next_norm is None and self.dx_split_ok(vol, dtype, dx_split):
+            # the readers of one half of a 2 x 32-channel row fetch whole 128-byte lines: two dense tensors instead
+            da, db_ = _empty_like_vol(dy, dx_split[0]), _empty_like_vol(dy, dx_split[1])
+            hip.conv3d_k3_split(dy, wp, None, da, db_, self.cout, self.cin)
+            return [da, db_]
         dx = dx_out if dx_out is not None else _empty_like_vol(dy, self.cin)
         if next_norm is not None:
             nrm, yraw, stats, act = next_norm
@@ -670,10 +686,10 @@ class ConvNormAct:
         a, stats = self.norm.fwd(y, out, stats=stats, pooled=pooled)
         return a, (x, y, stats, a)
 
-    def bwd(self, saved, da, need_dx=True, red=None, next_saved=None, next_cna=None):
+    def bwd(self, saved, da, need_dx=True, red=None, next_saved=None, next_cna=None, dx_split=None):
         """red: this layer's IN-backward reductions if the producer of `da` already computed them.
         next_cna/next_saved: the ConvNormAct (and its saved tuple) whose activation is this conv's input; when given
-        the result is (dx, red_for_that_layer)."""
+        the result is (dx, red_for_that_layer).  dx_split: see Conv3.bwd (a list of two tensors where the split applies)."""
         x, y, stats, a = saved
         if not need_dx and isinstance(red, torch.Tensor) and self.conv.stem_inbwd_ok(x, y, da):
             # the stem unit: dy is consumed by the weight gradient alone, which forms it from (y, da, red) as it loads
@@ -683,7 +699,7 @@ class ConvNormAct:
         if next_cna is not None and need_dx:
             nx, ny, nstats, na = next_saved
             return self.conv.bwd(x, dy, True, bias_grad_is_zero=True, next_norm=(next_cna.norm, ny, nstats, na))
-        return self.conv.bwd(x, dy, need_dx, bias_grad_is_zero=True)
+        return self.conv.bwd(x, dy, need_dx, bias_grad_is_zero=True, dx_split=dx_split)
 
 
 def maxpool_fwd(x):

@@ -292,10 +292,13 @@ class _UNetFn(torch.autograd.Function):
             lvl = 3 - j
             up_in, s0, s1 = saved["dec"][j]
             g, red = c1.bwd(s1, g, True, red=red_c1, next_saved=s0, next_cna=c0)
-            dcat = c0.bwd(s0, g, True, red=red)
-            skip_grads[lvl] = dcat[..., :f[lvl]]
+            # gradient of cat([skip | up]): two dense tensors where the conv kernel can write them (96^3 / 48^3: each half is half
+            # a 128-byte row, and its readers would fetch the whole row), otherwise the two views of one tensor
+            dcat = c0.bwd(s0, g, True, red=red, dx_split=(f[lvl], c0.conv.cin - f[lvl]))
+            dskip, dup = dcat if isinstance(dcat, list) else (dcat[..., :f[lvl]], dcat[..., f[lvl]:])
+            skip_grads[lvl] = dskip
             below = unit_norm(net._dec[j - 1][2], saved["dec"][j - 1][2]) if j > 0 else unit_norm(net._enc[4][1], saved["enc"][4][1])
-            g, red_c1 = pair(up.bwd(up_in, dcat[..., f[lvl]:], True, next_norm=below))
+            g, red_c1 = pair(up.bwd(up_in, dup, True, next_norm=below))
         # encoder, bottom-up
         g = _UNetFn._encoder_bwd(net, saved, g, red_c1, skip_grads, (4,))
         if getattr(net, "_defer_tail", False):
