@@ -396,10 +396,10 @@ int msseg_scale_channels(const void* x, const float* scale, void* y, int N, long
 /* ---------------------------------------------------------------------------------------------
  * Normalisation / activation / pooling / layout (HBM-bound, one pass each).
  * ------------------------------------------------------------------------------------------- */
-/* Reductions are two-stage and deterministic: blocks write partials into `scratch`, the last block to arrive
- * (agent-scope release/acquire on a counter at scratch[0]) sums them in a fixed order.  `scratch` must be
- * 256-byte aligned, at least msseg_reduce_scratch_bytes() long and ZERO-INITIALISED ONCE by the caller (kernels
- * leave the counter at zero); kernels sharing one scratch must be ordered on one stream. */
+/* Reductions are two-stage and deterministic: blocks write partial rows into `scratch` with plain stores, and a
+ * second launch on the same stream adds them in a fixed order.  `scratch` must be 256-byte aligned and at least
+ * msseg_reduce_scratch_bytes() long; its first 256 bytes are reserved and neither read nor written, and it needs
+ * no initialisation.  Kernels sharing one scratch must be ordered on one stream. */
 size_t msseg_reduce_scratch_bytes(void);
 /* stats[n][c][0..1] = (sum, sum of squares) over the S voxels of sample n. */
 int msseg_channel_stats(const void* x, long long ldx, float* stats, int N, long long S, int C, void* scratch,

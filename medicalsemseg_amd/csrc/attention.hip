@@ -1,4 +1,4 @@
-// Swin 3-D shifted-window attention (forward + backward), LayerNorm over channels, GELU.
+// Swin 3-D shifted-window attention (forward + backward).
 //
 // Window attention replaces swin_nnformer.py:235-289 + :128-196 of the reference between the qkv Linear and the
 // proj Linear:  pad -> roll(-shift) -> window_partition -> softmax(q k^T * scale + bias[+mask]) v -> window_reverse
@@ -267,217 +267,6 @@ __global__ __launch_bounds__(256) void win_attn_bwd_kernel(const AttnParams p) {
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// LayerNorm over channels (one thread per token) and GELU
-// ---------------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T* __restrict__ x, long long ldx, const float* g,
-                                                            const float* bta, T* __restrict__ y, long long ldy,
-                                                            float* mean, float* rstd, long long rows, int C, float eps) {
-    for (long long r = blockIdx.x * 256LL + threadIdx.x; r < rows; r += (long long)gridDim.x * 256) {
-        const T* xr = x + r * ldx;
-        float s = 0.f, s2 = 0.f;
-        for (int c = 0; c < C; ++c) { const float v = DT<T>::ld(xr + c); s += v; s2 += v * v; }
-        const float mu = s / C;
-        float var = s2 / C - mu * mu;
-        var = var > 0.f ? var : 0.f;
-        const float rs = rsqrtf(var + eps);
-        if (mean) { mean[r] = mu; rstd[r] = rs; }
-        T* yr = y + r * ldy;
-        for (int c = 0; c < C; ++c)
-            DT<T>::st(yr + c, (DT<T>::ld(xr + c) - mu) * rs * (g ? g[c] : 1.f) + (bta ? bta[c] : 0.f));
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict__ x, long long ldx, const float* g,
-                                                            const float* mean, const float* rstd,
-                                                            const T* __restrict__ dy, long long lddy, T* __restrict__ dx,
-                                                            long long lddx, float* dg, float* db, long long rows, int C) {
-    for (long long r = blockIdx.x * 256LL + threadIdx.x; r < rows; r += (long long)gridDim.x * 256) {
-        const T* xr = x + r * ldx;
-        const T* dr = dy + r * lddy;
-        const float mu = mean[r], rs = rstd[r];
-        float a = 0.f, b = 0.f;
-        for (int c = 0; c < C; ++c) {
-            const float dyg = DT<T>::ld(dr + c) * (g ? g[c] : 1.f);
-            const float xh = (DT<T>::ld(xr + c) - mu) * rs;
-            a += dyg; b += dyg * xh;
-        }
-        a /= C; b /= C;
-        T* dxr = dx + r * lddx;
-        for (int c = 0; c < C; ++c) {
-            const float d = DT<T>::ld(dr + c);
-            const float xh = (DT<T>::ld(xr + c) - mu) * rs;
-            DT<T>::st(dxr + c, rs * (d * (g ? g[c] : 1.f) - a - xh * b));
-        }
-    }
-}
-
-// Vector forms: LPR lanes (a power of two <= 64) share one token row, 16-byte chunks, the row stays in registers between
-// the statistics and the normalisation (one pass over HBM); reductions by xor-shuffles inside the lane group.
-struct LnVecParams {
-    const void* x; long long ldx; const float* g; const float* b; void* y; long long ldy;
-    float* mean; float* rstd; const void* dy; long long lddy; long long rows; int C, lpr, nch; float eps;
-    const void* add; long long ldadd;   // backward: dx = T(layernorm backward) + add (the gradient of a residual branch that left x)
-};
-
-template <typename T, int MAXCH, bool BWD>
-__global__ __launch_bounds__(256) void layernorm_vec_kernel(const LnVecParams p) {
-    constexpr int EPC = DT<T>::EPC;
-    const int lane = threadIdx.x & 63, sub = lane & (p.lpr - 1), rows_per_wave = 64 / p.lpr;
-    const long long wave_id = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const long long nwaves = (long long)gridDim.x * 4;
-    const float invC = 1.0f / (float)p.C;
-    // per-chunk affine parameters of this lane
-    float gv[MAXCH][EPC], bv[MAXCH][EPC];
-#pragma unroll
-    for (int k = 0; k < MAXCH; ++k) {
-        const int ch = sub + k * p.lpr;
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) {
-            gv[k][e] = (ch < p.nch && p.g) ? p.g[ch * EPC + e] : 1.f;
-            bv[k][e] = (!BWD && ch < p.nch && p.b) ? p.b[ch * EPC + e] : 0.f;
-        }
-    }
-    for (long long r0 = wave_id * rows_per_wave; r0 < p.rows; r0 += nwaves * rows_per_wave) {
-        const long long r = r0 + lane / p.lpr;
-        const bool rok = r < p.rows;
-        float xv[MAXCH][EPC], dv[MAXCH][EPC];
-#pragma unroll
-        for (int k = 0; k < MAXCH; ++k) {
-            const int ch = sub + k * p.lpr;
-            const bool ok = rok && ch < p.nch;
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) xv[k][e] = dv[k][e] = 0.f;
-            if (ok) {
-                Chunk<T>::load((const T*)p.x + r * p.ldx + ch * EPC, xv[k]);
-                if constexpr (BWD) Chunk<T>::load((const T*)p.dy + r * p.lddy + ch * EPC, dv[k]);
-            }
-        }
-        if constexpr (!BWD) {
-            // the row is in registers: mean first, then the centred sum of squares (E[x^2] - mean^2 loses
-            // eps * mean^2 / var, which shows on wide rows with a large mean)
-            float s = 0.f;
-#pragma unroll
-            for (int k = 0; k < MAXCH; ++k)
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) s += xv[k][e];
-            for (int o = p.lpr >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o);
-            const float mu = s * invC;
-            float s2 = 0.f;
-#pragma unroll
-            for (int k = 0; k < MAXCH; ++k) {
-                if (sub + k * p.lpr < p.nch) {
-#pragma unroll
-                    for (int e = 0; e < EPC; ++e) { const float d = xv[k][e] - mu; s2 += d * d; }
-                }
-            }
-            for (int o = p.lpr >> 1; o > 0; o >>= 1) s2 += __shfl_xor(s2, o);
-            const float var = s2 * invC;
-            const float rs = rsqrtf(var + p.eps);
-            if (rok && sub == 0 && p.mean) { p.mean[r] = mu; p.rstd[r] = rs; }
-#pragma unroll
-            for (int k = 0; k < MAXCH; ++k) {
-                const int ch = sub + k * p.lpr;
-                if (rok && ch < p.nch) {
-                    float o[EPC];
-#pragma unroll
-                    for (int e = 0; e < EPC; ++e) o[e] = (xv[k][e] - mu) * rs * gv[k][e] + bv[k][e];
-                    Chunk<T>::store((T*)p.y + r * p.ldy + ch * EPC, o);
-                }
-            }
-        } else {
-            const float mu = rok ? p.mean[r] : 0.f, rs = rok ? p.rstd[r] : 0.f;
-            float a = 0.f, b = 0.f;
-#pragma unroll
-            for (int k = 0; k < MAXCH; ++k)
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) {
-                    const float dyg = dv[k][e] * gv[k][e];
-                    a += dyg;
-                    b += dyg * ((xv[k][e] - mu) * rs);
-                }
-            for (int o = p.lpr >> 1; o > 0; o >>= 1) { a += __shfl_xor(a, o); b += __shfl_xor(b, o); }
-            a *= invC; b *= invC;
-#pragma unroll
-            for (int k = 0; k < MAXCH; ++k) {
-                const int ch = sub + k * p.lpr;
-                if (rok && ch < p.nch) {
-                    float o[EPC];
-#pragma unroll
-                    for (int e = 0; e < EPC; ++e) o[e] = rs * (dv[k][e] * gv[k][e] - a - (xv[k][e] - mu) * rs * b);
-                    if (p.add) {   // the sum autograd forms for a tensor with two consumers: both terms rounded to T, then added
-                        float r2[EPC];
-                        Chunk<T>::load((const T*)p.add + r * p.ldadd + ch * EPC, r2);
-#pragma unroll
-                        for (int e = 0; e < EPC; ++e) o[e] = (float)(T)o[e] + r2[e];
-                    }
-                    Chunk<T>::store((T*)p.y + r * p.ldy + ch * EPC, o);
-                }
-            }
-        }
-    }
-}
-
-// returns false when the vector form does not apply (unaligned rows / odd channel counts)
-template <typename T, bool BWD> bool launch_ln_vec(LnVecParams p, hipStream_t stream) {
-    constexpr int EPC = DT<T>::EPC;
-    const size_t esz = sizeof(T);
-    if (p.C % EPC || ((uintptr_t)p.x & 15) || ((uintptr_t)p.y & 15) || (p.ldx * esz) % 16 || (p.ldy * esz) % 16) return false;
-    if (BWD && (((uintptr_t)p.dy & 15) || (p.lddy * esz) % 16)) return false;
-    p.nch = p.C / EPC;
-    int lpr = 1;
-    while (lpr < p.nch && lpr < 64) lpr <<= 1;
-    p.lpr = lpr;
-    const int maxch = (p.nch + lpr - 1) / lpr;
-    // (rows wider than 8 x 64 chunks -- 4096 bf16 channels -- fall back to the scalar kernel: one thread per row.  The 3072-wide
-    //  LayerNorm of the MONAI variant's last patch merging ran there at 1 ms per pass for 54 rows.)
-    if (maxch > 8) return false;
-    const long long waves = (p.rows + (64 / lpr) - 1) / (64 / lpr);
-    long long blocks = (waves + 3) / 4;
-    const long long cap = (long long)msseg_num_cus() * 8;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    dim3 grid((unsigned)blocks);
-    switch (maxch) {
-        case 1: hipLaunchKernelGGL((layernorm_vec_kernel<T, 1, BWD>), grid, dim3(256), 0, stream, p); break;
-        case 2: hipLaunchKernelGGL((layernorm_vec_kernel<T, 2, BWD>), grid, dim3(256), 0, stream, p); break;
-        case 3: hipLaunchKernelGGL((layernorm_vec_kernel<T, 3, BWD>), grid, dim3(256), 0, stream, p); break;
-        case 4: hipLaunchKernelGGL((layernorm_vec_kernel<T, 4, BWD>), grid, dim3(256), 0, stream, p); break;
-        case 5: case 6: hipLaunchKernelGGL((layernorm_vec_kernel<T, 6, BWD>), grid, dim3(256), 0, stream, p); break;
-        default: hipLaunchKernelGGL((layernorm_vec_kernel<T, 8, BWD>), grid, dim3(256), 0, stream, p); break;
-    }
-    return true;
-}
-
-// exact-erf GELU (nn.GELU of the patch merging, swin_nnformer.py:306) and its gradient; 16-byte chunks where the tensors are
-// aligned (one element per thread and trip ran at a fraction of the memory rate), the scalar form for the rest
-template <typename T, bool BWD>
-__global__ void gelu_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ out, long long n) {
-    constexpr int EPC = DT<T>::EPC;
-    const bool vec = ((((uintptr_t)x) | ((uintptr_t)out) | (BWD ? (uintptr_t)dy : 0)) & 15) == 0;
-    const long long nvec = vec ? n / EPC : 0;
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < nvec; i += (long long)gridDim.x * 256) {
-        float v[EPC], g[EPC], o[EPC];
-        Chunk<T>::load(x + i * EPC, v);
-        if constexpr (BWD) Chunk<T>::load(dy + i * EPC, g);
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) {
-            const float cdf = 0.5f * (1.f + erff(v[e] * 0.70710678118654752f));
-            if constexpr (!BWD) o[e] = v[e] * cdf;
-            else o[e] = g[e] * (cdf + v[e] * 0.3989422804014327f * expf(-0.5f * v[e] * v[e]));
-        }
-        Chunk<T>::store(out + i * EPC, o);
-    }
-    for (long long i = nvec * EPC + blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const float v = DT<T>::ld(x + i);
-        const float cdf = 0.5f * (1.f + erff(v * 0.70710678118654752f));
-        if constexpr (!BWD) DT<T>::st(out + i, v * cdf);
-        else DT<T>::st(out + i, DT<T>::ld(dy + i) * (cdf + v * 0.3989422804014327f * expf(-0.5f * v * v)));
-    }
-}
-
 int fill_attn(AttnParams& p, int B, int S, int H, int W, int C, int heads, int ws, int shift, int bias_ws) {
     if (B < 1 || S < 1 || H < 1 || W < 1 || heads < 1 || C % heads || ws < 1 || shift < 0 || shift >= ws)
         MSSEG_FAIL(MSSEG_EINVAL, "window_attention: bad shape");
@@ -607,86 +396,6 @@ int msseg_window_attention_bwd(const void* qkv, const float* qkv_bias, const flo
     if (smem > 160 * 1024) MSSEG_FAIL(MSSEG_EINVAL, "window_attention_bwd: window too large for LDS (%zu bytes)", smem);
     ATTN_LAUNCH(win_attn_bwd_kernel, smem, "window_attention_bwd");
     MSSEG_CHECK_LAUNCH("window_attention_bwd");
-    return MSSEG_OK;
-}
-
-int msseg_layernorm_fwd(const void* x, long long ldx, const float* gamma, const float* beta, void* y, long long ldy,
-                        float* mean, float* rstd, long long rows, int C, float eps, int dtype, msseg_stream_t stream) {
-    if (!x || !y || rows < 1 || C < 1) MSSEG_FAIL(MSSEG_EINVAL, "layernorm_fwd: bad args");
-    LnVecParams v{};
-    v.x = x; v.ldx = ldx; v.g = gamma; v.b = beta; v.y = y; v.ldy = ldy; v.mean = mean; v.rstd = rstd;
-    v.rows = rows; v.C = C; v.eps = eps;
-    bool done = false;   // by the vector kernel
-    for_dtype(dtype, [&](auto t) { done = launch_ln_vec<typename decltype(t)::type, false>(v, (hipStream_t)stream); });
-    const bool known = done || for_dtype(dtype, [&](auto t) {
-        using T = typename decltype(t)::type;
-        hipLaunchKernelGGL(layernorm_fwd_kernel<T>, dim3(stream_grid(rows)), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx,
-                           gamma, beta, (T*)y, ldy, mean, rstd, rows, C, eps);
-    });
-    if (!known) MSSEG_FAIL(MSSEG_EINVAL, "layernorm_fwd: bad dtype");
-    MSSEG_CHECK_LAUNCH("layernorm_fwd");
-    return MSSEG_OK;
-}
-
-int msseg_layernorm_bwd(const void* x, long long ldx, const float* gamma, const float* mean, const float* rstd,
-                        const void* dy, long long lddy, void* dx, long long lddx, long long rows, int C, int dtype,
-                        msseg_stream_t stream) {
-    if (!x || !mean || !rstd || !dy || !dx || rows < 1 || C < 1) MSSEG_FAIL(MSSEG_EINVAL, "layernorm_bwd: bad args");
-    LnVecParams v{};
-    v.x = x; v.ldx = ldx; v.g = gamma; v.y = dx; v.ldy = lddx; v.mean = (float*)mean; v.rstd = (float*)rstd;
-    v.dy = dy; v.lddy = lddy; v.rows = rows; v.C = C;
-    float* dgamma = nullptr;
-    float* dbeta = nullptr;
-    bool done = false;   // by the vector kernel
-    for_dtype(dtype, [&](auto t) { done = launch_ln_vec<typename decltype(t)::type, true>(v, (hipStream_t)stream); });
-    const bool known = done || for_dtype(dtype, [&](auto t) {
-        using T = typename decltype(t)::type;
-        hipLaunchKernelGGL(layernorm_bwd_kernel<T>, dim3(stream_grid(rows)), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx,
-                           gamma, mean, rstd, (const T*)dy, lddy, (T*)dx, lddx, dgamma, dbeta, rows, C);
-    });
-    if (!known) MSSEG_FAIL(MSSEG_EINVAL, "layernorm_bwd: bad dtype");
-    MSSEG_CHECK_LAUNCH("layernorm_bwd");
-    return MSSEG_OK;
-}
-
-int msseg_layernorm_bwd_add(const void* x, long long ldx, const float* gamma, const float* mean, const float* rstd,
-                            const void* dy, long long lddy, const void* add, long long ldadd, void* dx, long long lddx,
-                            long long rows, int C, int dtype, msseg_stream_t stream) {
-    if (!x || !mean || !rstd || !dy || !dx || !add || rows < 1 || C < 1) MSSEG_FAIL(MSSEG_EINVAL, "layernorm_bwd_add: bad args");
-    if (dtype != MSSEG_F32 && dtype != MSSEG_BF16) MSSEG_FAIL(MSSEG_EINVAL, "layernorm_bwd_add: bad dtype");
-    const size_t esz = dtype == MSSEG_F32 ? 4 : 2;
-    if (((uintptr_t)add & 15) || (ldadd * esz) % 16) MSSEG_FAIL(MSSEG_EINVAL, "layernorm_bwd_add: `add` must have 16-byte aligned rows");
-    LnVecParams v{};
-    v.x = x; v.ldx = ldx; v.g = gamma; v.y = dx; v.ldy = lddx; v.mean = (float*)mean; v.rstd = (float*)rstd;
-    v.dy = dy; v.lddy = lddy; v.rows = rows; v.C = C; v.add = add; v.ldadd = ldadd;
-    bool done = false;
-    for_dtype(dtype, [&](auto t) { done = launch_ln_vec<typename decltype(t)::type, true>(v, (hipStream_t)stream); });
-    if (!done) MSSEG_FAIL(MSSEG_EINVAL, "layernorm_bwd_add: rows of %d channels do not take the vector kernel (16-byte chunks, <= 4096 channels)", C);
-    MSSEG_CHECK_LAUNCH("layernorm_bwd_add");
-    return MSSEG_OK;
-}
-
-int msseg_gelu_fwd(const void* x, void* y, long long n, int dtype, msseg_stream_t stream) {
-    if (!x || !y || n < 1) MSSEG_FAIL(MSSEG_EINVAL, "gelu_fwd: bad args");
-    const bool known = for_dtype(dtype, [&](auto t) {
-        using T = typename decltype(t)::type;
-        hipLaunchKernelGGL((gelu_kernel<T, false>), dim3(stream_grid(n, 1024)), dim3(256), 0, (hipStream_t)stream, (const T*)x,
-                           (const T*)nullptr, (T*)y, n);
-    });
-    if (!known) MSSEG_FAIL(MSSEG_EINVAL, "gelu_fwd: bad dtype");
-    MSSEG_CHECK_LAUNCH("gelu_fwd");
-    return MSSEG_OK;
-}
-
-int msseg_gelu_bwd(const void* x, const void* dy, void* dx, long long n, int dtype, msseg_stream_t stream) {
-    if (!x || !dy || !dx || n < 1) MSSEG_FAIL(MSSEG_EINVAL, "gelu_bwd: bad args");
-    const bool known = for_dtype(dtype, [&](auto t) {
-        using T = typename decltype(t)::type;
-        hipLaunchKernelGGL((gelu_kernel<T, true>), dim3(stream_grid(n, 1024)), dim3(256), 0, (hipStream_t)stream, (const T*)x,
-                           (const T*)dy, (T*)dx, n);
-    });
-    if (!known) MSSEG_FAIL(MSSEG_EINVAL, "gelu_bwd: bad dtype");
-    MSSEG_CHECK_LAUNCH("gelu_bwd");
     return MSSEG_OK;
 }
 

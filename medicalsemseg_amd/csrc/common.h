@@ -161,7 +161,7 @@ MSSEG_DEVFN u32x4_t chunk_pack_bf16(const float* f) {
 }
 
 // ---- InstanceNorm + LeakyReLU backward, per element -------------------------------------------------------------------
-// Shared by the backward apply pass (elementwise.hip) and by the kernels that apply it to an operand as they load it
+// Shared by the backward apply pass (instnorm.hip) and by the kernels that apply it to an operand as they load it
 // (stem_conv.hip), which must give the apply pass's bits.  The expressions are written as the apply pass has always had them
 // and the contraction is the compiler's: in both places it makes one fma of the pre-activation, one of dz - k0 - xh * k1,
 // fma(-mean, mean, s2 / S) of the variance and fma(-mean, sc, beta) of the shift (read from the device assembly; writing the
@@ -218,29 +218,6 @@ MSSEG_DEVFN float wave_sum(float v) {
     return v;
 }
 
-// ---- deterministic grid-wide reductions: "last block finalises" -----------------------------------
-// Every block stores its partial results with plain stores, then calls this.  Exactly one block (the
-// last to arrive) gets `true` and may read all partials with plain loads.  Placement-independent
-// agent-scope release/acquire (cdna_hip_programming.md Guideline 16); the counter is left at zero.
-MSSEG_DEVFN bool grid_last_block(unsigned int* counter, unsigned int total_blocks, int* lds_flag) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its stores
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned int prev = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = (prev == total_blocks - 1u) ? 1 : 0;
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        *lds_flag = last;
-    }
-    __syncthreads();
-    return *lds_flag != 0;
-}
-
 // Fixed-order sum of R partial rows of L floats (L % 4 == 0, L <= 4 * NT) by one block of NT threads: float4-wide,
 // every thread with up to 8 independent loads in flight, row slots then combined through LDS in a fixed order
 // (bit-reproducible).  The L totals end up in lds[NT * 4 ..]; lds: >= NT * 4 + L floats, 16-byte aligned.
@@ -268,13 +245,14 @@ MSSEG_DEVFN void block_rows_sum(const float* rows, int R, int L, float* lds, lon
     __syncthreads();
 }
 
-#define MSSEG_SCRATCH_COUNTER_BYTES 256
+#define MSSEG_SCRATCH_HEADER_BYTES 256
 #define MSSEG_STATS_NMAX 8
 
-// the reduce scratch that the deterministic grid-wide reductions work in: counter block + partial rows
+// the reduce scratch that the two-launch reductions work in: a reserved header (neither read nor written), then the
+// partial rows, which a second launch on the same stream adds in a fixed order
 static inline int scratch_ok(const void* scratch, size_t bytes, const char* who) {
     if (!scratch || ((uintptr_t)scratch & 255) || bytes < msseg_reduce_scratch_bytes())
-        MSSEG_FAIL(MSSEG_EWORKSPACE, "%s: needs a zero-initialised, 256-byte aligned scratch of %zu bytes", who,
+        MSSEG_FAIL(MSSEG_EWORKSPACE, "%s: needs a 256-byte aligned scratch of %zu bytes", who,
                    msseg_reduce_scratch_bytes());
     return MSSEG_OK;
 }
@@ -305,3 +283,5 @@ template <typename F> static inline bool for_dtype(int dtype, F&& f) {
     else return false;
     return true;
 }
+// what an entry point returns then
+static inline int bad_dtype(int dtype) { MSSEG_FAIL(MSSEG_EINVAL, "bad dtype %d", dtype); }

@@ -285,7 +285,7 @@ int msseg_deconv2_fwd_launch(const void* x, long long ldx, const void* wp, const
 }
 
 // dx (+ red[N][Cin][2] InstanceNorm-backward sums when yraw != null, + dbias[Cout] when dbias != null).
-// scratch: the zero-initialised reduce scratch (msseg_reduce_scratch_bytes()).
+// scratch: the reduce scratch (msseg_reduce_scratch_bytes(); partial rows past its reserved header, added by a second launch).
 int msseg_deconv2_bwd_launch(const void* dy, long long lddy, const void* wp, void* dx, long long lddx, int N, int D, int H,
                              int W, int Cin, int Cout, const void* yraw, long long ldyraw, const void* act, long long ldact,
                              const float* fwd_stats, float slope, float eps, float* red, float* dgamma, float* dbeta,
@@ -303,10 +303,10 @@ int msseg_deconv2_bwd_launch(const void* dy, long long lddy, const void* wp, voi
     const int gx = (int)(gxl < 1 ? 1 : gxl);
     const bool inbwd = yraw != nullptr, dbg = dbias != nullptr;
     const int R = gx * N, ncb = Cin / 32;
-    const size_t need = MSSEG_SCRATCH_COUNTER_BYTES + ((size_t)ncb * R * N * 64 + (size_t)R * Cout) * 4;
+    const size_t need = MSSEG_SCRATCH_HEADER_BYTES + ((size_t)ncb * R * N * 64 + (size_t)R * Cout) * 4;
     if ((inbwd || dbg) && (!scratch || scratch_bytes < need))
         MSSEG_FAIL(MSSEG_EWORKSPACE, "deconv2_bwd: scratch of %zu bytes needed", need);
-    p.stats_ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
+    p.stats_ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_HEADER_BYTES);
     p.bias_ws = p.stats_ws + (size_t)ncb * R * N * 64;
     dim3 grid(gx, N);
 #define DC2B(NH_) do {                                                                                                   \

@@ -240,10 +240,10 @@ int msseg_dwconv3d_k3_wgrad(const void* x, long long ldx, const void* dy, long l
     if (rc) return rc;
     if (!dw && !dbias) MSSEG_FAIL(MSSEG_EINVAL, "dwconv3d_k3_wgrad: nothing to compute");
     if (int rc = scratch_ok(scratch, scratch_bytes, "dwconv3d_k3_wgrad")) return rc;
-    float* ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
+    float* ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_HEADER_BYTES);
     const long long NV = (long long)N * D * H * W;
     const size_t row_bytes = (size_t)28 * C * sizeof(float);
-    long long rows = (long long)((scratch_bytes - MSSEG_SCRATCH_COUNTER_BYTES) / row_bytes);
+    long long rows = (long long)((scratch_bytes - MSSEG_SCRATCH_HEADER_BYTES) / row_bytes);
     if (rows < 1) MSSEG_FAIL(MSSEG_EINVAL, "dwconv3d_k3_wgrad: %d channels exceed the reduce scratch", C);
     const int gy = ceil_div(3 * (C / epc_of(dtype)), 64);
     long long want = (long long)msseg_num_cus() * 8 / gy;      // several workgroups per CU in total: the voxel loop is latency-bound

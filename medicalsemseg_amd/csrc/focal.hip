@@ -199,12 +199,12 @@ int msseg_focal_spatial_sum(const void* x, long long ldx, const void* g, long lo
         (mode == 1 && !m_in) || (g && ldg < 1))
         MSSEG_FAIL(MSSEG_EINVAL, "focal_spatial_sum: bad args");
     if (int rc = scratch_ok(scratch, scratch_bytes, "focal_spatial_sum")) return rc;
-    float* part = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
+    float* part = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_HEADER_BYTES);
     const int vslots = 256 / (C / epc);
     long long blocks = ceil_div_ll(S, (long long)vslots * 8);
     const long long cap = (long long)msseg_num_cus() * 4 / N + 1;
     if (blocks > cap) blocks = cap;
-    const long long fit = (long long)((scratch_bytes - MSSEG_SCRATCH_COUNTER_BYTES) / ((size_t)N * C * sizeof(float)));
+    const long long fit = (long long)((scratch_bytes - MSSEG_SCRATCH_HEADER_BYTES) / ((size_t)N * C * sizeof(float)));
     if (blocks > fit) blocks = fit;
     if (blocks < 1) MSSEG_FAIL(MSSEG_EINVAL, "focal_spatial_sum: %d x %d channels exceed the reduce scratch", N, C);
     const long long vpb = ceil_div_ll(S, blocks);

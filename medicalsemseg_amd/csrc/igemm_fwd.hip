@@ -169,7 +169,7 @@ static int k3_fwd_impl(const void* x, long long ldx, const void* wp, const float
         if (N > MSSEG_STATS_NMAX) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3: fused statistics need N <= %d", MSSEG_STATS_NMAX);
         if (Cout > 64 * 16) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_k3: fused statistics need Cout <= 1024");
         if ((rc = scratch_ok(scratch, scratch_bytes, "conv3d_k3 (fused statistics)"))) return rc;
-        f.stats_ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
+        f.stats_ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_HEADER_BYTES);
         f.nb_S = (long long)D * H * W;
     }
     if (dtype == MSSEG_BF16) {
@@ -213,7 +213,7 @@ int msseg_conv3d_k3_fwd_accumulate(const void* x, long long ldx, const void* wp,
     pp.x = x; pp.ldx = ldx; pp.wp = wp; pp.y = y; pp.ldy = ldy;
     pp.N = N; pp.D = D; pp.H = H; pp.W = W; pp.K = Cin; pp.M = Cout;
     pp.fused.stats = stats;
-    pp.fused.stats_ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
+    pp.fused.stats_ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_HEADER_BYTES);
     pp.accumulate = 1;
     if (Cin == 48) {
         if (!msseg_k3c48_eligible(pp))
@@ -351,7 +351,7 @@ int msseg_conv3d_stem_fwd(const void* x, long long ldx, const void* wp, const fl
         if (N > MSSEG_STATS_NMAX) MSSEG_FAIL(MSSEG_EINVAL, "conv3d_stem: fused statistics need N <= %d", MSSEG_STATS_NMAX);
         if (int rc = scratch_ok(scratch, scratch_bytes, "conv3d_stem (fused statistics)")) return rc;
         sp.stats = stats;
-        sp.stats_ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
+        sp.stats_ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_HEADER_BYTES);
     }
     return msseg_stem_fwd_launch(sp, (hipStream_t)stream);
 }
@@ -409,7 +409,7 @@ static int flat_inbwd_common(IgemmParams& p, int N, long long S, int Cout, const
     if (int rc = scratch_ok(scratch, scratch_bytes, who)) return rc;
     p.N = N; p.D = 1; p.H = 1; p.W = (int)S;
     p.fused.stats = red;
-    p.fused.stats_ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
+    p.fused.stats_ws = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_HEADER_BYTES);
     p.fused.nb_y = yraw; p.fused.nb_ldy = ldyraw; p.fused.nb_a = act; p.fused.nb_lda = ldact; p.fused.nb_stats = fwd_stats;
     p.fused.nb_slope = slope; p.fused.nb_eps = eps; p.fused.nb_S = S;
     p.fused.nb_dgamma = dgamma; p.fused.nb_dbeta = dbeta; p.fused.nb_acc = accumulate;

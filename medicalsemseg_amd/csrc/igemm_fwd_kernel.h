@@ -640,7 +640,7 @@ int launch_cfg(IgemmParams& p, hipStream_t stream) {
         // one partial row of N x COUTB x 2 floats per workgroup: no more workgroups than the reduce scratch holds rows of
         // (a persistent workgroup walks tiles in steps of the grid, so a smaller grid is only slower)
         const size_t row_bytes = (size_t)ncb * p.N * C::COUTB * 2 * sizeof(float);
-        const size_t fit = (msseg_reduce_scratch_bytes() - MSSEG_SCRATCH_COUNTER_BYTES) / row_bytes;
+        const size_t fit = (msseg_reduce_scratch_bytes() - MSSEG_SCRATCH_HEADER_BYTES) / row_bytes;
         if (fit < 1) MSSEG_FAIL(MSSEG_EWORKSPACE, "igemm: one row of fused sums (%zu bytes) exceeds the reduce scratch", row_bytes);
         if ((size_t)gx > fit) gx = (int)fit;
     }

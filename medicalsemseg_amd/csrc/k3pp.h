@@ -6,7 +6,7 @@
 // partial row per workgroup to stats_ws, msseg_k3_fused_finalize adds the rows.
 struct K3Fused {
     float* stats;        // per-(n, cout) (sum, sum of squares) of the stored output, [N][M][2]
-    float* stats_ws;     // partial rows (the reduce scratch past its counter block)
+    float* stats_ws;     // partial rows (the reduce scratch past its reserved header)
     long long nb_S;      // voxels per sample
     // InstanceNorm-BACKWARD sums (nb_y != nullptr): the launch produces da, the gradient w.r.t. the activation
     // a = lrelu(IN(yraw)); the epilogue accumulates (sum dz, sum dz * yraw), dz = da * lrelu'(a), and the finalise step

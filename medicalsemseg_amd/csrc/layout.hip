@@ -11,6 +11,9 @@
 //                 adjoint sums, per fine voxel, the slots whose offset equals the voxel's parity in slot order (deterministic).
 // torch ran these as a fill + strided copy per pad / crop and eight strided copies + eight index-adds per merging (7.8 % of the
 // GPU time of the official-variant step).  HBM-bound; one thread per (destination voxel, chunk).
+//
+// Also the layout changes at the network's boundary, one thread per element: NCDHW <-> channels-last NDHWC with an optional
+// dtype change, and zero_stuff2 (a stride-2 convolution's gradient spread onto the input grid).
 #include "common.h"
 
 namespace {
@@ -110,6 +113,52 @@ __global__ __launch_bounds__(256) void merge_gather_bwd_kernel(const T* __restri
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// NCDHW <-> NDHWC (with a dtype change), zero stuffing
+// ---------------------------------------------------------------------------------------------------------
+template <typename TS, typename TD_>
+__global__ void ncdhw_to_ndhwc_kernel(const TS* __restrict__ src, TD_* __restrict__ dst, long long ldd, int N, int C,
+                                      long long S) {
+    const long long total = (long long)N * S * C;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int c = (int)(i % C);
+        const long long s = (i / C) % S;
+        const long long n = i / ((long long)C * S);
+        DT<TD_>::st(dst + (n * S + s) * ldd + c, DT<TS>::ld(src + (n * C + c) * S + s));
+    }
+}
+template <typename TS, typename TD_>
+__global__ void ndhwc_to_ncdhw_kernel(const TS* __restrict__ src, long long lds, TD_* __restrict__ dst, int N, int C,
+                                      long long S) {
+    const long long total = (long long)N * S * C;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long s = i % S;
+        const int c = (int)((i / S) % C);
+        const long long n = i / ((long long)C * S);
+        DT<TD_>::st(dst + (n * C + c) * S + s, DT<TS>::ld(src + (n * S + s) * lds + c));
+    }
+}
+
+// out[n][2o] = dy[n][o], zero elsewhere: turns the input gradient / weight gradient of a stride-2 convolution
+// into stride-1 problems on the input grid.
+template <typename T>
+__global__ void zero_stuff2_kernel(const T* __restrict__ dy, long long lddy, T* __restrict__ out, long long ldo, int N,
+                                   int OD, int OH, int OW, int ID, int IH, int IW, int C) {
+    const long long total = (long long)N * ID * IH * IW * C;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int c = (int)(i % C);
+        long long t = i / C;
+        const int w = (int)(t % IW); t /= IW;
+        const int h = (int)(t % IH); t /= IH;
+        const int d = (int)(t % ID);
+        const int n = (int)(t / ID);
+        float v = 0.f;
+        if (!(d & 1) && !(h & 1) && !(w & 1) && d / 2 < OD && h / 2 < OH && w / 2 < OW)
+            v = DT<T>::ld(dy + ((((long long)n * OD + d / 2) * OH + h / 2) * OW + w / 2) * lddy + c);
+        DT<T>::st(out + ((((long long)n * ID + d) * IH + h) * IW + w) * ldo + c, v);
+    }
+}
+
 int check(const void* a, long long lda, const void* b, long long ldb, int C, int dtype, long long total, const char* who) {
     if (!a || !b) MSSEG_FAIL(MSSEG_EINVAL, "%s: null pointer", who);
     if (dtype != MSSEG_F32 && dtype != MSSEG_BF16) MSSEG_FAIL(MSSEG_EINVAL, "%s: bad dtype", who);
@@ -165,6 +214,56 @@ int msseg_merge_gather_bwd(const void* dy, long long lddy, void* dx, long long l
                            lddx, N, D, H, W, C, subs);
     });
     MSSEG_CHECK_LAUNCH("merge_gather_bwd");
+    return MSSEG_OK;
+}
+
+int msseg_ncdhw_to_ndhwc(const void* src, int src_dtype, void* dst, long long ldd, int dst_dtype, int N, int C,
+                         long long S, msseg_stream_t stream) {
+    if (!src || !dst || N < 1 || C < 1 || S < 1 || ldd < C) MSSEG_FAIL(MSSEG_EINVAL, "ncdhw_to_ndhwc: bad args");
+    const int g = stream_grid((long long)N * C * S, 1024);
+    hipStream_t st = (hipStream_t)stream;
+    if (src_dtype == MSSEG_F32 && dst_dtype == MSSEG_F32)
+        hipLaunchKernelGGL((ncdhw_to_ndhwc_kernel<float, float>), dim3(g), dim3(256), 0, st, (const float*)src, (float*)dst, ldd, N, C, S);
+    else if (src_dtype == MSSEG_F32 && dst_dtype == MSSEG_BF16)
+        hipLaunchKernelGGL((ncdhw_to_ndhwc_kernel<float, bf16_t>), dim3(g), dim3(256), 0, st, (const float*)src, (bf16_t*)dst, ldd, N, C, S);
+    else if (src_dtype == MSSEG_BF16 && dst_dtype == MSSEG_BF16)
+        hipLaunchKernelGGL((ncdhw_to_ndhwc_kernel<bf16_t, bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, ldd, N, C, S);
+    else if (src_dtype == MSSEG_BF16 && dst_dtype == MSSEG_F32)
+        hipLaunchKernelGGL((ncdhw_to_ndhwc_kernel<bf16_t, float>), dim3(g), dim3(256), 0, st, (const bf16_t*)src, (float*)dst, ldd, N, C, S);
+    else MSSEG_FAIL(MSSEG_EINVAL, "ncdhw_to_ndhwc: bad dtypes");
+    MSSEG_CHECK_LAUNCH("ncdhw_to_ndhwc");
+    return MSSEG_OK;
+}
+
+int msseg_ndhwc_to_ncdhw(const void* src, long long lds, int src_dtype, void* dst, int dst_dtype, int N, int C,
+                         long long S, msseg_stream_t stream) {
+    if (!src || !dst || N < 1 || C < 1 || S < 1 || lds < C) MSSEG_FAIL(MSSEG_EINVAL, "ndhwc_to_ncdhw: bad args");
+    const int g = stream_grid((long long)N * C * S, 1024);
+    hipStream_t st = (hipStream_t)stream;
+    if (src_dtype == MSSEG_F32 && dst_dtype == MSSEG_F32)
+        hipLaunchKernelGGL((ndhwc_to_ncdhw_kernel<float, float>), dim3(g), dim3(256), 0, st, (const float*)src, lds, (float*)dst, N, C, S);
+    else if (src_dtype == MSSEG_BF16 && dst_dtype == MSSEG_F32)
+        hipLaunchKernelGGL((ndhwc_to_ncdhw_kernel<bf16_t, float>), dim3(g), dim3(256), 0, st, (const bf16_t*)src, lds, (float*)dst, N, C, S);
+    else if (src_dtype == MSSEG_BF16 && dst_dtype == MSSEG_BF16)
+        hipLaunchKernelGGL((ndhwc_to_ncdhw_kernel<bf16_t, bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)src, lds, (bf16_t*)dst, N, C, S);
+    else if (src_dtype == MSSEG_F32 && dst_dtype == MSSEG_BF16)
+        hipLaunchKernelGGL((ndhwc_to_ncdhw_kernel<float, bf16_t>), dim3(g), dim3(256), 0, st, (const float*)src, lds, (bf16_t*)dst, N, C, S);
+    else MSSEG_FAIL(MSSEG_EINVAL, "ndhwc_to_ncdhw: bad dtypes");
+    MSSEG_CHECK_LAUNCH("ndhwc_to_ncdhw");
+    return MSSEG_OK;
+}
+
+int msseg_zero_stuff2(const void* dy, long long lddy, void* out, long long ldo, int N, int OD, int OH, int OW, int ID,
+                      int IH, int IW, int C, int dtype, msseg_stream_t stream) {
+    if (!dy || !out || N < 1 || C < 1) MSSEG_FAIL(MSSEG_EINVAL, "zero_stuff2: bad args");
+    const int g = stream_grid((long long)N * ID * IH * IW * C, 1024);
+    const bool known = for_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(zero_stuff2_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const T*)dy, lddy, (T*)out, ldo, N, OD,
+                           OH, OW, ID, IH, IW, C);
+    });
+    if (!known) return bad_dtype(dtype);
+    MSSEG_CHECK_LAUNCH("zero_stuff2");
     return MSSEG_OK;
 }
 

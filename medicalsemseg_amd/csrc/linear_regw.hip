@@ -21,7 +21,7 @@
 //   EPI_GELU_BWD  y = (dy W) as stored * gelu'(aux): the input gradient of fc2 straight into the gradient of fc1's output
 //   EPI_ADD       y = aux + (x W + b) as stored: the residual add behind the attention projection / fc2 of a Swin block
 //                 (swin_nnformer.py:243-262) without the separate add pass
-// with the arithmetic of gelu_kernel (attention.hip) on the bf16-rounded operands, i.e. bit-identical to the unfused chain.
+// with the arithmetic of gelu_kernel (pointwise.hip) on the bf16-rounded operands, i.e. bit-identical to the unfused chain.
 #include "k3pp.h"
 #include "pingpong.h"   // pack_bf16x2
 

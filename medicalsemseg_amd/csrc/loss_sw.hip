@@ -604,10 +604,10 @@ int msseg_seg_loss_fwd(const void* logits, long long ld, int dtype, const void* 
     if (!logits || !labels || !partial || !loss || N < 1 || N > 8 || S < 1 || C < 1 || C > 16 || (ld != 0 && ld < C) ||
         label_dtype < 0 || label_dtype > 3 || kind < 0 || kind > 2)
         MSSEG_FAIL(MSSEG_EINVAL, "seg_loss_fwd: bad args (1 <= N <= 8, 1 <= C <= 16, 0 <= kind <= 2)");
-    const size_t need = MSSEG_SCRATCH_COUNTER_BYTES + (size_t)N * ((size_t)msseg_num_cus() * 8 / N + 2) * C * 7 * 4;
+    const size_t need = MSSEG_SCRATCH_HEADER_BYTES + (size_t)N * ((size_t)msseg_num_cus() * 8 / N + 2) * C * 7 * 4;
     if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < need)
         MSSEG_FAIL(MSSEG_EWORKSPACE, "seg_loss_fwd: scratch of %zu bytes needed", need);
-    float* rows = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_COUNTER_BYTES);
+    float* rows = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_HEADER_BYTES);
     DISPATCH_TC(dtype, C, launch_fwd, logits, ld, labels, label_dtype, partial, hard, loss, N, S, C, smooth_nr, smooth_dr,
                 kind, alpha, beta, rows, (hipStream_t)stream);
 }

@@ -74,7 +74,7 @@ __global__ __launch_bounds__(F_THREADS) void stem_fwd_kernel(const StemParams p)
     if (STATS) sacc.zero_slots();
     float nsc[NORM ? JT : 1][4], nsh[NORM ? JT : 1][4];
     int n_n = -1;
-    auto load_norm = [&](int n) {   // scale / shift of sample n: instnorm_kernel's arithmetic (elementwise.hip mean_rstd)
+    auto load_norm = [&](int n) {   // scale / shift of sample n: instnorm_kernel's arithmetic (instnorm.hip; mean_rstd of common.h)
         if constexpr (NORM != 0) {
             const float inv = 1.0f / (float)((long long)p.D * p.H * p.W);
 #pragma unroll
@@ -183,7 +183,7 @@ constexpr int WG_BUF_BYTES = P_BYTES + 3 * XS_ELEMS * 2 + 64;
 constexpr int WG_NMAX = 8;                          // samples of the INBWD constants table
 constexpr int WG_TAB_BYTES = WG_NMAX * 32 * 6 * 4;
 
-// INBWD: dy does not exist.  It is the InstanceNorm + LeakyReLU backward apply (elementwise.hip, instnorm_stream_kernel MODE 2
+// INBWD: dy does not exist.  It is the InstanceNorm + LeakyReLU backward apply (instnorm.hip, instnorm_stream_kernel MODE 2
 // without the stored activation) of the unit's raw output yraw and the gradient da of its activation; the only consumer of the
 // stem's dy is this weight gradient (no input gradient, and the bias gradient of a conv in front of InstanceNorm is zero), so
 // the tile is formed while it is staged: each thread loads the yraw and da chunks of the LDS slots the DMA would have filled

@@ -498,7 +498,9 @@ _scratch_cache = {}
 
 
 def scratch(device) -> torch.Tensor:
-    """zero-initialised scratch for the deterministic two-stage reductions (one per device, stable address)."""
+    """scratch for the deterministic two-launch reductions (one per device, stable address): blocks store partial rows past
+    a reserved 256-byte header that no kernel reads or writes, and a second launch on the same stream adds them in a fixed
+    order.  The C contract asks for no initialisation; the buffer is allocated as zeros all the same."""
     key = device.index if device.index is not None else torch.cuda.current_device()
     buf = _scratch_cache.get(key)
     if buf is None:

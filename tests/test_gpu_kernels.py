@@ -469,7 +469,7 @@ def test_conv3d_k3_fused_stats(dtype, cin, cout, sp, N):
     wp = hip.pack_conv_k3(w.to(dev), dtype, vol=(N, *sp))
     y = torch.empty(N, *sp, cout, dtype=dtype, device=dev)
     stats = torch.full((N, cout, 2), float("nan"), device=dev)
-    for _ in range(3):   # the scratch counter must come back to zero after every launch
+    for _ in range(3):   # repeated launches share the scratch: each rewrites its partial rows, nothing carries over
         hip.conv3d_k3(xg, wp, b.to(dev), y, cin, cout, stats)
     yf = y.float().reshape(N, -1, cout)
     ref = torch.stack([yf.sum(1), (yf * yf).sum(1)], dim=-1)

@@ -1,7 +1,8 @@
 """The InstanceNorm forward and backward-apply kernels take several rows per thread and trip: shapes at which that batching
 can go wrong (fewer rows than one batch, partial last trips, channel slices of wider buffers), against float64 torch
 formulas, with every output inside a sentinel-filled buffer that must come back untouched around it and fully written
-inside it.  The pooled-backward and head-backward reductions, which walk rows the same way, get the same guard on small shapes."""
+inside it.  The pooled-backward and head-backward reductions, which walk rows the same way, get the same guard on small shapes.
+One test states the contract of the reduce scratch these reductions share: its 256-byte header is never touched."""
 import functools
 
 import pytest
@@ -70,12 +71,13 @@ def _reference(dtype, C, sp, res):
 
 @pytest.mark.parametrize("layout", ["dense", "first", "second"])
 @pytest.mark.parametrize("res", [False, True])
-@pytest.mark.parametrize("C", [32, 48, 20])
+@pytest.mark.parametrize("C", [32, 48, 20, 6])
 @pytest.mark.parametrize("sp", [(3, 5, 7), (8, 8, 10), (12, 12, 18)])
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_instnorm_act_fwd_and_bwd_apply(dtype, sp, C, res, layout):
     """res: forward with a residual, backward from the stored activation and with dres; otherwise forward without one and
-    the backward recomputing the sign from x (y absent).  C = 20 takes the scalar kernels"""
+    the backward recomputing the sign from x (y absent).  C = 20 takes the scalar kernels in bf16 only (20 % 4 == 0: float32
+    streams 16-byte chunks); C = 6 takes them in both dtypes and in all three layouts"""
     from medicalsemseg_amd import hip
     dev = _dev()
     N = 2
@@ -99,6 +101,60 @@ def test_instnorm_act_fwd_and_bwd_apply(dtype, sp, C, res, layout):
     if res:
         dres.assert_exact("instnorm dres")
         check(ncdhw(dres.t), ref["dres"], dtype, "instnorm dres")
+
+
+def _scratch_users(dtype, C, dev):
+    """every output of one round of the reductions that work in hip.scratch: N = 2, (3, 5, 7) voxels, C channels"""
+    from medicalsemseg_amd import hip
+    N, sp = 2, (3, 5, 7)
+    x = cl(gen(N, C, *sp, seed=61) * 2 + 0.5, dtype, dev)
+    dy = cl(gen(N, C, *sp, seed=62), dtype, dev)
+    gamma, beta = (gen(C, seed=63) * 0.2 + 1).to(dev), (gen(C, seed=64) * 0.2).to(dev)
+
+    def unwritten(*shape):   # NaN never compares equal: an element a kernel leaves alone fails the comparison of the rounds
+        return torch.full(shape, float("nan"), device=dev)
+
+    out = {}
+    out["channel_stats"] = hip.channel_stats(x, unwritten(N, C, 2))
+    out["channel_sum"] = hip.channel_sum(x, unwritten(C))
+    out["in dgamma"], out["in dbeta"] = unwritten(C), unwritten(C)
+    out["in red"] = hip.instnorm_act_bwd_reduce(x, out["channel_stats"], gamma, None, dy, SLOPE, EPS, out["in dgamma"],
+                                                out["in dbeta"], False, beta)
+    rows, drows = x.view(N * 3 * 5 * 7, C), dy.view(N * 3 * 5 * 7, C)   # the same tensor as [210, C] token rows
+    out["ln y"], out["ln dx"] = torch.empty_like(rows), torch.empty_like(rows)
+    out["ln mean"], out["ln rstd"] = hip.layernorm_fwd(rows, gamma, beta, out["ln y"], EPS)
+    out["ln dgamma"], out["ln dbeta"] = unwritten(C), unwritten(C)
+    hip.layernorm_bwd(rows, gamma, out["ln mean"], out["ln rstd"], drows, out["ln dx"], out["ln dgamma"], out["ln dbeta"])
+    if dtype == torch.bfloat16:   # statistics from the conv epilogue: partial rows per workgroup, the same second launch
+        cin = cout = 32
+        xc = cl(gen(N, cin, 8, 8, 8, seed=65), dtype, dev)
+        w = gen(cout, cin, 3, 3, 3, seed=66, scale=(cin * 27) ** -0.5)
+        wp = hip.pack_conv_k3(w.to(dev), dtype, vol=(N, 8, 8, 8))
+        out["conv y"] = torch.empty(N, 8, 8, 8, cout, dtype=dtype, device=dev)
+        out["conv stats"] = unwritten(N, cout, 2)
+        hip.conv3d_k3(xc, wp, gen(cout, seed=67).to(dev), out["conv y"], cin, cout, out["conv stats"])
+    return out
+
+
+@pytest.mark.parametrize("C", [32, 6])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_reduce_scratch_header_is_neither_read_nor_written(dtype, C):
+    """include/msseg.h: the first 256 bytes of the reduce scratch are reserved, no kernel reads or writes them, and the
+    scratch needs no initialisation.  The reductions give the same bits with the header as allocated and with every header
+    byte 0xFF, and leave those bytes as they found them."""
+    from medicalsemseg_amd import hip
+    dev = _dev()
+    header = hip.scratch(dev)[:256]
+    try:
+        first = _scratch_users(dtype, C, dev)
+        header.fill_(0xFF)
+        second = _scratch_users(dtype, C, dev)
+        assert first.keys() == second.keys()
+        for name in first:
+            assert torch.equal(first[name], second[name]), f"{name}: depends on the scratch header"
+        assert bool((header == 0xFF).all()), "a kernel wrote into the scratch header"
+    finally:
+        header.zero_()
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
