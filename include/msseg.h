@@ -597,6 +597,46 @@ int msseg_seg_loss_bwd(const void* logits, long long ld, int dtype, const void* 
                        int C, float smooth_nr, float smooth_dr, int kind, float alpha, float beta, msseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Region-based training (nnU-Net's overlapping label regions): channel c of the logits is one SIGMOID output whose
+ * target at a voxel with label value `lab` is t = (mask[c] >> lab) & 1 (0 for lab outside 0..31), formed in registers
+ * from the label map; no multi-channel label tensor exists.  The masks are read on the host when the call is made and
+ * travel in the kernel arguments.  1 <= C <= 16, else MSSEG_EINVAL with nothing launched.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct { uint32_t mask[16]; } msseg_region_masks;
+/* The four passes of msseg_seg_loss_* (same argument lists, layouts, N <= 8 rule of _fwd and scratch) for the sigmoid form
+ * of each `kind`.  With p = sigmoid(x), per (n, c): I = sum p*t, T = sum t.
+ *  MSSEG_LOSS_DICE_CE: mean_{n,c}(1 - (2I + snr)/(sum p^2 + T + sdr)) + mean_{n,c,s}(max(x,0) - x*t + log1p(exp(-|x|)));
+ *    partial[n][c] = (I, sum p^2, T, sum of the BCE values); loss[3] = (dice + bce, dice, bce).
+ *  MSSEG_LOSS_TVERSKY: mean_{n,c}(1 - (I + snr)/(I + alpha*(sum p - I) + beta*(T - I) + sdr)); slot 1 is sum p.
+ *  MSSEG_LOSS_DICE_FOCAL: the Dice term plus the mean over N*C*S of the sigmoid focal values (gamma 2) against t.
+ * hard[n][c] = (|P_c & T_c|, |P_c|, |T_c|) with P_c = (x_c > 0).
+ * bwd: dlogits = gscale[0] * dLoss/dlogits; Dice: 1/(N*C) * (-2t/den + (2I + snr)*2p/den^2) * p*(1-p); BCE: (p - t)/(N*C*S);
+ *    1 - p is sigmoid(-x), not a subtraction. */
+int msseg_region_loss_partials(const void* logits, long long ld, int dtype, const void* labels, int label_dtype,
+                               float* partial, float* hard, int N, long long S, int C, int kind,
+                               const msseg_region_masks* masks, msseg_stream_t stream);
+int msseg_region_loss_fwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype, float* partial,
+                          float* hard, float* loss, int N, long long S, int C, float smooth_nr, float smooth_dr, int kind,
+                          float alpha, float beta, const msseg_region_masks* masks, void* scratch, size_t scratch_bytes,
+                          msseg_stream_t stream);
+int msseg_region_loss_finalize(const float* partial, float* loss, int N, long long S, int C, float smooth_nr,
+                               float smooth_dr, int kind, float alpha, float beta, msseg_stream_t stream);
+int msseg_region_loss_bwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype,
+                          const float* partial, const float* gscale, void* dlogits, long long ldd, int N, long long S,
+                          int C, float smooth_nr, float smooth_dr, int kind, float alpha, float beta,
+                          const msseg_region_masks* masks, msseg_stream_t stream);
+/* logits fp32 [C][V] -> label map: bits = sum_c (logits[c][v] > 0) << c (NaN does not fire); out[v] = 0, then for c = 0..C-1
+ * in order: if bit c is set, out[v] = values[c] (later regions paint over earlier ones, nnU-Net's regions_class_order).
+ * values: C bytes on the host.  bits: nullable, the fired-region set per voxel. */
+int msseg_region_decode_u8(const float* logits, int C, long long V, const uint8_t* values, uint8_t* out, uint16_t* bits,
+                           msseg_stream_t stream);
+/* counts[c][0..2] = (|P_c & T_c|, |P_c|, |T_c|) of two uint8 label maps, both taken through the masks (a value above 31 is in
+ * no region).  Per-block integer counts into `scratch` (the reduce scratch), added in a fixed order in 64-bit integers by a
+ * second step; exact up to 2^24 per count (the float output). */
+int msseg_region_counts_u8(const uint8_t* pred, const uint8_t* label, long long V, int C, const msseg_region_masks* masks,
+                           float* counts, void* scratch, size_t scratch_bytes, msseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Optimiser: fused AdamW over one flat fp32 buffer (torch.optim.AdamW(betas=(0.9,0.95), eps=1e-6) of
  * run_training.py:92-93; decay applies where decay_mask[i] != 0 -- timm add_weight_decay semantics).
  * grad_scale[0] multiplies the gradient first (clip coefficient / loss-scale inverse).

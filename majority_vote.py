@@ -21,7 +21,9 @@ if ROOT not in sys.path:
 def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description="majority vote over the label maps of several folds")
     parser.add_argument("--in_folder", type=str, required=True, help="the folder that holds Fold0 .. Fold<folds - 1>")
-    parser.add_argument("--n_classes", type=int, required=True)
+    parser.add_argument("--n_classes", type=int, required=True,
+                        help="number of label values of the maps: --output_dim of the run, or under --label_regions one more "
+                             "than the largest label a SET or VALUE names (4 for 1,2,3=1 2,3=2 3=3)")
     parser.add_argument("--subfolder_prefix", type=str, default="rs", help="rs, pred or native")
     parser.add_argument("--folds", type=int, default=5)
     return parser

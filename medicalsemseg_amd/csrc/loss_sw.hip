@@ -1,6 +1,7 @@
 // Segmentation losses -- Dice + cross-entropy, Tversky, Dice + focal -- as one pass over logits/labels forward and one
-// pass backward (the loss kind is a compile-time parameter of the same kernels), hard Dice metric counts, and the
-// sliding-window gather / blend / normalise kernels.
+// pass backward (the loss kind is a compile-time parameter of the same kernels, and so is REGIONS: one sigmoid output per
+// overlapping label region instead of a softmax over exclusive classes), hard Dice metric counts, and the sliding-window
+// gather / blend / normalise kernels.
 #include <type_traits>
 
 #include "common.h"
@@ -86,13 +87,32 @@ MSSEG_DEVFN float focal_grad(float x, float t) {
     return t > 0.f ? -dz : dz;
 }
 
+// REGIONS: target of channel c at a voxel with label value lab -- is lab in region c?  The masks are kernel arguments (scalar
+// registers), c is a compile-time index in every caller: no table load.  A label outside 0..31 is in no region.
+MSSEG_DEVFN float region_target(const msseg_region_masks& rm, int c, int lab) {
+    return ((unsigned)lab < 32u && ((rm.mask[c] >> (lab & 31)) & 1u)) ? 1.f : 0.f;
+}
+
+// p = sigmoid(x), q = sigmoid(-x) = 1 - p (each from its own quotient, not from a subtraction) and L = log1p(exp(-|x|)), the
+// softplus tail that BCEWithLogits = max(x, 0) - x*t + L needs
+MSSEG_DEVFN void sigmoid_parts(float x, float& p, float& q, float& L) {
+    const float e = expf(-fabsf(x));
+    const float r = 1.f / (1.f + e), er = e * r;
+    L = log1pf(e);
+    p = x >= 0.f ? r : er;
+    q = x >= 0.f ? er : r;
+}
+
 // partial[n][c][0..3] += (sum p*t, sum p^2, sum t, -sum t*log p); hard[n][c][0..2] += (|P&T|, |P|, |T|)
 // (KIND_TVERSKY: slot 1 is sum p, slot 3 stays 0; KIND_DICE_FOCAL: slot 3 is the sum of the focal values)
-template <typename T, int CMAX, int KIND>
+// REGIONS: p = sigmoid(x[c]) and t = region_target per channel, slot 3 of KIND_DICE_CE is the sum of the BCE values, the
+// hard prediction of channel c is x[c] > 0
+template <typename T, int CMAX, int KIND, bool REGIONS>
 __global__ __launch_bounds__(256) void dice_ce_partials_kernel(const T* __restrict__ logits, long long ld,
                                                                const void* __restrict__ labels, int label_dtype,
                                                                float* partial, float* hard, long long S, int C,
-                                                               long long vox_per_block, float* rows) {
+                                                               long long vox_per_block, float* rows,
+                                                               const msseg_region_masks rm) {
     __shared__ float red[4][CMAX * 7];
     const long long n = blockIdx.y;
     const long long s0 = (long long)blockIdx.x * vox_per_block;
@@ -107,6 +127,27 @@ __global__ __launch_bounds__(256) void dice_ce_partials_kernel(const T* __restri
     // single 2-byte load in flight per class: 1.3 TB/s); the per-thread order of the voxels, and with it every sum, is unchanged
     const bool vec = ld > 0 && ld * (long long)sizeof(T) == 16 && C <= DT<T>::EPC && (((uintptr_t)logits) & 15) == 0;
     auto one = [&](float* x, int lab) {
+        if constexpr (REGIONS) {
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c) {
+                if (c < C) {
+                    const float t = region_target(rm, c, lab);
+                    float p, q, L;
+                    sigmoid_parts(x[c], p, q, L);
+                    acc[c][0] += p * t;
+                    if constexpr (KIND == KIND_TVERSKY) acc[c][1] += p;
+                    else acc[c][1] += p * p;
+                    acc[c][2] += t;
+                    if constexpr (KIND == KIND_DICE_CE) acc[c][3] += fmaxf(x[c], 0.f) - x[c] * t + L;
+                    else if constexpr (KIND == KIND_DICE_FOCAL) acc[c][3] += focal_value(x[c], t);
+                    const float pm = x[c] > 0.f ? 1.f : 0.f;
+                    acc[c][4] += pm * t;
+                    acc[c][5] += pm;
+                    acc[c][6] += t;
+                }
+            }
+            return;
+        }
         int am = 0;
         float best = x[0];
 #pragma unroll
@@ -193,10 +234,11 @@ __global__ __launch_bounds__(256) void dice_ce_partials_kernel(const T* __restri
 }
 
 // loss[0..2] = (total, first term, second term) from the N*C rows of sums at `sums` (`stride` floats apart):
-// (dice + ce, dice, ce) | (tversky, tversky, 0) | (dice + focal, dice, focal); one thread, fixed order
+// (dice + ce, dice, ce) | (tversky, tversky, 0) | (dice + focal, dice, focal); one thread, fixed order.  regions: the sums are
+// those of the sigmoid kinds (the same expressions; only the count behind the mean of slot 3 differs)
 template <int KIND>
 MSSEG_DEVFN void loss_triple(const float* sums, int stride, float* loss, int N, long long S, int C, float snr, float sdr,
-                             float alpha, float beta) {
+                             float alpha, float beta, int regions) {
     float dice = 0.f, ce = 0.f;
     for (int i = 0; i < N * C; ++i) {
         const float I = sums[i * stride + 0], p2 = sums[i * stride + 1], t = sums[i * stride + 2];
@@ -209,7 +251,8 @@ MSSEG_DEVFN void loss_triple(const float* sums, int stride, float* loss, int N, 
         }
     }
     dice /= (float)(N * C);
-    if constexpr (KIND == KIND_DICE_CE) ce /= (float)((double)N * (double)S);
+    // the softmax cross-entropy has one term per voxel, the regions' BCE one per voxel and channel
+    if constexpr (KIND == KIND_DICE_CE) ce /= (float)(regions ? (double)N * (double)C * (double)S : (double)N * (double)S);
     else if constexpr (KIND == KIND_DICE_FOCAL) ce /= (float)((double)N * (double)C * (double)S);
     loss[0] = dice + ce;
     loss[1] = dice;
@@ -218,16 +261,16 @@ MSSEG_DEVFN void loss_triple(const float* sums, int stride, float* loss, int N, 
 
 template <int KIND>
 __global__ void dice_ce_finalize_kernel(const float* partial, float* loss, int N, long long S, int C, float snr,
-                                        float sdr, float alpha, float beta) {
+                                        float sdr, float alpha, float beta, int regions) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    loss_triple<KIND>(partial, 4, loss, N, S, C, snr, sdr, alpha, beta);
+    loss_triple<KIND>(partial, 4, loss, N, S, C, snr, sdr, alpha, beta, regions);
 }
 
 // rows [N][nblk][C*7] -> partial[N][C][4], hard[N][C][3] (optional) and the loss triple, one block, fixed order
 template <int KIND>
 __global__ __launch_bounds__(256) void dice_ce_rows_finalize_kernel(const float* rows, int nblk, float* partial, float* hard,
                                                                     float* loss, int N, long long S, int C, float snr,
-                                                                    float sdr, float alpha, float beta) {
+                                                                    float sdr, float alpha, float beta, int regions) {
     __shared__ float tot[8 * 16 * 7];
     const int L = C * 7;
     // thread = (column o, row slot): 256 / L' slots per column add every slot-th row, then the slots are added in order
@@ -267,22 +310,25 @@ __global__ __launch_bounds__(256) void dice_ce_rows_finalize_kernel(const float*
         if (k < 4) partial[(n * C + c) * 4 + k] = tot[i];
         else if (hard) hard[(n * C + c) * 3 + (k - 4)] = tot[i];
     }
-    if (threadIdx.x == 0 && loss) loss_triple<KIND>(tot, 7, loss, N, S, C, snr, sdr, alpha, beta);
+    if (threadIdx.x == 0 && loss) loss_triple<KIND>(tot, 7, loss, N, S, C, snr, sdr, alpha, beta, regions);
 }
 
-template <typename T, int CMAX, int KIND>
+// REGIONS: no softmax Jacobian -- d[c] = (d dice / d p_c) * p_c * (1 - p_c) + the BCE / focal term of channel c alone
+template <typename T, int CMAX, int KIND, bool REGIONS>
 __global__ __launch_bounds__(256) void dice_ce_bwd_kernel(const T* __restrict__ logits, long long ld,
                                                           const void* __restrict__ labels, int label_dtype,
                                                           const float* __restrict__ partial, const float* gscale,
                                                           T* __restrict__ dlogits, long long ldd, int N, long long S,
-                                                          int C, float snr, float sdr, float alpha, float beta) {
+                                                          int C, float snr, float sdr, float alpha, float beta,
+                                                          const msseg_region_masks rm) {
     const long long n = blockIdx.y;
     // per (n, c) constants of d dice / d p (d tversky / d p)
     float ka[CMAX], kb[CMAX];
     const float gs = gscale ? gscale[0] : 1.f;
     const float wd = gs / (float)(N * C);
-    // weight of the per-element term: cross-entropy (mean over N*S) or focal (mean over N*C*S)
-    const float wc = gs / (float)(KIND == KIND_DICE_FOCAL ? (double)N * (double)C * (double)S : (double)N * (double)S);
+    // weight of the per-element term: cross-entropy (mean over N*S), or focal / the regions' BCE (mean over N*C*S)
+    const float wc = gs / (float)((KIND == KIND_DICE_FOCAL || REGIONS) ? (double)N * (double)C * (double)S
+                                                                       : (double)N * (double)S);
 #pragma unroll
     for (int c = 0; c < CMAX; ++c) {
         ka[c] = kb[c] = 0.f;
@@ -304,6 +350,22 @@ __global__ __launch_bounds__(256) void dice_ce_bwd_kernel(const T* __restrict__ 
     const bool vec = ld > 0 && ld * (long long)sizeof(T) == 16 && ldd == ld && C <= DT<T>::EPC &&
                      ((((uintptr_t)logits) | ((uintptr_t)dlogits)) & 15) == 0;
     auto grad = [&](float* x, int lab, float* d) {   // x: logits in, probabilities out; d[c] = d loss / d logit c
+        if constexpr (REGIONS) {
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c) {
+                d[c] = 0.f;
+                if (c < C) {
+                    const float t = region_target(rm, c, lab);
+                    float p, q, L;
+                    sigmoid_parts(x[c], p, q, L);
+                    if constexpr (KIND == KIND_TVERSKY) d[c] = (ka[c] * t + kb[c]) * (p * q);
+                    else d[c] = (ka[c] * t + kb[c] * p) * (p * q);
+                    if constexpr (KIND == KIND_DICE_CE) d[c] += wc * (t > 0.f ? -q : p);   // p - t
+                    else if constexpr (KIND == KIND_DICE_FOCAL) d[c] += wc * focal_grad(x[c], t);
+                }
+            }
+            return;
+        }
         float raw[CMAX];
         if constexpr (KIND == KIND_DICE_FOCAL) {
 #pragma unroll
@@ -524,19 +586,30 @@ template <typename F> void for_kind(int kind, F&& f) {
     else if (kind == KIND_DICE_FOCAL) f(std::integral_constant<int, KIND_DICE_FOCAL>{});
     else f(std::integral_constant<int, KIND_DICE_CE>{});
 }
+// ... and f(kind, std::bool_constant<REGIONS>) with the masks to hand to the kernel by value: those at `masks`, or zeros for
+// the softmax kinds (masks == nullptr), which do not read them
+template <typename F> void for_kind_regions(int kind, const msseg_region_masks* masks, F&& f) {
+    const msseg_region_masks rm = masks ? *masks : msseg_region_masks{};
+    for_kind(kind, [&](auto k) {
+        if (masks) f(k, std::true_type{}, rm);
+        else f(k, std::false_type{}, rm);
+    });
+}
 
 template <typename T, int CMAX>
 int launch_partials(const void* logits, long long ld, const void* labels, int label_dtype, float* partial, float* hard,
-                    int N, long long S, int C, int kind, hipStream_t st, float* rows = nullptr, int* nblk_out = nullptr) {
+                    int N, long long S, int C, int kind, const msseg_region_masks* masks, hipStream_t st,
+                    float* rows = nullptr, int* nblk_out = nullptr) {
     long long blocks = ceil_div_ll(S, 256LL * 8);
     const long long cap = (long long)msseg_num_cus() * 8 / N + 1;
     if (blocks > cap) blocks = cap;
     const long long vpb = ceil_div_ll(S, blocks);
     blocks = ceil_div_ll(S, vpb);
     if (nblk_out) *nblk_out = (int)blocks;
-    for_kind(kind, [&](auto k) {
-        hipLaunchKernelGGL((dice_ce_partials_kernel<T, CMAX, decltype(k)::value>), dim3((unsigned)blocks, N), dim3(256), 0, st,
-                           (const T*)logits, ld, labels, label_dtype, partial, hard, S, C, vpb, rows);
+    for_kind_regions(kind, masks, [&](auto k, auto r, const msseg_region_masks& rm) {
+        hipLaunchKernelGGL((dice_ce_partials_kernel<T, CMAX, decltype(k)::value, decltype(r)::value>),
+                           dim3((unsigned)blocks, N), dim3(256), 0, st, (const T*)logits, ld, labels, label_dtype, partial,
+                           hard, S, C, vpb, rows, rm);
     });
     MSSEG_CHECK_LAUNCH("dice_ce_partials");
     return MSSEG_OK;
@@ -544,14 +617,15 @@ int launch_partials(const void* logits, long long ld, const void* labels, int la
 
 template <typename T, int CMAX>
 int launch_fwd(const void* logits, long long ld, const void* labels, int label_dtype, float* partial, float* hard,
-               float* loss, int N, long long S, int C, float snr, float sdr, int kind, float alpha, float beta, float* rows,
-               hipStream_t st) {
+               float* loss, int N, long long S, int C, float snr, float sdr, int kind, float alpha, float beta,
+               const msseg_region_masks* masks, float* rows, hipStream_t st) {
     int nblk = 0;
-    const int rc = launch_partials<T, CMAX>(logits, ld, labels, label_dtype, partial, hard, N, S, C, kind, st, rows, &nblk);
+    const int rc = launch_partials<T, CMAX>(logits, ld, labels, label_dtype, partial, hard, N, S, C, kind, masks, st, rows,
+                                            &nblk);
     if (rc) return rc;
     for_kind(kind, [&](auto k) {
         hipLaunchKernelGGL(dice_ce_rows_finalize_kernel<decltype(k)::value>, dim3(1), dim3(256), 0, st, rows, nblk, partial,
-                           hard, loss, N, S, C, snr, sdr, alpha, beta);
+                           hard, loss, N, S, C, snr, sdr, alpha, beta, masks ? 1 : 0);
     });
     MSSEG_CHECK_LAUNCH("dice_ce_rows_finalize");
     return MSSEG_OK;
@@ -560,14 +634,14 @@ int launch_fwd(const void* logits, long long ld, const void* labels, int label_d
 template <typename T, int CMAX>
 int launch_bwd(const void* logits, long long ld, const void* labels, int label_dtype, const float* partial,
                const float* gscale, void* dlogits, long long ldd, int N, long long S, int C, float snr, float sdr, int kind,
-               float alpha, float beta, hipStream_t st) {
+               float alpha, float beta, const msseg_region_masks* masks, hipStream_t st) {
     long long blocks = ceil_div_ll(S, 256LL * 4);
     const long long cap = (long long)msseg_num_cus() * 16 / N + 1;
     if (blocks > cap) blocks = cap;
-    for_kind(kind, [&](auto k) {
-        hipLaunchKernelGGL((dice_ce_bwd_kernel<T, CMAX, decltype(k)::value>), dim3((unsigned)blocks, N), dim3(256), 0, st,
-                           (const T*)logits, ld, labels, label_dtype, partial, gscale, (T*)dlogits, ldd, N, S, C, snr, sdr,
-                           alpha, beta);
+    for_kind_regions(kind, masks, [&](auto k, auto r, const msseg_region_masks& rm) {
+        hipLaunchKernelGGL((dice_ce_bwd_kernel<T, CMAX, decltype(k)::value, decltype(r)::value>), dim3((unsigned)blocks, N),
+                           dim3(256), 0, st, (const T*)logits, ld, labels, label_dtype, partial, gscale, (T*)dlogits, ldd, N,
+                           S, C, snr, sdr, alpha, beta, rm);
     });
     MSSEG_CHECK_LAUNCH("dice_ce_bwd");
     return MSSEG_OK;
@@ -587,20 +661,21 @@ int launch_bwd(const void* logits, long long ld, const void* labels, int label_d
         return rc__;                                                                          \
     } while (0)
 
-extern "C" {
-
-int msseg_seg_loss_partials(const void* logits, long long ld, int dtype, const void* labels, int label_dtype,
-                            float* partial, float* hard, int N, long long S, int C, int kind, msseg_stream_t stream) {
+// the bodies of the msseg_seg_loss_* (masks == nullptr) and msseg_region_loss_* entry points
+static int loss_partials(const void* logits, long long ld, int dtype, const void* labels, int label_dtype, float* partial,
+                         float* hard, int N, long long S, int C, int kind, const msseg_region_masks* masks,
+                         msseg_stream_t stream) {
     if (!logits || !labels || (!partial && !hard) || N < 1 || S < 1 || C < 1 || C > 16 || (ld != 0 && ld < C) ||
         label_dtype < 0 || label_dtype > 3 || kind < 0 || kind > 2)
         MSSEG_FAIL(MSSEG_EINVAL, "seg_loss_partials: bad args (C=%d must be 1..16, kind=%d 0..2)", C, kind);
-    DISPATCH_TC(dtype, C, launch_partials, logits, ld, labels, label_dtype, partial, hard, N, S, C, kind,
+    DISPATCH_TC(dtype, C, launch_partials, logits, ld, labels, label_dtype, partial, hard, N, S, C, kind, masks,
                 (hipStream_t)stream);
 }
 
-int msseg_seg_loss_fwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype, float* partial,
-                       float* hard, float* loss, int N, long long S, int C, float smooth_nr, float smooth_dr, int kind,
-                       float alpha, float beta, void* scratch, size_t scratch_bytes, msseg_stream_t stream) {
+static int loss_fwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype, float* partial,
+                    float* hard, float* loss, int N, long long S, int C, float smooth_nr, float smooth_dr, int kind,
+                    float alpha, float beta, const msseg_region_masks* masks, void* scratch, size_t scratch_bytes,
+                    msseg_stream_t stream) {
     if (!logits || !labels || !partial || !loss || N < 1 || N > 8 || S < 1 || C < 1 || C > 16 || (ld != 0 && ld < C) ||
         label_dtype < 0 || label_dtype > 3 || kind < 0 || kind > 2)
         MSSEG_FAIL(MSSEG_EINVAL, "seg_loss_fwd: bad args (1 <= N <= 8, 1 <= C <= 16, 0 <= kind <= 2)");
@@ -609,29 +684,91 @@ int msseg_seg_loss_fwd(const void* logits, long long ld, int dtype, const void* 
         MSSEG_FAIL(MSSEG_EWORKSPACE, "seg_loss_fwd: scratch of %zu bytes needed", need);
     float* rows = (float*)((unsigned char*)scratch + MSSEG_SCRATCH_HEADER_BYTES);
     DISPATCH_TC(dtype, C, launch_fwd, logits, ld, labels, label_dtype, partial, hard, loss, N, S, C, smooth_nr, smooth_dr,
-                kind, alpha, beta, rows, (hipStream_t)stream);
+                kind, alpha, beta, masks, rows, (hipStream_t)stream);
 }
 
-int msseg_seg_loss_finalize(const float* partial, float* loss, int N, long long S, int C, float smooth_nr,
-                            float smooth_dr, int kind, float alpha, float beta, msseg_stream_t stream) {
+static int loss_finalize(const float* partial, float* loss, int N, long long S, int C, float smooth_nr, float smooth_dr,
+                         int kind, float alpha, float beta, int regions, msseg_stream_t stream) {
     if (!partial || !loss || N < 1 || S < 1 || C < 1 || kind < 0 || kind > 2)
         MSSEG_FAIL(MSSEG_EINVAL, "seg_loss_finalize: bad args");
     for_kind(kind, [&](auto k) {
         hipLaunchKernelGGL(dice_ce_finalize_kernel<decltype(k)::value>, dim3(1), dim3(64), 0, (hipStream_t)stream, partial,
-                           loss, N, S, C, smooth_nr, smooth_dr, alpha, beta);
+                           loss, N, S, C, smooth_nr, smooth_dr, alpha, beta, regions);
     });
     MSSEG_CHECK_LAUNCH("seg_loss_finalize");
     return MSSEG_OK;
 }
 
-int msseg_seg_loss_bwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype,
-                       const float* partial, const float* gscale, void* dlogits, long long ldd, int N, long long S, int C,
-                       float smooth_nr, float smooth_dr, int kind, float alpha, float beta, msseg_stream_t stream) {
+static int loss_bwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype, const float* partial,
+                    const float* gscale, void* dlogits, long long ldd, int N, long long S, int C, float smooth_nr,
+                    float smooth_dr, int kind, float alpha, float beta, const msseg_region_masks* masks,
+                    msseg_stream_t stream) {
     if (!logits || !labels || !partial || !dlogits || N < 1 || S < 1 || C < 1 || C > 16 || (ld != 0 && ld < C) ||
         (ldd != 0 && ldd < C) || label_dtype < 0 || label_dtype > 3 || kind < 0 || kind > 2)
         MSSEG_FAIL(MSSEG_EINVAL, "seg_loss_bwd: bad args");
     DISPATCH_TC(dtype, C, launch_bwd, logits, ld, labels, label_dtype, partial, gscale, dlogits, ldd, N, S, C, smooth_nr,
-                smooth_dr, kind, alpha, beta, (hipStream_t)stream);
+                smooth_dr, kind, alpha, beta, masks, (hipStream_t)stream);
+}
+
+extern "C" {
+
+int msseg_seg_loss_partials(const void* logits, long long ld, int dtype, const void* labels, int label_dtype,
+                            float* partial, float* hard, int N, long long S, int C, int kind, msseg_stream_t stream) {
+    return loss_partials(logits, ld, dtype, labels, label_dtype, partial, hard, N, S, C, kind, nullptr, stream);
+}
+
+int msseg_seg_loss_fwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype, float* partial,
+                       float* hard, float* loss, int N, long long S, int C, float smooth_nr, float smooth_dr, int kind,
+                       float alpha, float beta, void* scratch, size_t scratch_bytes, msseg_stream_t stream) {
+    return loss_fwd(logits, ld, dtype, labels, label_dtype, partial, hard, loss, N, S, C, smooth_nr, smooth_dr, kind, alpha,
+                    beta, nullptr, scratch, scratch_bytes, stream);
+}
+
+int msseg_seg_loss_finalize(const float* partial, float* loss, int N, long long S, int C, float smooth_nr,
+                            float smooth_dr, int kind, float alpha, float beta, msseg_stream_t stream) {
+    return loss_finalize(partial, loss, N, S, C, smooth_nr, smooth_dr, kind, alpha, beta, 0, stream);
+}
+
+int msseg_seg_loss_bwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype,
+                       const float* partial, const float* gscale, void* dlogits, long long ldd, int N, long long S, int C,
+                       float smooth_nr, float smooth_dr, int kind, float alpha, float beta, msseg_stream_t stream) {
+    return loss_bwd(logits, ld, dtype, labels, label_dtype, partial, gscale, dlogits, ldd, N, S, C, smooth_nr, smooth_dr,
+                    kind, alpha, beta, nullptr, stream);
+}
+
+// the sigmoid (region) forms: the same passes with the masks; C outside 1..16 is refused before anything is launched
+#define REGION_ARGS_OK(who)                                                                                   \
+    if (!masks || C < 1 || C > 16) MSSEG_FAIL(MSSEG_EINVAL, who ": needs the region masks and 1 <= C <= 16 (got C=%d)", C)
+
+int msseg_region_loss_partials(const void* logits, long long ld, int dtype, const void* labels, int label_dtype,
+                               float* partial, float* hard, int N, long long S, int C, int kind,
+                               const msseg_region_masks* masks, msseg_stream_t stream) {
+    REGION_ARGS_OK("region_loss_partials");
+    return loss_partials(logits, ld, dtype, labels, label_dtype, partial, hard, N, S, C, kind, masks, stream);
+}
+
+int msseg_region_loss_fwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype, float* partial,
+                          float* hard, float* loss, int N, long long S, int C, float smooth_nr, float smooth_dr, int kind,
+                          float alpha, float beta, const msseg_region_masks* masks, void* scratch, size_t scratch_bytes,
+                          msseg_stream_t stream) {
+    REGION_ARGS_OK("region_loss_fwd");
+    return loss_fwd(logits, ld, dtype, labels, label_dtype, partial, hard, loss, N, S, C, smooth_nr, smooth_dr, kind, alpha,
+                    beta, masks, scratch, scratch_bytes, stream);
+}
+
+int msseg_region_loss_finalize(const float* partial, float* loss, int N, long long S, int C, float smooth_nr,
+                               float smooth_dr, int kind, float alpha, float beta, msseg_stream_t stream) {
+    if (C < 1 || C > 16) MSSEG_FAIL(MSSEG_EINVAL, "region_loss_finalize: 1 <= C <= 16 (got C=%d)", C);
+    return loss_finalize(partial, loss, N, S, C, smooth_nr, smooth_dr, kind, alpha, beta, 1, stream);
+}
+
+int msseg_region_loss_bwd(const void* logits, long long ld, int dtype, const void* labels, int label_dtype,
+                          const float* partial, const float* gscale, void* dlogits, long long ldd, int N, long long S,
+                          int C, float smooth_nr, float smooth_dr, int kind, float alpha, float beta,
+                          const msseg_region_masks* masks, msseg_stream_t stream) {
+    REGION_ARGS_OK("region_loss_bwd");
+    return loss_bwd(logits, ld, dtype, labels, label_dtype, partial, gscale, dlogits, ldd, N, S, C, smooth_nr, smooth_dr,
+                    kind, alpha, beta, masks, stream);
 }
 
 int msseg_sw_normalize(float* out, const float* cnt, int C, long long V, msseg_stream_t stream) {

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import hip
+from .utils.arguments import n_label_values, region_table
 
 
 class AugRow(C.Structure):
@@ -82,7 +83,8 @@ def draw_class_rows(rng: np.random.Generator, n, counts, ratios, cfg_like):
 
 def class_crop_config(ratios, dilation=0, n_classes=None):
     """--t_rand_crop_class_ratios / --t_rand_crop_center_dilation -> (ratios as a tuple of floats, or None when the crop is
-    off; dilation); a ValueError names the flag.  n_classes: --output_dim, the number of ratios expected."""
+    off; dilation); a ValueError names the flag.  n_classes: the number of label values (arguments.n_label_values: --output_dim
+    without --label_regions), the number of ratios expected."""
     r = tuple(ratios) if isinstance(ratios, (tuple, list)) else (() if ratios is None else (ratios,))
     n = int(dilation)
     if not 0 <= n <= hip.MAX_CENTER_DILATION:
@@ -103,7 +105,7 @@ def class_crop_config_from_args(cfg):
     """the flags of a parsed command line -> class_crop_config(...); giving the class ratios together with another crop
     flag is a ValueError that names both"""
     ratios, n = class_crop_config(getattr(cfg, "t_rand_crop_class_ratios", ()), getattr(cfg, "t_rand_crop_center_dilation", 0),
-                                  getattr(cfg, "output_dim", None))
+                                  n_label_values(cfg) if hasattr(cfg, "output_dim") else None)
     if ratios is not None:
         for other in ("t_rand_crop_fgbg", "t_rand_spatial_crop"):
             if getattr(cfg, other, False):
@@ -374,13 +376,17 @@ def check_transform_flags(cfg):
             "t_rand_crop_classes": " (crop centres per class: --t_rand_crop_class_ratios NEG POS POS ..., one ratio per "
                                    "class, is the same sampler)",
             "t_rand_crop_dilated_center": " (crop centres near a class: --t_rand_crop_class_ratios R0 R1 ... with "
-                                          "--t_rand_crop_center_dilation 48)"}
+                                          "--t_rand_crop_center_dilation 48)",
+            "t_convert_labels_to_brats": " (overlapping label regions with sigmoid outputs: --label_regions SET=VALUE ..., "
+                                         "e.g. --output_dim 3 --label_regions 1,2,3=1 2,3=2 3=3; MONAI's mapping changed "
+                                         "between releases, so none is built in)"}
     for flag in ("t_percentile_ct_intensity", "t_normalize_channel_wise", "t_crop_foreground_kdiv", "t_rand_crop_classes",
                  "t_rand_crop_dilated_center", "t_convert_labels_to_brats"):
         if getattr(cfg, flag, False) and not (flag == "t_normalize_channel_wise" and not cfg.t_normalize):
             raise NotImplementedError(f"--{flag} is not implemented on the device data path{hint.get(flag, '')}")
     zscore_config(cfg)
     class_crop_config_from_args(cfg)
+    region_table(cfg)
 
 
 def zscore_config(cfg):

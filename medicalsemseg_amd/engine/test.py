@@ -23,7 +23,13 @@ foreground crop, spacing resample and RAS reorientation in one launch.  ``--rest
 the model grid, post-processing if enabled, then the label map is restored.  ``--restore_mode linear``: the blended logits
 are resampled trilinearly and the arg max is taken per native voxel inside the kernel (nnU-Net's order), then
 post-processing runs on the native map; ``pred/`` then holds the unprocessed model-grid arg max.  Batches without the entry
-behave as before."""
+behave as before.
+
+Region-based training (``--label_regions``, an addition of this build): the label map is ``hip.region_decode_u8`` of the
+sigmoid logits (threshold 0, regions painted in their listed order) instead of the arg max; ``class{c}Dice``, ``ppDice`` and
+the Hausdorff meters are per REGION (both maps taken through the region's label set); post-processing runs on the decoded
+map over ``n_label_values`` label values.  ``--restore_mode linear`` is refused: the threshold would have to move inside
+the restore kernel."""
 from __future__ import annotations
 
 import os
@@ -34,13 +40,32 @@ import torch
 from .. import hip, metrics
 from ..data_device import normalised_zero, output_name
 from ..utils import misc
+from ..utils.arguments import n_label_values, region_table
 from .train import _metric_update
 from .utils import sliding_window_inference
 
 
-def label_map(outputs: torch.Tensor) -> torch.Tensor:
-    """logits [1, C, D, H, W] -> uint8 [D, H, W] on the device (engine/test.py:140-141)"""
+def label_map(outputs: torch.Tensor, regions=None) -> torch.Tensor:
+    """logits [1, C, D, H, W] -> uint8 [D, H, W] on the device (engine/test.py:140-141): the arg max, or with a region
+    table (masks, values) the decoded region map (hip.region_decode_u8)"""
+    if regions is not None:
+        return hip.region_decode_u8(outputs[0].float().contiguous(), regions[1])
     return hip.argmax_u8(outputs[0].float().contiguous())
+
+
+def region_lut(mask: int, device) -> torch.Tensor:
+    """uint8 [256]: 1 where the label value belongs to the region of bit mask `mask`, for `lut[label_map.long()]`"""
+    return torch.tensor([(mask >> v) & 1 if v < 32 else 0 for v in range(256)], dtype=torch.uint8, device=device)
+
+
+def region_hausdorff95(maps: torch.Tensor, labels: torch.Tensor, masks) -> np.ndarray:
+    """metrics.hausdorff95 per region: [B, R], both maps taken through each region's label set to {0, 1} (a cold path: a
+    torch index per region), class 1 of the two-class call"""
+    cols = []
+    for m in masks:
+        lut = region_lut(m, maps.device)
+        cols.append(np.asarray(metrics.hausdorff95(lut[maps.long()], lut[labels.long()], 2))[:, 1])
+    return np.stack(cols, axis=1)
 
 
 def post_enabled(cfg) -> bool:
@@ -51,16 +76,22 @@ def post_enabled(cfg) -> bool:
 
 def postprocess(seg: torch.Tensor, cfg, return_stats: bool = False):
     """uint8 [D, H, W] label map -> the map after the steps the --post_* flags ask for (hip.postprocess_u8)"""
-    return hip.postprocess_u8(seg, cfg.output_dim, min_size=int(getattr(cfg, "post_min_size", 0)),
+    return hip.postprocess_u8(seg, n_label_values(cfg), min_size=int(getattr(cfg, "post_min_size", 0)),
                               keep_largest=bool(getattr(cfg, "post_keep_largest", False)),
                               connectivity=int(getattr(cfg, "post_connectivity", 26)),
                               fill_holes=bool(getattr(cfg, "post_fill_holes", False)),
                               hole_connectivity=int(getattr(cfg, "post_hole_connectivity", 26)), return_stats=return_stats)
 
 
-def dice_of_maps(maps: torch.Tensor, labels: torch.Tensor, n_classes: int) -> float:
+def dice_of_maps(maps: torch.Tensor, labels: torch.Tensor, n_classes: int, regions=None) -> float:
     """hard Dice of uint8 maps [B, D, H, W] against labels [B, 1, D, H, W]: per class the mean over the volumes that hold
-    it, then the mean over the classes"""
+    it, then the mean over the classes.  regions (masks, values): per region instead, from hip.region_counts_u8."""
+    if regions is not None:
+        from ..losses import dice_from_counts
+        counts = torch.stack([hip.region_counts_u8(maps[b].contiguous(), labels[b].to(torch.uint8).contiguous(), regions[0])
+                              for b in range(maps.shape[0])])
+        dice = dice_from_counts(counts)[0].cpu()
+        return float(torch.stack([dice[:, c].nanmean() for c in range(dice.shape[1])]).nanmean())
     dice = torch.cat([metrics.dice_from_maps(maps[b], labels[b], n_classes)[0] for b in range(maps.shape[0])]).cpu()
     return float(torch.stack([dice[:, c].nanmean() for c in range(n_classes)]).nanmean())
 
@@ -90,6 +121,13 @@ def eval_model(inferer, model, data_loader, criterion, device, cfg, log_writer=N
     model.eval()
     metric_logger = misc.MetricLogger(delimiter="  ")
     post = post_enabled(cfg)
+    regions = region_table(cfg)
+
+    def hd95(maps):
+        if regions is not None:
+            return region_hausdorff95(maps, labels, regions[0])
+        return metrics.hausdorff95(maps, labels, cfg.output_dim)
+
     for name in ["loss", "mHdorffDist", "mDice"] + ["class" + str(c) + "Dice" for c in range(cfg.output_dim)] \
             + (["ppDice", "ppHdorffDist"] if post else []):
         metric_logger.add_meter(name, misc.SmoothedValue(window_size=1, fmt="{value:.6f}"))
@@ -112,17 +150,17 @@ def eval_model(inferer, model, data_loader, criterion, device, cfg, log_writer=N
             loss = criterion(outputs, labels)
         mDice = _metric_update(metric_logger, criterion, outputs, labels, cfg.output_dim)
         # engine/test.py:31,48-51: Hausdorff-95 of the arg-max map against the labels, all classes, MONAI's "mean" reduction
-        pred_maps = torch.stack([label_map(outputs[b:b + 1]) for b in range(outputs.shape[0])])
-        hdorf, _ = metrics.hausdorff_mean(metrics.hausdorff95(pred_maps, labels, cfg.output_dim))
+        pred_maps = torch.stack([label_map(outputs[b:b + 1], regions) for b in range(outputs.shape[0])])
+        hdorf, _ = metrics.hausdorff_mean(hd95(pred_maps))
         metric_logger.update(loss=loss.item(), mHdorffDist=hdorf, mDice=mDice.item())
         if post:
             # the same two metrics after the clean-up step; the meters above stay those of the unfiltered output
             pp_maps = torch.stack([postprocess(m, cfg) for m in pred_maps])
-            pp_hdorf, _ = metrics.hausdorff_mean(metrics.hausdorff95(pp_maps, labels, cfg.output_dim))
-            metric_logger.update(ppDice=dice_of_maps(pp_maps, labels, cfg.output_dim), ppHdorffDist=pp_hdorf)
+            pp_hdorf, _ = metrics.hausdorff_mean(hd95(pp_maps))
+            metric_logger.update(ppDice=dice_of_maps(pp_maps, labels, cfg.output_dim, regions), ppHdorffDist=pp_hdorf)
         if getattr(cfg, "save_eval_output", False) and cfg.output_dir:
             os.makedirs(cfg.output_dir, exist_ok=True)
-            saved = pp_maps[0] if post else label_map(outputs)
+            saved = pp_maps[0] if post else pred_maps[0]
             np.save(os.path.join(cfg.output_dir, "pred_" + img_name + ".npy"), saved.cpu().numpy())
     metric_logger.synchronize_between_processes()
     print("Evaluation averaged stats:", metric_logger.log_all_average())
@@ -133,6 +171,11 @@ def test_model(model, data_loader, device, cfg, log_writer=None):
     model.eval()
     air_cval = (0.0 - cfg.t_norm_mean) / cfg.t_norm_std if cfg.t_normalize else 0.0
     restore_mode = getattr(cfg, "restore_mode", "nearest")
+    regions = region_table(cfg)
+    if regions is not None and restore_mode == "linear":
+        raise ValueError("--restore_mode linear is not implemented under --label_regions (the sigmoid threshold would have to "
+                         "be taken per native voxel inside the restore kernel): use --restore_mode nearest, which restores "
+                         "the decoded region map")
     only_largest = not (int(getattr(cfg, "post_min_size", 0)) > 1 or getattr(cfg, "post_fill_holes", False))
     for i, batch in enumerate(data_loader):
         inputs = batch["image"].to(device, non_blocking=True)
@@ -144,7 +187,7 @@ def test_model(model, data_loader, device, cfg, log_writer=None):
                                                overlap=cfg.val_infer_overlap, mode="gaussian",
                                                cval=normalised_zero(cfg) if restore is not None else air_cval,
                                                mirror_axes=getattr(cfg, "infer_mirror_axes", ()))
-        seg = label_map(outputs)
+        seg = label_map(outputs, regions)
         # with --restore_mode linear the clean-up runs on the native map instead (below); pred/ stays the raw arg max
         if post_enabled(cfg) and not (restore is not None and restore_mode == "linear"):
             seg, stats = postprocess(seg, cfg, return_stats=True)

@@ -23,7 +23,7 @@ def _metric_update(metric_logger, criterion, outputs, labels, n_cls):
     elif hard is not None:
         scores, not_nans = L.dice_from_counts(hard)
     else:
-        scores, not_nans = L.dice_metric(outputs.detach(), labels)
+        scores, not_nans = L.dice_metric(outputs.detach(), labels, regions=getattr(criterion, "regions", None))
     scores, not_nans = scores.cpu(), not_nans.cpu()
     class_means = torch.zeros(n_cls)
     for c in range(n_cls):

@@ -1,5 +1,6 @@
 """Validation with sliding-window inference: mirror of ``/root/reference/engine/val.py:15-110``.  With a ``--post_*`` flag
-(engine/test.py) it also reports ``ppDice``: the hard Dice of the post-processed arg-max map, as ``eval_model`` does."""
+(engine/test.py) it also reports ``ppDice``: the hard Dice of the post-processed arg-max map, as ``eval_model`` does.  Under
+``--label_regions`` the map is the decoded region map and every Dice is per region."""
 from __future__ import annotations
 
 import math
@@ -8,6 +9,7 @@ import sys
 import torch
 
 from ..utils import misc
+from ..utils.arguments import region_table
 from .test import dice_of_maps, label_map, post_enabled, postprocess
 from .train import _metric_update
 from .utils import mirror_axes_tuple, sliding_window_inference
@@ -17,6 +19,7 @@ def run_validation(model, data_loader, criterion, device, epoch, cfg, log_writer
     model.eval()
     metric_logger = misc.MetricLogger(delimiter="  ")
     post = post_enabled(cfg)
+    regions = region_table(cfg)
     for name in ["loss", "mDice"] + ["class" + str(c) + "Dice" for c in range(cfg.output_dim)] + (["ppDice"] if post else []):
         metric_logger.add_meter(name, misc.SmoothedValue(window_size=100, fmt="{value:.6f}"))
     header = "Validation for epoch: [{}]".format(epoch)
@@ -42,8 +45,8 @@ def run_validation(model, data_loader, criterion, device, epoch, cfg, log_writer
         metric_logger.update(loss=loss_value)
         metric_logger.update(mDice=mDice.item())
         if post:
-            pp_maps = torch.stack([postprocess(label_map(outputs[b:b + 1]), cfg) for b in range(outputs.shape[0])])
-            metric_logger.update(ppDice=dice_of_maps(pp_maps, labels, cfg.output_dim))
+            pp_maps = torch.stack([postprocess(label_map(outputs[b:b + 1], regions), cfg) for b in range(outputs.shape[0])])
+            metric_logger.update(ppDice=dice_of_maps(pp_maps, labels, cfg.output_dim, regions))
         loss_value_reduce = misc.all_reduce_mean(loss_value)
         if log_writer is not None:
             epoch_1000x = int((data_iter_step / len(data_loader) + epoch) * 1000)

@@ -130,6 +130,12 @@ SIGNATURES = {
     "msseg_box_copy": ([_vp, _ll, _i, _i, _i, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp], _i),
     "msseg_merge_gather_fwd": ([_vp, _ll, _i, _i, _i, _vp, _ll, _i, _i, C.c_uint, _i, _vp], _i),
     "msseg_merge_gather_bwd": ([_vp, _ll, _vp, _ll, _i, _i, _i, _i, _i, C.c_uint, _i, _vp], _i),
+    "msseg_region_loss_partials": ([_vp, _ll, _i, _vp, _i, _vp, _vp, _i, _ll, _i, _i, _vp, _vp], _i),
+    "msseg_region_loss_fwd": ([_vp, _ll, _i, _vp, _i, _vp, _vp, _vp, _i, _ll, _i, _f, _f, _i, _f, _f, _vp, _vp, _sz, _vp], _i),
+    "msseg_region_loss_finalize": ([_vp, _vp, _i, _ll, _i, _f, _f, _i, _f, _f, _vp], _i),
+    "msseg_region_loss_bwd": ([_vp, _ll, _i, _vp, _i, _vp, _vp, _vp, _ll, _i, _ll, _i, _f, _f, _i, _f, _f, _vp, _vp], _i),
+    "msseg_region_decode_u8": ([_vp, _i, _ll, _vp, _vp, _vp, _vp], _i),
+    "msseg_region_counts_u8": ([_vp, _vp, _ll, _i, _vp, _vp, _vp, _sz, _vp], _i),
     "msseg_argmax_u8": ([_vp, _i, _ll, _vp, _vp], _i),
     "msseg_resample_nearest_u8": ([_vp, _i, _i, _i, _vp, _i, _i, _i, _vp], _i),
     "msseg_majority_vote_u8": ([_vp, _i, _ll, _i, _vp, _vp], _i),
@@ -1275,20 +1281,42 @@ def add(a, b, y):
 LOSS_DICE_CE, LOSS_TVERSKY, LOSS_DICE_FOCAL = 0, 1, 2
 
 
-def seg_loss_partials(logits, labels, n_cls, kind, channels_last_ld=0, want_hard=False):
+MAX_REGIONS = 16
+
+
+def region_masks(masks, n_regions=None):
+    """the msseg_region_masks image (16 uint32) of a tuple of region bit masks, for the msseg_region_* entry points"""
+    masks = tuple(int(m) for m in masks)
+    if not 1 <= len(masks) <= MAX_REGIONS or (n_regions is not None and len(masks) != n_regions):
+        raise ValueError(f"a region table holds 1..{MAX_REGIONS} masks, one per logits channel: got {len(masks)}"
+                         + (f" for {n_regions} channels" if n_regions is not None else ""))
+    if any(m < 0 or m >= 1 << 32 for m in masks):
+        raise ValueError("region masks are uint32 bit sets of the label values 0..31")
+    return (C.c_uint32 * 16)(*masks)
+
+
+def seg_loss_partials(logits, labels, n_cls, kind, channels_last_ld=0, want_hard=False, regions=None):
     """atomic partial sums (any N) for a loss kind: slot 1 / slot 3 of partial hold (sum p^2, CE sum) | (sum p, 0) | (sum p^2, focal sum).
-    logits: NCDHW (channels_last_ld == 0) or channels-last with voxel stride ld.  Returns (partial, hard)."""
+    logits: NCDHW (channels_last_ld == 0) or channels-last with voxel stride ld.  Returns (partial, hard).
+    regions (here and in the three passes below): a tuple of n_cls region bit masks selects the sigmoid form of the kind
+    (msseg_region_loss_*: the target of channel c is bit `label` of regions[c])."""
     _need_gpu(logits, labels)
     N = logits.shape[0]
     S = labels.numel() // N
     partial = torch.zeros(N, n_cls, 4, dtype=torch.float32, device=logits.device)
     hard = torch.zeros(N, n_cls, 3, dtype=torch.float32, device=logits.device) if want_hard else None
+    if regions is not None:
+        _ck(lib().msseg_region_loss_partials(_p(logits), channels_last_ld, dt(logits), _p(labels), _LAB[labels.dtype],
+                                             _p(partial), _p(hard), N, S, n_cls, kind, region_masks(regions, n_cls),
+                                             _stream()), "region_loss_partials")
+        return partial, hard
     _ck(lib().msseg_seg_loss_partials(_p(logits), channels_last_ld, dt(logits), _p(labels), _LAB[labels.dtype],
                                       _p(partial), _p(hard), N, S, n_cls, kind, _stream()), "seg_loss_partials")
     return partial, hard
 
 
-def seg_loss_fwd(logits, labels, n_cls, smooth_nr, smooth_dr, kind, alpha=0.0, beta=0.0, channels_last_ld=0, want_hard=True):
+def seg_loss_fwd(logits, labels, n_cls, smooth_nr, smooth_dr, kind, alpha=0.0, beta=0.0, channels_last_ld=0, want_hard=True,
+                 regions=None):
     """deterministic fused forward (N <= 8): (partial [N,C,4], hard [N,C,3] or None, loss3 = (total, first term, second term))"""
     _need_gpu(logits, labels)
     N = logits.shape[0]
@@ -1297,25 +1325,39 @@ def seg_loss_fwd(logits, labels, n_cls, smooth_nr, smooth_dr, kind, alpha=0.0, b
     hard = torch.empty(N, n_cls, 3, dtype=torch.float32, device=logits.device) if want_hard else None
     loss = torch.empty(3, dtype=torch.float32, device=logits.device)
     sc = scratch(logits.device)
+    if regions is not None:
+        _ck(lib().msseg_region_loss_fwd(_p(logits), channels_last_ld, dt(logits), _p(labels), _LAB[labels.dtype], _p(partial),
+                                        _p(hard), _p(loss), N, S, n_cls, smooth_nr, smooth_dr, kind, alpha, beta,
+                                        region_masks(regions, n_cls), _p(sc), sc.numel(), _stream()), "region_loss_fwd")
+        return partial, hard, loss
     _ck(lib().msseg_seg_loss_fwd(_p(logits), channels_last_ld, dt(logits), _p(labels), _LAB[labels.dtype], _p(partial),
                                  _p(hard), _p(loss), N, S, n_cls, smooth_nr, smooth_dr, kind, alpha, beta, _p(sc),
                                  sc.numel(), _stream()), "seg_loss_fwd")
     return partial, hard, loss
 
 
-def seg_loss_finalize(partial, S, smooth_nr, smooth_dr, kind, alpha=0.0, beta=0.0):
+def seg_loss_finalize(partial, S, smooth_nr, smooth_dr, kind, alpha=0.0, beta=0.0, regions=None):
     N, Cc = partial.shape[0], partial.shape[1]
     loss = torch.empty(3, dtype=torch.float32, device=partial.device)
+    if regions is not None:
+        _ck(lib().msseg_region_loss_finalize(_p(partial), _p(loss), N, S, Cc, smooth_nr, smooth_dr, kind, alpha, beta,
+                                             _stream()), "region_loss_finalize")
+        return loss
     _ck(lib().msseg_seg_loss_finalize(_p(partial), _p(loss), N, S, Cc, smooth_nr, smooth_dr, kind, alpha, beta, _stream()),
         "seg_loss_finalize")
     return loss
 
 
 def seg_loss_bwd(logits, labels, partial, gscale, dlogits, n_cls, smooth_nr, smooth_dr, kind, alpha=0.0, beta=0.0, ld_in=0,
-                 ld_out=0):
+                 ld_out=0, regions=None):
     _need_gpu(logits, labels, partial, dlogits)
     N = logits.shape[0]
     S = labels.numel() // N
+    if regions is not None:
+        _ck(lib().msseg_region_loss_bwd(_p(logits), ld_in, dt(logits), _p(labels), _LAB[labels.dtype], _p(partial),
+                                        _p(gscale), _p(dlogits), ld_out, N, S, n_cls, smooth_nr, smooth_dr, kind, alpha, beta,
+                                        region_masks(regions, n_cls), _stream()), "region_loss_bwd")
+        return dlogits
     _ck(lib().msseg_seg_loss_bwd(_p(logits), ld_in, dt(logits), _p(labels), _LAB[labels.dtype], _p(partial), _p(gscale),
                                  _p(dlogits), ld_out, N, S, n_cls, smooth_nr, smooth_dr, kind, alpha, beta, _stream()),
         "seg_loss_bwd")
@@ -1403,6 +1445,36 @@ def argmax_u8(logits: torch.Tensor) -> torch.Tensor:
     out = torch.empty(logits.shape[1:], dtype=torch.uint8, device=logits.device)
     _ck(lib().msseg_argmax_u8(_p(logits), logits.shape[0], out.numel(), _p(out), _stream()), "argmax_u8")
     return out
+
+
+def region_decode_u8(logits: torch.Tensor, values, want_bits: bool = False):
+    """sigmoid logits [C, D, H, W] fp32 (one sample, contiguous) -> uint8 [D, H, W]: 0, then values[c] for every channel c in
+    order whose logit is > 0 (later regions paint over earlier ones; NaN does not fire).  want_bits: also the uint16 map of
+    the fired channels (bit c), returned as (map, bits)."""
+    _need_gpu(logits)
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 4
+    values = tuple(int(v) for v in values)
+    if len(values) != logits.shape[0] or any(v < 0 or v > 255 for v in values):
+        raise ValueError(f"region_decode_u8: one value in 0..255 per channel ({logits.shape[0]}), got {values!r}")
+    out = torch.empty(logits.shape[1:], dtype=torch.uint8, device=logits.device)
+    bits = torch.empty(logits.shape[1:], dtype=torch.uint16, device=logits.device) if want_bits else None
+    _ck(lib().msseg_region_decode_u8(_p(logits), logits.shape[0], out.numel(), (C.c_uint8 * 16)(*values), _p(out), _p(bits),
+                                     _stream()), "region_decode_u8")
+    return (out, bits) if want_bits else out
+
+
+def region_counts_u8(pred: torch.Tensor, label: torch.Tensor, masks) -> torch.Tensor:
+    """two uint8 label maps of the same voxel count -> float32 [R, 3] = (|P_r & T_r|, |P_r|, |T_r|) per region r, both maps
+    taken through the region bit masks; integer sums in a fixed order"""
+    _need_gpu(pred, label)
+    assert pred.dtype == torch.uint8 and label.dtype == torch.uint8 and pred.is_contiguous() and label.is_contiguous()
+    assert pred.numel() == label.numel(), "prediction and label differ in voxel count"
+    rm = region_masks(masks)
+    counts = torch.empty(len(masks), 3, dtype=torch.float32, device=pred.device)
+    sc = scratch(pred.device)
+    _ck(lib().msseg_region_counts_u8(_p(pred), _p(label), pred.numel(), len(masks), rm, _p(counts), _p(sc), sc.numel(),
+                                     _stream()), "region_counts_u8")
+    return counts
 
 
 def resample_nearest_u8(src: torch.Tensor, target_size) -> torch.Tensor:

@@ -86,6 +86,11 @@ _SPEC = {
         # --t_rand_crop_center_dilation N takes the centres within L1 distance N (0..254) of a class instead of on it (the
         # reference's --t_rand_crop_dilated_center is N = 48)
         ("--t_rand_crop_class_ratios", "l", [], F), ("--t_rand_crop_center_dilation", "v", 0, I),
+        # region-based training (nnU-Net): one SIGMOID output per region, a region being a union of label values.  One token
+        # SET=VALUE per output channel, --output_dim of them: SET a comma list of label values in 0..31, VALUE the label
+        # (0..255) a voxel gets in the decoded map where the region fires, later regions painted over earlier ones.
+        # `--output_dim 3 --label_regions 1,2,3=1 2,3=2 3=3` is Decathlon BrainTumour's whole tumour / core / enhancing.
+        ("--label_regions", "l", [], S),
     ],
     "file inference": [  # run_predict.py: the files of a data list (engine/test.py, csrc/restore.hip)
         # the section of the data list to predict (labels of "validation" / "training" are ignored)
@@ -125,3 +130,62 @@ def collapse_lists(args):
 
 def get_args(argv=None):
     return collapse_lists(build_parser().parse_args(argv))
+
+
+MAX_REGIONS = 16
+
+
+def parse_label_regions(tokens, output_dim):
+    """``--label_regions`` tokens ``SET=VALUE`` -> ``(masks, values)``: per output channel the uint32 bit mask of the label
+    values in its SET (bit l set: label l belongs to the region) and the label VALUE of the decoded map.  A ValueError names
+    the flag for: a token count other than ``output_dim``, more than 16 regions, an empty SET, a label outside 0..31, a VALUE
+    outside 0..255, a malformed token."""
+    flag = "--label_regions"
+    if isinstance(tokens, str):
+        tokens = [tokens]
+    tokens = list(tokens)
+    if len(tokens) > MAX_REGIONS:
+        raise ValueError(f"{flag}: at most {MAX_REGIONS} regions are supported, got {len(tokens)}")
+    if len(tokens) != int(output_dim):
+        raise ValueError(f"{flag}: one SET=VALUE token per output channel ({output_dim} for --output_dim {output_dim}), "
+                         f"got {len(tokens)}")
+    masks, values = [], []
+    for tok in tokens:
+        head, sep, tail = str(tok).partition("=")
+        try:
+            if not sep:
+                raise ValueError
+            labels = [int(v) for v in head.split(",") if v.strip() != ""]
+            value = int(tail)
+        except ValueError:
+            raise ValueError(f"{flag}: `{tok}` is not SET=VALUE with SET a comma list of integers, e.g. 1,2,3=1") from None
+        if not labels:
+            raise ValueError(f"{flag}: `{tok}` has an empty label set")
+        if any(v < 0 or v > 31 for v in labels):
+            raise ValueError(f"{flag}: `{tok}` names a label outside 0..31")
+        if value < 0 or value > 255:
+            raise ValueError(f"{flag}: `{tok}` has a value outside 0..255")
+        mask = 0
+        for v in labels:
+            mask |= 1 << v
+        masks.append(mask)
+        values.append(value)
+    return tuple(masks), tuple(values)
+
+
+def region_table(cfg):
+    """``(masks, values)`` of ``--label_regions`` (parse_label_regions), or None without the flag"""
+    tokens = getattr(cfg, "label_regions", None)
+    if tokens is None or (not isinstance(tokens, str) and len(tokens) == 0):
+        return None
+    return parse_label_regions(tokens, cfg.output_dim)
+
+
+def n_label_values(cfg):
+    """number of label values of the label maps: ``--output_dim`` for exclusive classes; under ``--label_regions`` one more
+    than the largest label any SET or VALUE names (the output channels are regions then, not label values)"""
+    table = region_table(cfg)
+    if table is None:
+        return cfg.output_dim
+    masks, values = table
+    return 1 + max(max(m.bit_length() - 1 for m in masks), max(values))

@@ -27,7 +27,7 @@ from medicalsemseg_amd.engine.test import eval_model
 from medicalsemseg_amd.losses import build_criterion
 from medicalsemseg_amd.models.model_builder import build_model
 from medicalsemseg_amd.utils import misc
-from medicalsemseg_amd.utils.arguments import get_args
+from medicalsemseg_amd.utils.arguments import get_args, n_label_values
 
 
 def main(cfg):
@@ -45,7 +45,7 @@ def main(cfg):
     criterion = build_criterion(cfg)
     if cfg.synthetic:
         vval = cfg.synthetic_val_size if isinstance(cfg.synthetic_val_size, int) else cfg.synthetic_val_size[0]
-        loader = SyntheticLoader(cfg.synthetic_steps, 1, vval, cfg.in_chans, cfg.output_dim, cfg.seed + 7 + misc.get_rank(),
+        loader = SyntheticLoader(cfg.synthetic_steps, 1, vval, cfg.in_chans, n_label_values(cfg), cfg.seed + 7 + misc.get_rank(),
                                  with_crop_info=False)
     else:
         # the validation list of the data list (its "validation" section, or fold --cv_fold of the seeded split),

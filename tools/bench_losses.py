@@ -1,5 +1,5 @@
-"""Forward + backward time of the three loss kinds (DiceCE, Tversky, DiceFocal) on what the UNet hands over at the flagship
-shape: channels-last bf16 logits rows 2 x 96^3 x 8 (3 classes valid), fp32 labels, gradient rows written in the same layout.
+"""Forward + backward time of the three loss kinds (DiceCE, Tversky, DiceFocal), and of their sigmoid forms under a region
+table (--label_regions; `regions:` rows), on what the UNet hands over at the flagship shape: channels-last bf16 logits rows 2 x 96^3 x 8 (3 classes valid), fp32 labels, gradient rows written in the same layout.
 A pair is the three launches a criterion issues (partials, rows finalize, backward).  All kinds move the same bytes (35.4 MB
 forward, 63.7 MB backward), so DiceCE's time from the same run is the yardstick.  The kinds are timed in alternation: ROUNDS
 replays each of a captured graph of REPS pairs, between device events; median / min / max of the per-pair times in us.
@@ -22,12 +22,14 @@ logits = rows[..., :C].permute(0, 4, 1, 2, 3)
 labels = torch.randint(0, C, (N, 1) + vol, device=dev).float()
 drows = torch.empty_like(rows)
 gscale = torch.ones(1, device=dev)
+REGIONS = (0b110, 0b100, 0b010)      # three overlapping regions over the label values 0..2
 kinds = {"DiceCE": (hip.LOSS_DICE_CE, 0.0, 0.0), "Tversky": (hip.LOSS_TVERSKY, 0.3, 0.7), "DiceFocal": (hip.LOSS_DICE_FOCAL, 0.0, 0.0)}
+kinds.update({"regions:" + k: v + (REGIONS,) for k, v in list(kinds.items())})
 
 
-def pair(kind, alpha, beta):
-    partial, _, loss3 = hip.seg_loss_fwd(logits, labels, C, 1e-5, 1e-5, kind, alpha, beta, LD, want_hard=True)
-    hip.seg_loss_bwd(logits, labels, partial, gscale, drows, C, 1e-5, 1e-5, kind, alpha, beta, LD, LD)
+def pair(kind, alpha, beta, regions=None):
+    partial, _, loss3 = hip.seg_loss_fwd(logits, labels, C, 1e-5, 1e-5, kind, alpha, beta, LD, want_hard=True, regions=regions)
+    hip.seg_loss_bwd(logits, labels, partial, gscale, drows, C, 1e-5, 1e-5, kind, alpha, beta, LD, LD, regions=regions)
     return loss3
 
 
@@ -55,6 +57,6 @@ for _ in range(ROUNDS):
 base = sorted(times["DiceCE"])[ROUNDS // 2]
 for name, ts in times.items():
     ts.sort()
-    print(f"{name:10s} fwd + bwd, {N} x {C} x 96^3 bf16 rows of {LD}: median {ts[ROUNDS // 2]:.1f} us, min {ts[0]:.1f}, "
+    print(f"{name:17s} fwd + bwd, {N} x {C} x 96^3 bf16 rows of {LD}: median {ts[ROUNDS // 2]:.1f} us, min {ts[0]:.1f}, "
           f"max {ts[-1]:.1f} over {ROUNDS} replays of {REPS} pairs; {ts[ROUNDS // 2] / base:.2f} x DiceCE; "
           f"loss {float(losses[name][0]):.5f}")
